@@ -24,9 +24,15 @@ Workloads (--workload; BASELINE.json `configs`):
              are split into N contiguous ranges of equal cost, B is row-sharded, ONE all-gather of B per step over RCCL, no
              collective on C (configs[4]: --rmat-scale 23).
 
-value = useful GFLOP/s of the whole job = 2 * nnz * n_cols / time (dense-block padding is NOT counted).  The JSON line also
-carries the roofline of the dominant kernel and a CPU baseline (the reference's own VBR::multiply compiled into oracle/_ref, or
-the oracle's restatement of it, timed on this box's host: 1 thread and all cores).
+value = useful GFLOP/s of the whole job = 2 * nnz * n_cols / time (dense-block padding is NOT counted).  A plain run does only what
+that figure needs: set up, warm up, time the K steps, print the line.  With --full the JSON line also carries the per-kernel times
+and the roofline of the dominant kernel, a CPU baseline (the reference's own VBR::multiply compiled into oracle/_ref, or the
+oracle's restatement of it, timed on the host: 1 thread and all cores), the parity spot checks of the generated power-law
+inputs and, for the default workload, the benchmark set (`config.suite`).
+
+--dump-outputs DIR: after the timed steps, C of the last step (what a caller of the product receives: n_cols x rows, column-major,
+rows in the reordered order) is written as DIR/C.npy in float32; an output above 60 MiB is written as a fixed, seeded sample of its
+rows (DIR/C_sampled_rows.npy).  The inputs are seeded: the same arguments give the same inputs from run to run.
 
 Timing: a short untimed pre-roll (--settle-ms, default 300 ms of steps) brings the GPU out of its idle clock state -- a freshly
 leased board runs the first few thousand microseconds 20 % below its steady clock -- then W untimed warm-up steps, then
@@ -107,6 +113,27 @@ def _emit(out):
     print(json.dumps(out), flush=True)
 
 
+DUMP_LIMIT_BYTES = 60 << 20
+
+
+def dump_outputs(out_dir, C, n_cols):
+    """--dump-outputs: C (device, n_cols x rows column-major, fp32) as out_dir/C.npy; above DUMP_LIMIT_BYTES a fixed, seeded sample of
+    its rows, in ascending order, as out_dir/C_sampled_rows.npy.  Returns what was written, for the JSON line."""
+    import torch
+    Cv = C.view(n_cols, -1)
+    rows = Cv.shape[1]
+    name = "C"
+    if Cv.numel() * 4 > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (4 * n_cols)
+        pick = np.sort(np.random.Generator(np.random.PCG64(0)).choice(rows, size=keep, replace=False))
+        Cv = Cv[:, torch.from_numpy(pick).to(Cv.device)]
+        name = "C_sampled_rows"
+    arr = Cv.float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {"dir": out_dir, name: list(arr.shape), "of_rows": int(rows)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -123,7 +150,7 @@ def main():
                     help="storage type of A and B on the device (accumulation and C are always fp32); default per workload")
     ap.add_argument("--ncols", type=int, default=None)
     ap.add_argument("--fixed-height", type=int, default=0, help="reorder OFF: fixed block-row height instead of clustering (-a 2 -F 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--graph", action="store_true",
                     help="replay the steps from a captured HIP graph (measured: no gain -- the step is one 60 us kernel and eager launches already queue ahead)")
     ap.add_argument("--workload", choices=["cant", "rmat", "ogbn-like", "rmat-part", "cant-weak"], default=None,
@@ -162,8 +189,12 @@ def main():
                     help="gloo: DEBUG ONLY -- several ranks on ONE GPU (a one-GPU box), collectives staged through host memory; checks the "
                          "multi-rank logic end to end, its timings mean nothing")
     ap.add_argument("--dist-path", action="store_true", help="run the multi-GPU code path even with one rank")
-    ap.add_argument("--no-suite", action="store_true", help="N = 1, default workload: do not append the benchmark set (config.suite: synthetic families + the reference's real matrices)")
-    ap.add_argument("--check-rows", type=int, default=64, help="rmat / ogbn-like: rows of C checked against a float64 evaluation before timing")
+    ap.add_argument("--no-suite", action="store_true", help="--full, N = 1, default workload: do not append the benchmark set (config.suite: synthetic families + the reference's real matrices)")
+    ap.add_argument("--check-rows", type=int, default=64, help="rmat / ogbn-like: rows of C checked against a float64 evaluation before timing (--full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel times + roofline, the CPU baseline, the parity spot checks and (default workload) the benchmark set; "
+                         "a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write C of the last timed step to DIR/*.npy (float32, at most 60 MiB: a seeded sample of rows above)")
     args = ap.parse_args()
     # ---- --gpus N without a launcher: start the N ranks ourselves, as a CHILD process, before anything here touches the GPU ---------
     # (torch is not even imported yet; a process that has initialised the GPU must never be replaced by exec on these boxes)
@@ -229,7 +260,7 @@ def main():
         if not args.rmat_density > 0.0:
             args.rmat_density = 1e-4 if args.rmat_scale != 20 else 1e-3
         import bench_parts
-        bench_parts.run(args, torch, sa, dist, rank, local_rank, world, dev, _emit, cpu_baseline)
+        bench_parts.run(args, torch, sa, dist, rank, local_rank, world, dev, _emit, cpu_baseline, dump_outputs)
         if distributed:
             dist.destroy_process_group()
         return
@@ -482,7 +513,7 @@ def main():
 
     # ---- parity spot check for the generated power-law inputs (full-size parity lives in tests/; this guards the bench line) ----
     check = None
-    if power_law and args.check_rows > 0:
+    if args.full and power_law and args.check_rows > 0:
         Ch = None
         rng = np.random.Generator(np.random.PCG64(11 + rank))
         perm_l = sa.get_permutation(grouping)
@@ -584,18 +615,20 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     ms_per_step = elapsed / args.steps * 1e3
+    dumped = dump_outputs(args.dump_outputs, C, N) if (args.dump_outputs and rank == 0) else None
 
-    # ---- per-kernel device time (HIP events on the launch stream, one pair per kernel launch) ----------------------
-    dmain.set_class_timing(True)
+    # ---- per-kernel device time (--full; HIP events on the launch stream, one pair per kernel launch) ----------------------
     kt, kc = {}, {}
-    for _ in range(min(max(args.steps, 10), 50)):
-        step()
-        for k, v in dmain.class_times().items():
-            kt.setdefault(k, []).append(v)
-        for k, v in dmain.clock_mhz().items():    # s_memtime / s_memrealtime over the kernel: the clock the pipes really ran at
-            if v > 0:
-                kc.setdefault(k, []).append(v)
-    dmain.set_class_timing(False)
+    if args.full:
+        dmain.set_class_timing(True)
+        for _ in range(min(max(args.steps, 10), 50)):
+            step()
+            for k, v in dmain.class_times().items():
+                kt.setdefault(k, []).append(v)
+            for k, v in dmain.clock_mhz().items():    # s_memtime / s_memrealtime over the kernel: the clock the pipes really ran at
+                if v > 0:
+                    kc.setdefault(k, []).append(v)
+        dmain.set_class_timing(False)
     kernel_ms = {k: float(np.mean(v)) for k, v in kt.items()}
     kernel_mhz = {k: float(np.mean(v)) for k, v in kc.items()}
     # A step that is ONE kernel launch (aligned stream plan, one tile type, no sparse part): its duration is the event time
@@ -614,7 +647,7 @@ def main():
         nnz_total = float(tt.item())
     useful_gflops = 2.0 * nnz_total * N / (ms_per_step * 1e-3) / 1e9
     imbalance = None
-    if strong:
+    if strong and args.full:
         tt = torch.tensor([float(sum(kernel_ms.values()))], dtype=torch.float64, device=dev)
         mx, sm = tt.clone(), tt.clone()
         dist.all_reduce(mx, op=dist.ReduceOp.MAX)
@@ -728,10 +761,12 @@ def main():
         roofline["shader_clock_mhz"] = round(kernel_mhz[dom], 0)
     if kernel_mhz.get(dom, 0) > 0 and not h16 and dom != "sparse":
         roofline["frac_at_measured_clock"] = round(dom_tflops / (PEAK_MFMA_F32_TFLOPS * kernel_mhz[dom] / PEAK_CLOCK_MHZ), 4)
+    if not args.full:
+        roofline = None                                  # its kernel times are measured by --full only
 
-    # ---- CPU baseline: the reference's VBR::multiply on this host -- 1 thread (the reference is single-threaded) and all cores -----
+    # ---- CPU baseline (--full): the reference's VBR::multiply on this host -- 1 thread (the reference is single-threaded) and all cores -----
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(sa, args, m, grouping, vb, w, rbs, ff, N, B, ldb, B_gath, emul or world, shard_rows, distributed or bool(emul), h16, torch)
         except Exception as e:  # the baseline is a report, never a reason to lose the measurement
@@ -761,7 +796,7 @@ def main():
             "host_seconds": {"generate": round(t_gen, 2), "reorder": round(t_reorder, 2), "vbs_build": round(t_build, 2)},
             "parallelism": ("single GPU" if not distributed else
                             ("row-range partition x%d by cost (nnz + rows), identical seeded generation + reorder on every rank, B row-sharded, one all-gather "
-                             "per step; kernel-time imbalance max/mean %.3f" % (world, imbalance)) if strong else
+                             "per step%s" % (world, "" if imbalance is None else "; kernel-time imbalance max/mean %.3f" % imbalance)) if strong else
                             ("row-partition x%d, B all-gather%s" % (world, exchange_note)) if ex is None else
                             ("row-partition x%d, B row-block all-to-all (%d blocks sent / %d received by rank 0 per step = %.2f %% of the "
                              "all-gather's traffic), own-shard product overlapped" % (world, ex.n_send, ex.n_recv, 100.0 * ex.needed_fraction))),
@@ -771,8 +806,8 @@ def main():
         "roofline": roofline,
         "cpu_baseline": cpu,
     }
-    # ---- the benchmark SET (BASELINE.json: "... SuiteSparse set"): same run, same box, after the headline measurement ------------------------
-    if not distributed and args.workload == "cant" and not args.matrix and not args.no_suite and args.dtype == "f32":
+    # ---- the benchmark SET (--full; BASELINE.json: "... SuiteSparse set"): same run, same box, after the headline measurement ------------------------
+    if args.full and not distributed and args.workload == "cant" and not args.matrix and not args.no_suite and args.dtype == "f32":
         try:
             import bench_suite
             d.close()
@@ -787,6 +822,8 @@ def main():
         out["config"]["generator"] = gen_stats
     if check is not None:
         out["config"]["parity_spot_check"] = check
+    if dumped is not None:
+        out["config"]["dumped_outputs"] = dumped
     if distributed:
         dist.destroy_process_group()
     _emit(out)

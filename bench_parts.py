@@ -48,7 +48,7 @@ def choose_parts(P, k, cost, seed=17):
     return [0] + rest
 
 
-def run(args, torch, sa, dist, rank, local_rank, world, dev, emit, cpu_baseline):
+def run(args, torch, sa, dist, rank, local_rank, world, dev, emit, cpu_baseline, dump_outputs):
     distributed = world > 1 or args.dist_path
     scale, N, w = args.rmat_scale, args.ncols, args.col_block
     n = 1 << scale
@@ -114,6 +114,7 @@ def run(args, torch, sa, dist, rank, local_rank, world, dev, emit, cpu_baseline)
                ag_ms=0.0)
     worst_check = 0.0
     last = None
+    dumped = None
     for ip in my_parts:
         r0, r1 = cuts[ip]
         t0 = time.time()
@@ -180,9 +181,9 @@ def run(args, torch, sa, dist, rank, local_rank, world, dev, emit, cpu_baseline)
             if float(same.item()) < 1.0:
                 raise SystemExit("rank %d: the chunked all-gather + product differs from the single all-gather + product" % rank)
             del C_one
-        # ---- parity spot check: rows of C against a float64 evaluation on the stored (rounded) values -------------------------
+        # ---- parity spot check (--full): rows of C against a float64 evaluation on the stored (rounded) values -------------------------
         worst = 0.0
-        if args.check_rows > 0:
+        if args.full and args.check_rows > 0:
             rng = np.random.Generator(np.random.PCG64(11 + ip))
             perm_l = sa.get_permutation(grouping)
             heavy = np.argsort(np.diff(m.rowptr)[perm_l])[-2:]                 # the two heaviest rows of the part are always checked
@@ -221,9 +222,11 @@ def run(args, torch, sa, dist, rank, local_rank, world, dev, emit, cpu_baseline)
         elapsed = time.perf_counter() - t_start
         ms = elapsed / args.steps * 1e3
         ev_ms = ev0.elapsed_time(ev1) / args.steps
-        # the all-gather alone (same stream, same fences)
+        if args.dump_outputs and rank == 0 and ip == my_parts[-1]:
+            dumped = dump_outputs(args.dump_outputs, C, N)
+        # the all-gather alone (--full; same stream, same fences)
         ag_ms = 0.0
-        if distributed:
+        if distributed and args.full:
             fence()
             t1 = time.perf_counter()
             for _ in range(min(args.steps, 5)):
@@ -233,13 +236,14 @@ def run(args, torch, sa, dist, rank, local_rank, world, dev, emit, cpu_baseline)
                     dist.all_gather_into_tensor(B_gath, B_shard)
             torch.cuda.synchronize()
             ag_ms = (time.perf_counter() - t1) * 1e3 / min(args.steps, 5)
-        d.set_class_timing(True)
         kt = {}
-        for _ in range(min(max(args.steps, 3), 10)):
-            d.spmm_gathered(B_gath, shard_rows, C, N, accumulate=False, shard_ld=shard_ld)
-            for k_, v_ in d.class_times().items():
-                kt.setdefault(k_, []).append(v_)
-        d.set_class_timing(False)
+        if args.full:                            # per-kernel device times
+            d.set_class_timing(True)
+            for _ in range(min(max(args.steps, 3), 10)):
+                d.spmm_gathered(B_gath, shard_rows, C, N, accumulate=False, shard_ld=shard_ld)
+                for k_, v_ in d.class_times().items():
+                    kt.setdefault(k_, []).append(v_)
+            d.set_class_timing(False)
         kernel_ms = {k_: float(np.mean(v_)) for k_, v_ in kt.items()}
         t_lb, b_alg, b_gather, fl_dense = part_roofline(info, sp, rows_c, n, N, esz, peak_mfma)
         po = {"part": ip, "rows": [int(r0), int(r1)], "nnz": int(m.nztot()), "expected_cost_share": round(float(part_cost[ip] / part_cost.sum()), 5),
@@ -306,7 +310,7 @@ def run(args, torch, sa, dist, rank, local_rank, world, dev, emit, cpu_baseline)
                           "bandwidth, not a fraction of a bound -- with the long rows taken column window by column window it passes what HBM alone delivers).  "
                           "Structurally far from the B-once bound: R-MAT rows do not share columns outside the hub"}
     cpu = None
-    if not args.no_cpu_baseline and last is not None:
+    if args.full and not args.no_cpu_baseline and last is not None:
         m, grouping, rbs = last
         try:
             B_plain = B_gath if shard_ld == shard_rows else B_gath.view(P, N, shard_ld)[:, :, :shard_rows].contiguous().view(-1)     # (the CPU baseline reads the unpadded layout)
@@ -342,7 +346,8 @@ def run(args, torch, sa, dist, rank, local_rank, world, dev, emit, cpu_baseline)
                                      ("single GPU; the %d parts of the %d-rank job one after the other; time = sum over the parts; part-time max/mean %.3f" % (P, P, imbalance)),
                       "timing": "per part: %d warm-up + EXACTLY %d timed products between fences" % (args.warmup, args.steps) + ("" if distributed else "; ms_per_step = sum over the parts"),
                       "host_seconds": {"generate": round(tot["gen"], 2), "reorder": round(tot["reorder"], 2), "vbs_build": round(tot["build"], 2)},
-                      "parts_detail": parts_all, "parity_spot_check": {"rows_per_part": args.check_rows + 2, "max_err_over_sum_abs": worst_check, "tolerance": 1e-5},
+                      "parts_detail": parts_all,
+                      "parity_spot_check": {"rows_per_part": args.check_rows + 2, "max_err_over_sum_abs": worst_check, "tolerance": 1e-5} if args.full else None,
                       "reorder_note": ("on R-MAT inputs the clustering arm has lost to the fixed grid in every measurement (0.1 %: 104.8 against 82.2 ms after 60 s of host "
                                        "reorder; `auto` keeps the fixed grid on 8 of 8 parts): rows of a power-law graph share columns only inside the hub, which the fixed grid "
                                        "already turns into tiles -- the clustering pays off on FEM / banded / clustered families (config.suite of the default line)"),
@@ -350,6 +355,8 @@ def run(args, torch, sa, dist, rank, local_rank, world, dev, emit, cpu_baseline)
            "roofline": roofline, "cpu_baseline": cpu}
     if extrap:
         out["config"]["extrapolated"] = extrap
+    if dumped is not None:
+        out["config"]["dumped_outputs"] = dumped
     if distributed:
         out["config"]["allgather"] = dict(gather_pick or {}, mode=gather_mode, ms_alone=round(float(mx[2]), 4), chunks=int(getattr(args, "ag_chunks", 1)))
         out["config"]["host_seconds_max_rank"] = round(float(mx[3]), 2)

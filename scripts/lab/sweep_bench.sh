@@ -1,4 +1,4 @@
-run() { desc="$1"; shift; env "$@" python bench.py --no-cpu-baseline $ARGS 2>/dev/null | tail -1 | python -c "
+run() { desc="$1"; shift; env "$@" python bench.py --full --no-cpu-baseline $ARGS 2>/dev/null | tail -1 | python -c "
 import sys, json
 d=json.loads(sys.stdin.read()); r=d['roofline']; print('$desc', d['value'], d['ms_per_step'], r['path'], r['achieved'], r['frac'], r['kernels_ms'], r.get('shader_clock_mhz'))"; }
 ARGS=""

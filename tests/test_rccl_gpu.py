@@ -32,7 +32,7 @@ def test_one_rank_under_nccl_all_gather_plus_gathered_product():
     env = dict(os.environ)
     env.update({"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(_free_port()), "RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dist-path", "--backend", "nccl", "--workload", "rmat-part", "--rmat-scale", "16",
-                        "--rmat-density", "1e-3", "--dtype", "bf16", "--ncols", "256", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+                        "--rmat-density", "1e-3", "--dtype", "bf16", "--ncols", "256", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     out = _last_json(p.stdout)
@@ -53,7 +53,7 @@ def test_two_ranks_under_nccl_when_two_gpus_are_visible():
         env.pop(k, None)
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rmat-scale", "16", "--rmat-density", "1e-3", "--dtype", "bf16", "--ncols", "256",
-                        "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     out = _last_json(p.stdout)
     assert out["n_gpus"] == 2 and out["scaling"] == "strong"
