@@ -343,6 +343,23 @@ int sparta_vbs_create_transposed(sparta_vbs_t** out, int64_t rows, int64_t cols,
 int sparta_vbs_spmm_ba(sparta_vbs_t* At, const void* B, int64_t ldb, int32_t M, void* C, int64_t ldc, int32_t accumulate,
                        int32_t ptr_space, void* stream, float* dt_ms);
 
+/* SDDMM on the stored blocks of A: G (+)= (X * Y^T) sampled on A's pattern, in the handle's mab layout -- the gradient of A's values for
+ * C = A * B (X = dC, Y = B).  No reference counterpart (the reference only multiplies).
+ * X: rows x k, column-major, ldx >= rows (the layout of C, rows in the VBS's reordered order; a force_fixed_size padding row is a row like
+ * any other).  Y: cols x k, column-major, ldy >= cols (the layout of B).  G: nztot fp32 values laid out as sparta_vbs_host.mab (for a range
+ * handle the slice of its block-rows, from 0): for block-row ib (rows r0 ..), its block b (block-column jb), in-block column c, row i:
+ *   G[a_off + (b * w + c) * h + i] = sum_n X[r0 + i, n] * Y[jb * w + c, n];   positions with jb * w + c >= cols (ragged last block column) get 0.
+ * accumulate = 0 writes all nztot values, 1 adds to them.  fp32 handles take fp32 X, Y; 16-bit handles take X, Y in the handle's type with
+ * even ldx, ldy and accumulate in fp32 (exact products of the 16-bit inputs).  SPARTA_PTR_HOST: X, Y are fp32 host arrays (rounded on the
+ * device for 16-bit handles), G is a host array, *dt_ms (may be NULL) covers the kernel only; SPARTA_PTR_DEVICE: stream and dt_ms as for
+ * sparta_vbs_spmm.  Any k >= 1.  Offsets into X, Y and G are 64-bit; ldx * k and ldy * k must stay below 2^61 (else SPARTA_ERR_UNSUPPORTED).
+ * SPARTA_ERR_UNSUPPORTED on a handle without the dense blocks of every block-row (made by sparta_vbs_create_from_csr, hence also
+ * sparta_vbs_create_transposed).  The FIRST call on a handle builds and uploads the work list (and, for SPARTA_PTR_HOST, scratch); every
+ * later device-pointer call is kernel launches only and can be captured into a hipGraph -- a call that would still have to allocate while
+ * its stream is being captured returns SPARTA_ERR_UNSUPPORTED. */
+int sparta_vbs_sddmm(sparta_vbs_t* A, const void* X, int64_t ldx, const void* Y, int64_t ldy, int32_t k, float* G, int32_t accumulate,
+                     int32_t ptr_space, void* stream, float* dt_ms);
+
 /* A dense operand that does NOT change between products, prepared once.  The reference's drivers multiply the same B `-x` times
  * (test/cuda/cuda_multiply.cpp:250-269); the sparse-row kernels of a handle read B row-major, so a column-major (the reference's layout)
  * or gathered B is otherwise transposed into per-handle scratch on EVERY product (11 % of a power-law product).

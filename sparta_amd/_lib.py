@@ -38,6 +38,7 @@ SYMBOLS = [
     "sparta_blocking_csv_row", "sparta_degree_permutation", "sparta_vbs_save", "sparta_vbs_load", "sparta_vbs_to_blocked_ell",
     "sparta_vbs_build_partition", "sparta_vbs_partition_check", "sparta_vbs_plan_stats",
     "sparta_vbs_prepare_b", "sparta_vbs_spmm_prepared", "sparta_b_destroy",
+    "sparta_vbs_sddmm",
 ]
 
 
@@ -123,6 +124,7 @@ def _load():
     L.sparta_vbs_spmm_ba.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, C.c_int64, C.c_int32, C.c_int32, vp, f32p]
     L.sparta_vbs_spmm.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp,
                                   C.c_int32, f32p]
+    L.sparta_vbs_sddmm.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int32, f32p, C.c_int32, C.c_int32, vp, f32p]
     L.sparta_vbs_spmm_gathered.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32, f32p]
     L.sparta_vbs_spmm_gathered_ld.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32, f32p]
     L.sparta_pack_blocks.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp]

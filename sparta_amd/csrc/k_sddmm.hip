@@ -1,0 +1,218 @@
+// k_sddmm.hip -- sampled dense-dense product on the stored blocks of a VBS handle (sparta_vbs_sddmm):
+//   G[a_off + q * h + i] (+)= sum_n X[c_row + i, n] * Y[jab[b] * w + c, n]      stored column q = b * w + c of the block-row
+// the gradient of A's values for C = A * B (X = dC, Y = B).  Same work as the forward product: dense MFMA tiles, the reduction over k.
+//
+// One workgroup (4 waves) per work item = (block-row, tile of <= 32 of its rows, up to kSdGroups groups of 32 stored columns); wave v takes
+// the item's groups v, v + 4, v + 8, v + 12.  Stored columns are taken in mab order, so narrow blocks (w < 32) pack into one group; each lane
+// gathers the column of Y its stored column belongs to.  k is walked in chunks of KC: the X tile of the chunk (32 rows x KC) is staged in LDS
+// once and read by all four waves for every one of their groups.
+//
+// The operands are swapped (A operand = Y, B operand = X), so an accumulator holds ROW i = lane & 31 of the tile and stored column
+// (r & 3) + 8 (r >> 2) + 4 (lane >> 5) in register r: a store instruction writes 32 consecutive rows of one stored column = 32 consecutive
+// floats of mab (no transpose, any alignment).
+//
+// fp32: v_mfma_f32_32x32x2_f32.  Lane l holds entity l & 31 (row of X / stored column) at k = l >> 5: for a fixed n, 32 consecutive rows of the
+//       column-major X (Y) are one coalesced load; Y goes straight to registers, X through the LDS tile [KC][32].
+// 16-bit: v_mfma_f32_32x32x16_{f16,bf16} wants 8 consecutive k per lane, which column-major X and Y have strided.  Both are staged as
+//       [k][32 entities] images (coalesced row loads; X once per workgroup, Y per wave and group) and read back with ds_read_b64_tr_b16.
+//       EXEC is all ones at every transposed read (the group loops are wave-uniform), the LDS image is one 16-byte aligned static object.
+#include "vbs_kernel_common.hpp"
+
+namespace sparta_dev {
+
+namespace {
+
+constexpr int kSdWaves = 4;
+constexpr int kSdGpw = kSdGroups / kSdWaves;      // groups per wave
+constexpr int kKC32 = 32;                          // k chunk, fp32 (16 MFMA steps of depth 2)
+constexpr int kKC16 = 32;                          // k chunk, 16-bit (2 MFMA steps of depth 16)
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+
+// the 32 x 32 accumulator -> G: lane (i = lane & 31, g = lane >> 5), register r: stored column q0 + (r & 3) + 8 (r >> 2) + 4 g, row i
+__device__ __forceinline__ void sd_store(const f32x16& acc, float* G, int64_t base, int64_t q0, int64_t nq, int h, int mt, int lane, int accumulate) {
+    const int i = lane & 31;
+    if (i >= mt) return;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int64_t q = q0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (q >= nq) continue;
+        float* dst = G + base + q * h + i;
+        *dst = accumulate ? *dst + acc[r] : acc[r];
+    }
+}
+
+// the stored column of lane (lane & 31) in group gi of the item: its column of Y, or -1 (past the block-row's stored columns, or ragged)
+__device__ __forceinline__ int64_t sd_column(const SddmmParams& p, const BlockRowDesc& br, int64_t nq, int64_t q) {
+    if (q >= nq) return -1;
+    const int64_t b = q / p.w, c = q - b * p.w;
+    const int64_t col = (int64_t)p.jab[br.jab_off + b] * p.w + c;
+    return col < p.cols ? col : -1;
+}
+
+__global__ __launch_bounds__(kThreads) void vbs_sddmm_f32_kernel(const SddmmParams p) {
+    __shared__ float xs[kKC32][32];
+    const SddmmItem it = p.items[blockIdx.x];
+    const BlockRowDesc br = p.brows[it.brow];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int mt = min(32, br.h - it.r0);
+    const int64_t nq = (int64_t)br.nb * p.w;
+    const float* X = (const float*)p.X + (int64_t)br.c_row + it.r0;
+    const float* Y = (const float*)p.Y;
+    const float* yp[kSdGpw];
+    bool ok[kSdGpw];
+#pragma unroll
+    for (int t = 0; t < kSdGpw; t++) {
+        const int64_t col = sd_column(p, br, nq, (int64_t)(it.g0 + wv + kSdWaves * t) * 32 + (lane & 31));
+        ok[t] = col >= 0 && wv + kSdWaves * t < it.ng;
+        yp[t] = Y + (ok[t] ? col : 0) + (int64_t)(lane >> 5) * p.ldy;
+    }
+    f32x16 acc[kSdGpw];
+#pragma unroll
+    for (int t = 0; t < kSdGpw; t++)
+        for (int r = 0; r < 16; r++) acc[t][r] = 0.0f;
+    for (int n0 = 0; n0 < p.k; n0 += kKC32) {
+        if (n0 > 0) __syncthreads();
+#pragma unroll
+        for (int e0 = 0; e0 < kKC32 * 32; e0 += kThreads) {
+            const int e = e0 + tid, r = e & 31, nn = e >> 5;
+            xs[nn][r] = (r < mt && n0 + nn < p.k) ? X[r + (int64_t)(n0 + nn) * p.ldx] : 0.0f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < kSdGpw; t++) {
+            if (wv + kSdWaves * t >= it.ng) break;                      // wave-uniform
+            float yv[kKC32 / 2];
+#pragma unroll
+            for (int s = 0; s < kKC32 / 2; s++) {
+                const int n = n0 + 2 * s + (lane >> 5);
+                yv[s] = (ok[t] && n < p.k) ? yp[t][(int64_t)(2 * s) * p.ldy] : 0.0f;
+            }
+            yp[t] += (int64_t)kKC32 * p.ldy;
+#pragma unroll
+            for (int s = 0; s < kKC32 / 2; s++)
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(yv[s], xs[2 * s + (lane >> 5)][lane & 31], acc[t], 0, 0, 0);
+        }
+    }
+    const int64_t base = br.a_off + it.r0;
+#pragma unroll
+    for (int t = 0; t < kSdGpw; t++) {
+        if (wv + kSdWaves * t >= it.ng) break;
+        sd_store(acc[t], p.G, base, (int64_t)(it.g0 + wv + kSdWaves * t) * 32, nq, br.h, mt, lane, p.accumulate);
+    }
+}
+
+// 8 consecutive k (kb + 8 (lane >> 5) .. + 7) of entity lane & 31 from a [k][32] image of 16-bit values: two transposed reads.  Lane 4q + p of a
+// 16-lane group addresses row kb + 8 (lane >> 5) + 4 t + q, entities 16 ((lane >> 4) & 1) + 4 p .. + 3; lane i of the group receives entity i.
+// A 32-lane half reads 4 whole 64-byte rows: conflict-free.
+__device__ __forceinline__ s16x8 sd_tr_frag(const uint16_t* img, int kb, int lane) {
+    const int off = (kb + 8 * (lane >> 5) + ((lane & 15) >> 2)) * 32 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+    const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + off));
+    const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + off + 4 * 32));
+    return s16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+}
+
+struct SdLds16 {
+    uint16_t x[kKC16][32];                          // X tile of the chunk, [k][row]
+    uint16_t y[kSdWaves][kSdGpw][kKC16][32];        // per wave and group: Y of the chunk, [k][stored column]
+};
+
+// VEC (w, ldy multiples of 8, Y 16-byte aligned): a run of 8 stored columns is 8 consecutive columns of Y, 16 aligned bytes -- one load per lane
+// puts 8 columns of one k in the image (4 lanes a row of it); otherwise every lane gathers its own column, one 16-bit load per k
+template <bool BF16, bool VEC>
+__global__ __launch_bounds__(kThreads) void vbs_sddmm_h16_kernel(const SddmmParams p) {
+    __shared__ __attribute__((aligned(16))) SdLds16 lds;   // (the only LDS object: its base, and every row, is 16-byte aligned)
+    const SddmmItem it = p.items[blockIdx.x];
+    const BlockRowDesc br = p.brows[it.brow];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int mt = min(32, br.h - it.r0);
+    const int64_t nq = (int64_t)br.nb * p.w;
+    const uint16_t* X = (const uint16_t*)p.X + (int64_t)br.c_row + it.r0;
+    const uint16_t* Y = (const uint16_t*)p.Y;
+    const uint16_t* yp[kSdGpw];
+    bool ok[kSdGpw], full[kSdGpw];
+#pragma unroll
+    for (int t = 0; t < kSdGpw; t++) {
+        const int64_t q0 = (int64_t)(it.g0 + wv + kSdWaves * t) * 32;
+        const int64_t col = VEC ? sd_column(p, br, nq, q0 + 8 * (lane & 3)) : sd_column(p, br, nq, q0 + (lane & 31));
+        ok[t] = col >= 0 && wv + kSdWaves * t < it.ng;
+        yp[t] = Y + (ok[t] ? col : 0) + (int64_t)(VEC ? lane >> 2 : lane >> 5) * p.ldy;
+        full[t] = ok[t] && col + 8 <= p.cols;
+    }
+    f32x16 acc[kSdGpw];
+#pragma unroll
+    for (int t = 0; t < kSdGpw; t++)
+        for (int r = 0; r < 16; r++) acc[t][r] = 0.0f;
+    for (int n0 = 0; n0 < p.k; n0 += kKC16) {
+        if (n0 > 0) __syncthreads();
+#pragma unroll
+        for (int e0 = 0; e0 < kKC16 * 32; e0 += kThreads) {
+            const int e = e0 + tid, r = e & 31, nn = e >> 5;
+            lds.x[nn][r] = (r < mt && n0 + nn < p.k) ? X[r + (int64_t)(n0 + nn) * p.ldx] : (uint16_t)0;
+        }
+#pragma unroll
+        for (int t = 0; t < kSdGpw; t++) {
+            if (wv + kSdWaves * t >= it.ng) break;
+            if constexpr (VEC) {
+#pragma unroll
+                for (int s = 0; s < kKC16 / 16; s++) {
+                    const int nn = (lane >> 2) + 16 * s;
+                    const uint16_t* src = yp[t] + (int64_t)(n0 + 16 * s) * p.ldy;
+                    u32x4 v = {0u, 0u, 0u, 0u};
+                    if (full[t] && n0 + nn < p.k) v = *(const u32x4*)src;
+                    else if (ok[t] && n0 + nn < p.k) {                  // the ragged last block column: 1..7 of the 8 columns exist
+                        const int64_t col = (src - Y) % p.ldy;
+#pragma unroll
+                        for (int e = 0; e < 8; e++)
+                            if (col + e < p.cols) v[e >> 1] |= (uint32_t)src[e] << (16 * (e & 1));
+                    }
+                    *(u32x4*)&lds.y[wv][t][nn][8 * (lane & 3)] = v;
+                }
+            } else {
+#pragma unroll
+                for (int s = 0; s < kKC16 / 2; s++) {
+                    const int n = n0 + 2 * s + (lane >> 5);
+                    lds.y[wv][t][2 * s + (lane >> 5)][lane & 31] = (ok[t] && n < p.k) ? yp[t][(int64_t)(n0 + 2 * s) * p.ldy] : (uint16_t)0;
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < kKC16 / 16; m++) {
+            const s16x8 xf = sd_tr_frag(&lds.x[0][0], 16 * m, lane);
+#pragma unroll
+            for (int t = 0; t < kSdGpw; t++) {
+                if (wv + kSdWaves * t >= it.ng) break;
+                const s16x8 yf = sd_tr_frag(&lds.y[wv][t][0][0], 16 * m, lane);
+                if constexpr (BF16) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, yf), __builtin_bit_cast(bf16x8, xf), acc[t], 0, 0, 0);
+                else acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, yf), __builtin_bit_cast(f16x8, xf), acc[t], 0, 0, 0);
+            }
+        }
+    }
+    const int64_t base = br.a_off + it.r0;
+#pragma unroll
+    for (int t = 0; t < kSdGpw; t++) {
+        if (wv + kSdWaves * t >= it.ng) break;
+        sd_store(acc[t], p.G, base, (int64_t)(it.g0 + wv + kSdWaves * t) * 32, nq, br.h, mt, lane, p.accumulate);
+    }
+}
+
+}  // namespace
+
+void launch_sddmm(int dtype, unsigned n_items, hipStream_t st, const SddmmParams& p) {
+    if (n_items == 0) return;
+    const bool vec = p.w % 8 == 0 && p.ldy % 8 == 0 && (uintptr_t)p.Y % 16 == 0;
+    if (dtype == SPARTA_F32) hipLaunchKernelGGL(vbs_sddmm_f32_kernel, dim3(n_items), dim3(kThreads), 0, st, p);
+    else if (dtype == SPARTA_BF16 && vec) hipLaunchKernelGGL((vbs_sddmm_h16_kernel<true, true>), dim3(n_items), dim3(kThreads), 0, st, p);
+    else if (dtype == SPARTA_BF16) hipLaunchKernelGGL((vbs_sddmm_h16_kernel<true, false>), dim3(n_items), dim3(kThreads), 0, st, p);
+    else if (vec) hipLaunchKernelGGL((vbs_sddmm_h16_kernel<false, true>), dim3(n_items), dim3(kThreads), 0, st, p);
+    else hipLaunchKernelGGL((vbs_sddmm_h16_kernel<false, false>), dim3(n_items), dim3(kThreads), 0, st, p);
+}
+
+}  // namespace sparta_dev

@@ -38,8 +38,8 @@ struct CaptureScope {
     }
     ~CaptureScope() { g_capturing = false; }
 };
-int capture_refusal(const char* what) {
-    return sparta::fail(SPARTA_ERR_UNSUPPORTED, std::string("sparta_vbs_spmm: the stream is being captured and this call still has to ") + what +
+int capture_refusal(const char* what, const char* entry = "sparta_vbs_spmm") {
+    return sparta::fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the stream is being captured and this call still has to " + what +
                                                  " -- run it once outside the capture first");
 }
 
@@ -115,6 +115,9 @@ void destroy_impl(sparta_vbs* v) {
     if (v->d_Brm) (void)hipFree(v->d_Brm);
     if (v->d_B) (void)hipFree(v->d_B);
     if (v->d_C) (void)hipFree(v->d_C);
+    if (v->d_sd_items) (void)hipFree(v->d_sd_items);
+    if (v->d_sd_ws) (void)hipFree(v->d_sd_ws);
+    if (v->d_sd_h16) (void)hipFree(v->d_sd_h16);
     if (v->ev0) (void)hipEventDestroy(v->ev0);
     if (v->ev1) (void)hipEventDestroy(v->ev1);
     for (int c = 0; c < 4; c++)
@@ -2144,3 +2147,105 @@ int sparta_pack_blocks(const void* src, int64_t block_bytes, const int32_t* ids_
 }
 
 }  // extern "C"
+
+// ---- SDDMM (k_sddmm.hip) ----------------------------------------------------------------------------------------------------------------
+namespace {
+
+// the work list: per block-row with stored blocks, per tile of <= 32 of its rows, its groups of 32 stored columns in runs of <= kSdGroups
+// (built on the host from the block-row descriptors the handle already holds, at the first call)
+int ensure_sddmm_items(sparta_vbs_t* A) {
+    using sparta::fail;
+    if (A->n_sd_items >= 0) return SPARTA_OK;
+    if (g_capturing) return capture_refusal("build and upload its work list", "sparta_vbs_sddmm");
+    std::vector<BlockRowDesc> brows((size_t)A->n_brows);
+    if (A->n_brows > 0) HIP_TRY(hipMemcpy(brows.data(), A->d_brows, brows.size() * sizeof(BlockRowDesc), hipMemcpyDeviceToHost));
+    std::vector<SddmmItem> items;
+    for (int64_t ib = 0; ib < A->n_brows; ib++) {
+        const BlockRowDesc& br = brows[(size_t)ib];
+        const int64_t n_groups = ((int64_t)br.nb * A->w + 31) / 32;
+        for (int32_t r0 = 0; r0 < br.h; r0 += 32)
+            for (int64_t g0 = 0; g0 < n_groups; g0 += kSdGroups)
+                items.push_back(SddmmItem{(int32_t)ib, r0, (int32_t)g0, (int32_t)std::min<int64_t>(kSdGroups, n_groups - g0)});
+    }
+    if ((int64_t)items.size() > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_sddmm: more than 2^31 - 1 work items");
+    if (!items.empty()) {
+        HIP_TRY(hipMalloc((void**)&A->d_sd_items, items.size() * sizeof(SddmmItem)));
+        HIP_TRY(hipMemcpy(A->d_sd_items, items.data(), items.size() * sizeof(SddmmItem), hipMemcpyHostToDevice));
+    }
+    A->n_sd_items = (int64_t)items.size();
+    return SPARTA_OK;
+}
+
+int sddmm_impl(sparta_vbs_t* A, const void* X, int64_t ldx, const void* Y, int64_t ldy, int32_t k, float* G, int32_t accumulate, int32_t ptr_space,
+               void* stream, float* dt_ms) {
+    using sparta::fail;
+    if (!A || !X || !Y || !G) return fail(SPARTA_ERR_INVALID, "sparta_vbs_sddmm: NULL argument");
+    if (k <= 0) return fail(SPARTA_ERR_INVALID, "sparta_vbs_sddmm: k must be > 0");
+    if (ptr_space != SPARTA_PTR_HOST && ptr_space != SPARTA_PTR_DEVICE) return fail(SPARTA_ERR_INVALID, "sparta_vbs_sddmm: bad ptr_space");
+    if (ldx < A->rows || ldy < A->cols) return fail(SPARTA_ERR_INVALID, "sparta_vbs_sddmm: ldx < rows or ldy < cols");
+    if (ldx > (INT64_C(1) << 61) / k || ldy > (INT64_C(1) << 61) / k) return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_sddmm: ldx * k or ldy * k beyond 2^61");
+    const bool h16 = A->dtype != SPARTA_F32;
+    if (h16 && ptr_space == SPARTA_PTR_DEVICE && ((ldx | ldy) & 1)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_sddmm: 16-bit handles need even ldx, ldy");
+    if (A->ext_sparse)
+        return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_sddmm: the handle does not hold the dense blocks of every block-row (made by sparta_vbs_create_from_csr)");
+
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, "sparta_vbs_sddmm: hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, ptr_space == SPARTA_PTR_DEVICE);
+    if (g_capturing && dt_ms) return capture_refusal("time the product (dt_ms != NULL synchronises)", "sparta_vbs_sddmm");
+    if (int rc = ensure_sddmm_items(A)) return rc;
+
+    const void* dX = X;
+    const void* dY = Y;
+    float* dG = G;
+    int64_t kx = ldx, ky = ldy;
+    const size_t x_elems = (size_t)ldx * (size_t)(k - 1) + (size_t)A->rows, y_elems = (size_t)ldy * (size_t)(k - 1) + (size_t)A->cols;
+    const size_t g_elems = (size_t)A->nztot;
+    if (ptr_space == SPARTA_PTR_HOST) {
+        // host in, host out: X, Y, G staged in one device buffer; 16-bit handles round X, Y on the device
+        if (int rc = ensure_scratch(&A->d_sd_ws, &A->d_sd_ws_bytes, (x_elems + y_elems + g_elems) * sizeof(float))) return rc;
+        float* ws = (float*)A->d_sd_ws;
+        HIP_TRY(hipMemcpyAsync(ws, X, x_elems * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ws + x_elems, Y, y_elems * sizeof(float), hipMemcpyHostToDevice, st));
+        if (accumulate && g_elems > 0) HIP_TRY(hipMemcpyAsync(ws + x_elems + y_elems, G, g_elems * sizeof(float), hipMemcpyHostToDevice, st));
+        dX = ws; dY = ws + x_elems; dG = ws + x_elems + y_elems;
+        if (h16) {
+            kx = (A->rows + 7) / 8 * 8; ky = (A->cols + 7) / 8 * 8;       // (multiples of 8: the 16-byte loads of k_sddmm.hip)
+            const size_t hx = (size_t)kx * (size_t)k, hy = (size_t)ky * (size_t)k;
+            if (int rc = ensure_scratch(&A->d_sd_h16, &A->d_sd_h16_bytes, (hx + hy) * sizeof(uint16_t))) return rc;
+            uint16_t* hw = (uint16_t*)A->d_sd_h16;
+            launch_convert_h16(A->dtype == SPARTA_BF16, st, ws, ldx, A->rows, k, hw, kx);
+            launch_convert_h16(A->dtype == SPARTA_BF16, st, ws + x_elems, ldy, A->cols, k, hw + hx, ky);
+            HIP_TRY(hipGetLastError());
+            dX = hw; dY = hw + hx;
+        }
+    }
+    SddmmParams p;
+    p.brows = A->d_brows; p.jab = A->d_jab; p.items = A->d_sd_items;
+    p.X = dX; p.Y = dY; p.G = dG;
+    p.ldx = kx; p.ldy = ky; p.cols = A->cols;
+    p.k = k; p.w = (int32_t)A->w; p.accumulate = accumulate != 0; p.pad = 0;
+    if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
+    launch_sddmm(A->dtype, (unsigned)A->n_sd_items, st, p);
+    HIP_TRY(hipGetLastError());
+    if (dt_ms) {
+        HIP_TRY(hipEventRecord(A->ev1, st));
+        HIP_TRY(hipEventSynchronize(A->ev1));
+        HIP_TRY(hipEventElapsedTime(dt_ms, A->ev0, A->ev1));
+    }
+    if (ptr_space == SPARTA_PTR_HOST) {
+        if (g_elems > 0) HIP_TRY(hipMemcpyAsync(G, dG, g_elems * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return SPARTA_OK;
+}
+
+}  // namespace
+
+extern "C" int sparta_vbs_sddmm(sparta_vbs_t* A, const void* X, int64_t ldx, const void* Y, int64_t ldy, int32_t k, float* G, int32_t accumulate,
+                                int32_t ptr_space, void* stream, float* dt_ms) {
+    SPARTA_GUARD_BEGIN
+    return sddmm_impl(A, X, ldx, Y, ldy, k, G, accumulate, ptr_space, stream, dt_ms);
+    SPARTA_GUARD_END("sparta_vbs_sddmm")
+}

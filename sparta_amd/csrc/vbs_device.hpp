@@ -238,6 +238,21 @@ struct BlockRowDesc {
     int32_t nb, h, c_row, pad;
 };
 
+// SDDMM (k_sddmm.hip): one work item = one block-row, one tile of <= 32 of its rows, and up to kSdGroups groups of 32 stored columns
+// (stored column q = b * w + c of the block-row, the mab order; group g = columns 32 g .. 32 g + 31)
+constexpr int kSdGroups = 16;
+struct SddmmItem { int32_t brow, r0, g0, ng; };
+struct SddmmParams {
+    const BlockRowDesc* brows;
+    const int32_t* jab;
+    const SddmmItem* items;
+    const void* X;                  // rows x k, column-major (fp32, or the handle's 16-bit type)
+    const void* Y;                  // cols x k, column-major
+    float* G;                       // nztot values in the mab layout
+    int64_t ldx, ldy, cols;
+    int32_t k, w, accumulate, pad;
+};
+
 #define HIP_TRY(expr)                                                                                   \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \
@@ -381,6 +396,13 @@ struct sparta_vbs {
     size_t d_B_bytes = 0;
     void* d_C = nullptr;
     size_t d_C_bytes = 0;
+    // SDDMM (sparta_vbs_sddmm): the work list, built at the first call; host-pointer calls stage X, Y, G (and 16-bit X, Y) in scratch
+    sparta_dev::SddmmItem* d_sd_items = nullptr;
+    int64_t n_sd_items = -1;               // -1: not built yet
+    void* d_sd_ws = nullptr;
+    size_t d_sd_ws_bytes = 0;
+    void* d_sd_h16 = nullptr;
+    size_t d_sd_h16_bytes = 0;
 };
 
 namespace sparta_dev {
@@ -421,6 +443,8 @@ void launch_b_to_row_major(bool is16, unsigned grid, hipStream_t st, const void*
 // k_union.hip
 void launch_union_f32(unsigned n_slabs, hipStream_t st, const UnionParams& p);
 void launch_union_h16(bool bf16, unsigned n_slabs, hipStream_t st, const UnionParams& p);   // 16-bit handles: p.B = the row-major 16-bit B, side.A = 16-bit slices
+// k_sddmm.hip: one workgroup per work item (n_items <= 2^31 - 1); dtype = SPARTA_F32 / F16 / BF16
+void launch_sddmm(int dtype, unsigned n_items, hipStream_t st, const SddmmParams& p);
 // k_colres.hip
 int launch_colres(int nc, const ColresParams& p, size_t lds_bytes, hipStream_t st);     // nc = 1..4 columns per workgroup; 0 or a hipError_t
 int colres_max_slices(int nc);                                                          // slices the nc-column kernel holds sums for

@@ -185,6 +185,55 @@ class DeviceVBS:
                                   C.byref(dt) if timed else None))
         return dt.value if timed else None
 
+    def _nztot(self):
+        """stored elements of the handle (fixed at creation: read once)"""
+        if getattr(self, "_nztot_cached", None) is None:
+            self._nztot_cached = self.info()["nztot"]
+        return self._nztot_cached
+
+    def sddmm(self, X, Y, G_out, k, accumulate=False, ldx=None, ldy=None, timed=False, stream=None):
+        """G (+)= (X * Y^T) sampled on the stored blocks (sparta_vbs_sddmm), device tensors: X rows x k and Y cols x k, column-major (ldx, ldy),
+        in the handle's B dtype; G_out float32 with >= nztot elements, in the mab layout of the handle.  With X = dC and Y = B of C = A * B,
+        G is the gradient of A's stored values.  Stream-ordered on torch's current stream.  Returns kernel ms if timed else None."""
+        import torch
+        want = {_lib.F32: torch.float32, _lib.F16: torch.float16, _lib.BF16: torch.bfloat16}[self.dtype]
+        if not (X.is_cuda and Y.is_cuda and G_out.is_cuda and X.dtype == want and Y.dtype == want and G_out.dtype == torch.float32):
+            raise ValueError("X and Y must be %s tensors and G a float32 tensor, all on the GPU" % want)
+        if X.device.index != self.device or Y.device.index != self.device or G_out.device.index != self.device:
+            raise ValueError("X, Y and G must live on device %d" % self.device)
+        k = int(k)
+        if k <= 0:
+            raise ValueError("k must be > 0")
+        ldx = self.rows if ldx is None else int(ldx)
+        ldy = self.cols if ldy is None else int(ldy)
+        nztot = self._nztot()
+        if (X.numel() < ldx * (k - 1) + self.rows or Y.numel() < ldy * (k - 1) + self.cols or G_out.numel() < nztot
+                or not X.is_contiguous() or not Y.is_contiguous() or not G_out.is_contiguous()):
+            raise ValueError("X, Y or G too small / not contiguous for the stated leading dimensions")
+        st = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+        dt = C.c_float(0)
+        check(lib.sparta_vbs_sddmm(self.h, C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy, k,
+                                   C.cast(C.c_void_p(G_out.data_ptr()), _f32p), int(bool(accumulate)), _lib.PTR_DEVICE, C.c_void_p(st),
+                                   C.byref(dt) if timed else None))
+        return dt.value if timed else None
+
+    def sddmm_host(self, X, Y, k, G_out, accumulate=True):
+        """sddmm with host buffers (numpy, fp32; rounded on the device for 16-bit handles): X rows x k, Y cols x k, column-major;
+        G_out a contiguous float32 array of >= nztot elements, written in place.  Returns kernel ms."""
+        X = np.ascontiguousarray(X, np.float32).reshape(-1)
+        Y = np.ascontiguousarray(Y, np.float32).reshape(-1)
+        if not (isinstance(G_out, np.ndarray) and G_out.dtype == np.float32 and G_out.flags.c_contiguous):
+            raise ValueError("G must be a contiguous float32 numpy array (it is written in place)")
+        k = int(k)
+        if k <= 0:
+            raise ValueError("k must be > 0")
+        if X.size < self.rows * k or Y.size < self.cols * k or G_out.size < self._nztot():
+            raise ValueError("X, Y or G too small")
+        dt = C.c_float(0)
+        check(lib.sparta_vbs_sddmm(self.h, X.ctypes.data_as(C.c_void_p), self.rows, Y.ctypes.data_as(C.c_void_p), self.cols, k,
+                                   G_out.ctypes.data_as(_f32p), int(bool(accumulate)), _lib.PTR_HOST, None, C.byref(dt)))
+        return dt.value
+
     def spmm_gathered(self, B_gathered, shard_rows, C_out, n_cols, accumulate=False, algo=_lib.SPMM_MFMA,
                       c_layout=_lib.COL_MAJOR, shard_stride=None, timed=False, stream=None, shard_ld=None):
         """Multi-GPU entry: B_gathered is the all-gather result (n_shards column-major slabs of shard_rows x n_cols; shard_ld: elements between the columns of a

@@ -357,6 +357,17 @@ class VBR:
             self._dev = self.to_device(device)
         return self._dev.spmm_host(B, B_cols, C_out, accumulate=True, algo=algo)
 
+    def sddmm(self, X, Y, k, G_out=None, device=0):
+        """G += (X * Y^T) sampled on the stored blocks, in the layout of self.mab (the gradient of mab for C = A * B with X = dC, Y = B):
+        host buffers, column-major, X rows x k (ld = rows), Y cols x k (ld = cols); G_out None starts from zeros.  Executed on the GPU
+        with the cached device image multiply uses.  Returns G_out.  No reference counterpart."""
+        if G_out is None:
+            G_out = np.zeros(int(self.nztot), np.float32)
+        if self._dev is None or self._dev.device != device:
+            self._dev = self.to_device(device)
+        self._dev.sddmm_host(X, Y, k, G_out, accumulate=True)
+        return G_out
+
 
 def get_permutation(grouping):
     g = np.ascontiguousarray(grouping, np.int64)
