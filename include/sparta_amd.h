@@ -262,6 +262,18 @@ int sparta_vbs_create_range(sparta_vbs_t** out, int64_t rows, int64_t cols, int6
                             const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, const float* mab,
                             int64_t block_row_begin, int64_t block_row_end, int32_t dtype, int32_t device);
 
+/* sparta_vbs_create_range with creation flags.  flags = 0 is sparta_vbs_create_range exactly (that entry calls this one).
+ * SPARTA_CREATE_UPDATABLE: the handle can take new values for the same block pattern through sparta_vbs_set_values.  Such a handle keeps
+ * every block-row in its dense-block images (no block-row moves to the sparse-row kernels, whose image holds only what was non-zero at
+ * creation) and, for 16-bit handles, 32 bytes per 2-8 KB slice that say where in mab the slice came from.  Everything else -- plans,
+ * kernels, products -- is as for flags = 0.  Unknown bits: SPARTA_ERR_INVALID. */
+#define SPARTA_CREATE_UPDATABLE 1
+int sparta_vbs_create_range_ex(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t block_rows, int64_t block_col_size,
+                               const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, const float* mab,
+                               int64_t block_row_begin, int64_t block_row_end, int32_t dtype, int32_t device, int32_t flags);
+/* the flags a handle was created with (0 for sparta_vbs_create, _create_range, _create_from_csr, _create_transposed) */
+int sparta_vbs_flags(const sparta_vbs_t* A, int32_t* flags_out);
+
 /* Device handle straight from the CSR and a grouping, for matrices whose VBS image is mostly zeros (clustered power-law graphs:
  * 98 % of the stored area): does what sparta_vbs_build + sparta_vbs_create do, except that the block-rows the sparse-row
  * kernels will take anyway are never expanded into dense blocks -- neither on the host nor on the device.  Same product as a
@@ -359,6 +371,24 @@ int sparta_vbs_spmm_ba(sparta_vbs_t* At, const void* B, int64_t ldb, int32_t M, 
  * its stream is being captured returns SPARTA_ERR_UNSUPPORTED. */
 int sparta_vbs_sddmm(sparta_vbs_t* A, const void* X, int64_t ldx, const void* Y, int64_t ldy, int32_t k, float* G, int32_t accumulate,
                      int32_t ptr_space, void* stream, float* dt_ms);
+
+/* New values for the stored blocks of a handle made with SPARTA_CREATE_UPDATABLE, same block pattern: mab is nztot fp32 values laid out
+ * as sparta_vbs_host.mab (for a range handle the slice of its block-rows, from 0) -- the layout of G of sparta_vbs_sddmm, so that
+ * W -= lr * G on the caller's fp32 master copy followed by this call is one training step.  Every device image the handle holds is
+ * rewritten on the device (fp32: the reference-layout image and the fragment image with its per-step k-compaction redone; 16-bit: the
+ * slices of the stream plans and of the hub plan, rounded to nearest even exactly as creation rounds them); positions past `cols` in a
+ * ragged last block column are stored as given.  After the call, in stream order, every entry behaves as if the handle had been created
+ * from the new values; the plans and the autotune's choices stay as creation made them.
+ * SPARTA_PTR_DEVICE: stream-ordered on `stream`, kernel launches only (no allocation, no synchronisation): it can be captured into a
+ * hipGraph.  SPARTA_PTR_HOST: mab is a host array, staged through scratch the handle owns; the call returns when the copy is done.
+ * *dt_ms (may be NULL) covers the kernels only and synchronises (refused with SPARTA_ERR_UNSUPPORTED while the stream is being captured).
+ * SPARTA_ERR_UNSUPPORTED on a handle made without the flag (including sparta_vbs_create_from_csr and sparta_vbs_create_transposed);
+ * SPARTA_ERR_INVALID on a NULL handle, or a NULL mab with nztot > 0. */
+int sparta_vbs_set_values(sparta_vbs_t* A, const float* mab, int32_t ptr_space, void* stream, float* dt_ms);
+/* The k-compaction rule of the fp32 fragment image, for the CPU suite (no GPU): nonempty[k] != 0 says column k of a step's 32-deep slice
+ * has a non-zero; pos[k] is its fragment position (a permutation of 0..31, non-empty columns first: compact index c at (c >> 1) + 16 (c & 1)),
+ * *pairs the MFMA pairs the step issues.  The host packer and the update kernel both call the function behind this entry. */
+int sparta_frag_positions(const uint8_t* nonempty, uint8_t* pos, int32_t* pairs);
 
 /* A dense operand that does NOT change between products, prepared once.  The reference's drivers multiply the same B `-x` times
  * (test/cuda/cuda_multiply.cpp:250-269); the sparse-row kernels of a handle read B row-major, so a column-major (the reference's layout)

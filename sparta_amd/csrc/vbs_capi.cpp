@@ -10,7 +10,7 @@
 #include <memory>
 
 #include <cmath>
-#include "vbs_device.hpp"
+#include "vbs_kernel_common.hpp"
 
 using namespace sparta_dev;
 
@@ -118,6 +118,10 @@ void destroy_impl(sparta_vbs* v) {
     if (v->d_sd_items) (void)hipFree(v->d_sd_items);
     if (v->d_sd_ws) (void)hipFree(v->d_sd_ws);
     if (v->d_sd_h16) (void)hipFree(v->d_sd_h16);
+    for (int ty = 0; ty < 2; ty++)
+        if (v->d_upd_map[ty]) (void)hipFree(v->d_upd_map[ty]);
+    if (v->d_upd_hub) (void)hipFree(v->d_upd_hub);
+    if (v->d_upd_ws) (void)hipFree(v->d_upd_ws);
     if (v->ev0) (void)hipEventDestroy(v->ev0);
     if (v->ev1) (void)hipEventDestroy(v->ev1);
     for (int c = 0; c < 4; c++)
@@ -357,9 +361,11 @@ int sparta_device_count(void) {
 // add to C behind the tile launches (see the ordering note at the sparse-row launch in spmm_impl).
 static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t block_rows, int64_t w, const int64_t* row_part,
                        const int64_t* nzcount, const int64_t* jab, const float* mab, int64_t br0, int64_t br1, int32_t dtype,
-                       int32_t device, const sparta::HybridSparse* ext) {
+                       int32_t device, const sparta::HybridSparse* ext, int32_t flags = 0) {
     using sparta::fail;
     if (!out) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: out is NULL");
+    if (flags & ~SPARTA_CREATE_UPDATABLE) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create_range_ex: unknown bits in flags");
+    const bool updatable = (flags & SPARTA_CREATE_UPDATABLE) != 0;        // every block-row stays in the dense-block images; the slices' sources are kept
     *out = nullptr;
     sparta::BuildTrace trace("vbs_create");
     if (rows <= 0 || cols <= 0 || block_rows <= 0 || w <= 0 || !row_part || !nzcount)
@@ -454,6 +460,7 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
     } else {
         double K = 24.0;
         if (const char* e = std::getenv("SPARTA_SPARSE_K")) K = atof(e);
+        if (updatable) K = 0.0;          // (the sparse-row image holds only what was non-zero at creation: sparta_vbs_set_values could not fill it)
         if (K > 0.0) {
             sparse_flag.assign((size_t)(br1 - br0), 0);
             int64_t jo2 = 0, mo2 = 0, n_flagged = 0;
@@ -724,7 +731,7 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
     // ---- stream plans (persistent kernels): see build_stream_plans ----
     StreamPlanHost plan;
     {
-        StreamPlanIn pin{cols, w, br0, br1, jab_lo, mab_lo, row_part, nzcount, jab, mab, dtype, device, skip};
+        StreamPlanIn pin{cols, w, br0, br1, jab_lo, mab_lo, row_part, nzcount, jab, mab, dtype, device, skip, updatable && h16};
         trace.lap("tile lists");
         if (int rc = build_stream_plans(pin, plan)) return rc;
         trace.lap("stream plans");
@@ -752,7 +759,7 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
     if (plan_debug) return fail(SPARTA_ERR_NO_DEVICE, "sparta_vbs_create: no HIP device visible (this path has no CPU fallback)");
     sparta_vbs* v = hold.get();
     if (!v) return fail(SPARTA_ERR_ALLOC, "sparta_vbs_create: out of host memory");
-    v->device = device; v->dtype = dtype;
+    v->device = device; v->dtype = dtype; v->create_flags = flags;
     v->zero_ranges = plan.zero_ranges;
     v->rows = row_part[br1] - row_part[br0]; v->cols = cols; v->block_rows = br1 - br0; v->w = w;
     v->nblocks = nblocks; v->nztot = nztot; v->exec_area = exec_area;
@@ -783,6 +790,17 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
         if (!a0.empty()) CREATE_TRY(hipMemcpy(v->d_A, a0.data(), a0.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         if (!a1.empty()) CREATE_TRY(hipMemcpy((uint16_t*)v->d_A + a0.size(), a1.data(), a1.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         v->kp16 = (int)kp;
+        v->upd_base[1] = (int64_t)a0.size();
+        for (int ty = 0; ty < 2 && updatable; ty++) {
+            if (plan.upd_map[ty].empty()) continue;
+            CREATE_TRY(hipMalloc((void**)&v->d_upd_map[ty], plan.upd_map[ty].size() * sizeof(UpdSlice)));
+            CREATE_TRY(hipMemcpy(v->d_upd_map[ty], plan.upd_map[ty].data(), plan.upd_map[ty].size() * sizeof(UpdSlice), hipMemcpyHostToDevice));
+        }
+        if (updatable && !plan.upd_hub.empty()) {
+            v->n_upd_hub = (int64_t)plan.upd_hub.size();
+            CREATE_TRY(hipMalloc((void**)&v->d_upd_hub, plan.upd_hub.size() * sizeof(UpdSlice)));
+            CREATE_TRY(hipMemcpy(v->d_upd_hub, plan.upd_hub.data(), plan.upd_hub.size() * sizeof(UpdSlice), hipMemcpyHostToDevice));
+        }
     }
     CREATE_TRY(hipMalloc((void**)&v->d_jab, jab32.size() * sizeof(int32_t)));
     CREATE_TRY(hipMemcpy(v->d_jab, jab32.data(), jab32.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -980,12 +998,18 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
     return SPARTA_OK;
 }
 
+int sparta_vbs_create_range_ex(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t block_rows, int64_t w, const int64_t* row_part,
+                               const int64_t* nzcount, const int64_t* jab, const float* mab, int64_t br0, int64_t br1, int32_t dtype,
+                               int32_t device, int32_t flags) {
+    SPARTA_GUARD_BEGIN
+    return create_core(out, rows, cols, block_rows, w, row_part, nzcount, jab, mab, br0, br1, dtype, device, nullptr, flags);
+    SPARTA_GUARD_END("sparta_vbs_create")
+}
+
 int sparta_vbs_create_range(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t block_rows, int64_t w, const int64_t* row_part,
                             const int64_t* nzcount, const int64_t* jab, const float* mab, int64_t br0, int64_t br1, int32_t dtype,
                             int32_t device) {
-    SPARTA_GUARD_BEGIN
-    return create_core(out, rows, cols, block_rows, w, row_part, nzcount, jab, mab, br0, br1, dtype, device, nullptr);
-    SPARTA_GUARD_END("sparta_vbs_create")
+    return sparta_vbs_create_range_ex(out, rows, cols, block_rows, w, row_part, nzcount, jab, mab, br0, br1, dtype, device, 0);
 }
 
 static int create_from_csr_impl(sparta_vbs_t** out, int64_t rows, int64_t cols, const int64_t* rowptr, const int32_t* colidx, const float* vals,
@@ -1138,6 +1162,22 @@ int sparta_vbs_info(const sparta_vbs_t* A, int64_t* info) {
     info[9] = A->n_sp_rows;                // rows handled by the sparse-row path
     info[10] = A->a_bytes; info[11] = A->exec_area;
     info[12] = A->n_steps[0] + A->n_steps[1]; info[13] = A->n_workers; info[14] = A->n_split; info[15] = A->last_path;
+    return SPARTA_OK;
+}
+
+int sparta_vbs_flags(const sparta_vbs_t* A, int32_t* flags_out) {
+    if (!A || !flags_out) return sparta::fail(SPARTA_ERR_INVALID, "sparta_vbs_flags: NULL argument");
+    *flags_out = A->create_flags;
+    return SPARTA_OK;
+}
+
+// the k-compaction rule of the fp32 fragment image (frag_position / frag_pairs, vbs_kernel_common.hpp) for the CPU suite: no GPU involved
+int sparta_frag_positions(const uint8_t* nonempty, uint8_t* pos, int32_t* pairs) {
+    if (!nonempty || !pos || !pairs) return sparta::fail(SPARTA_ERR_INVALID, "sparta_frag_positions: NULL argument");
+    uint32_t mask = 0;
+    for (int k = 0; k < 32; k++) mask |= (uint32_t)(nonempty[k] != 0) << k;
+    for (int k = 0; k < 32; k++) pos[k] = (uint8_t)frag_position(mask, k);
+    *pairs = frag_pairs(mask);
     return SPARTA_OK;
 }
 
@@ -2248,4 +2288,61 @@ extern "C" int sparta_vbs_sddmm(sparta_vbs_t* A, const void* X, int64_t ldx, con
     SPARTA_GUARD_BEGIN
     return sddmm_impl(A, X, ldx, Y, ldy, k, G, accumulate, ptr_space, stream, dt_ms);
     SPARTA_GUARD_END("sparta_vbs_sddmm")
+}
+
+// ---- sparta_vbs_set_values (k_update.hip) -----------------------------------------------------------------------------------------------
+namespace {
+
+int set_values_impl(sparta_vbs_t* A, const float* mab, int32_t ptr_space, void* stream, float* dt_ms) {
+    using sparta::fail;
+    if (!A) return fail(SPARTA_ERR_INVALID, "sparta_vbs_set_values: NULL handle");
+    if (!mab && A->nztot > 0) return fail(SPARTA_ERR_INVALID, "sparta_vbs_set_values: mab is NULL");
+    if (ptr_space != SPARTA_PTR_HOST && ptr_space != SPARTA_PTR_DEVICE) return fail(SPARTA_ERR_INVALID, "sparta_vbs_set_values: bad ptr_space");
+    if (!(A->create_flags & SPARTA_CREATE_UPDATABLE))
+        return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_set_values: the handle was not made with SPARTA_CREATE_UPDATABLE (sparta_vbs_create_range_ex; handles of "
+                                            "sparta_vbs_create_from_csr and sparta_vbs_create_transposed cannot take new values)");
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, "sparta_vbs_set_values: hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, ptr_space == SPARTA_PTR_DEVICE);
+    if (g_capturing && dt_ms) return capture_refusal("time the update (dt_ms != NULL synchronises)", "sparta_vbs_set_values");
+    const float* src = mab;
+    if (ptr_space == SPARTA_PTR_HOST && A->nztot > 0) {
+        if (int rc = ensure_scratch(&A->d_upd_ws, &A->d_upd_ws_bytes, (size_t)A->nztot * sizeof(float))) return rc;
+        HIP_TRY(hipMemcpyAsync(A->d_upd_ws, mab, (size_t)A->nztot * sizeof(float), hipMemcpyHostToDevice, st));
+        src = (const float*)A->d_upd_ws;
+    }
+    if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
+    if (A->nztot > 0) {
+        if (A->dtype == SPARTA_F32) {
+            // the fragment image holds every stored element when the handle has no 33..64-row tiles: its kernel then writes the reference-layout image (if the
+            // handle still holds it: a dropped one is rebuilt from the fragment image when a call asks for it) from the same read of mab
+            const bool frag = A->d_a_frag != nullptr && A->n_steps[0] > 0;
+            const bool frag_covers = frag && A->n_steps[1] == 0;
+            if (A->d_A && !frag_covers) launch_update_copy(st, src, A->nztot, A->d_A);
+            if (frag) launch_update_f32_frag(st, A->d_steps[0], A->n_steps[0], src, A->d_a_frag, frag_covers ? A->d_A : nullptr);
+        } else {
+            const bool bf16 = A->dtype == SPARTA_BF16;
+            for (int ty = 0; ty < 2; ty++)
+                if (A->n_steps[ty] > 0)
+                    launch_update_h16(bf16, false, ty ? 64 : 32, A->kp16, st, A->d_upd_map[ty], A->n_steps[ty], src, (uint16_t*)A->d_A + A->upd_base[ty]);
+            if (A->n_upd_hub > 0) launch_update_h16(bf16, true, 64, 64, st, A->d_upd_hub, A->n_upd_hub, src, A->d_hub_A);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    if (dt_ms) {
+        HIP_TRY(hipEventRecord(A->ev1, st));
+        HIP_TRY(hipEventSynchronize(A->ev1));
+        HIP_TRY(hipEventElapsedTime(dt_ms, A->ev0, A->ev1));
+    }
+    if (ptr_space == SPARTA_PTR_HOST) HIP_TRY(hipStreamSynchronize(st));          // (the caller's array is free again when the call returns)
+    return SPARTA_OK;
+}
+
+}  // namespace
+
+extern "C" int sparta_vbs_set_values(sparta_vbs_t* A, const float* mab, int32_t ptr_space, void* stream, float* dt_ms) {
+    SPARTA_GUARD_BEGIN
+    return set_values_impl(A, mab, ptr_space, stream, dt_ms);
+    SPARTA_GUARD_END("sparta_vbs_set_values")
 }

@@ -3,6 +3,7 @@
 //   k_f32_stream.hip  persistent fp32 stream kernels, fix-up, B-tail copy, zero fill
 //   k_h16.hip         fp16 / bf16 storage: LDS-staged and direct stream kernels, conversions
 //   k_sparse.hip      sparse-row kernels, layout transposes, row-block pack
+//   k_update.hip      new values for the images of an updatable handle (sparta_vbs_set_values)
 //   vbs_plan.cpp      host: stream plans (step lists, worker ranges, split tiles)
 //   vbs_capi.cpp      host: device image (sparta_vbs), sparta_vbs_create* / sparta_vbs_spmm* (include/sparta_amd.h)
 // Every kernel TU exports plain launch functions (namespace sparta_dev); the host TUs never see a __global__ symbol.
@@ -253,6 +254,17 @@ struct SddmmParams {
     int32_t k, w, accumulate, pad;
 };
 
+// sparta_vbs_set_values (k_update.hip): where one 16-bit slice of an updatable handle comes from.  Row rr of the slice, column kk of its k range, is
+// mab[off_lo + kk * h_lo + rr] for rr < rows_lo, else mab[off_hi + kk * h_hi + (rr - 32)] for 32 <= rr < 32 + rows_hi, else zero.  An ordinary tile has
+// rows_lo = its rows (<= 64) and rows_hi = 0; a pair tile has rows_lo = 32 or 0 (upper block-row present or not) and rows_hi = the lower block-row's
+// rows or 0; a hub slice has rows_lo = the sub-tile's height.  Offsets are relative to the handle's first stored element.
+struct UpdSlice {
+    int64_t off_lo, off_hi;
+    int32_t h_lo, h_hi;
+    int32_t rows_lo, rows_hi;
+};
+static_assert(sizeof(UpdSlice) == 32, "UpdSlice must stay 32 bytes");
+
 #define HIP_TRY(expr)                                                                                   \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \
@@ -403,6 +415,14 @@ struct sparta_vbs {
     size_t d_sd_ws_bytes = 0;
     void* d_sd_h16 = nullptr;
     size_t d_sd_h16_bytes = 0;
+    // sparta_vbs_set_values (SPARTA_CREATE_UPDATABLE handles only): the source of every 16-bit slice, in image order; host-pointer calls stage mab in scratch
+    int32_t create_flags = 0;
+    sparta_dev::UpdSlice* d_upd_map[2] = {nullptr, nullptr};   // per tile type: one record per step (= slice) of d_A
+    int64_t upd_base[2] = {0, 0};                              // element offset of the type's first slice in d_A
+    sparta_dev::UpdSlice* d_upd_hub = nullptr;                 // one record per 64 x 64 slice of d_hub_A
+    int64_t n_upd_hub = 0;
+    void* d_upd_ws = nullptr;
+    size_t d_upd_ws_bytes = 0;
 };
 
 namespace sparta_dev {
@@ -445,6 +465,13 @@ void launch_union_f32(unsigned n_slabs, hipStream_t st, const UnionParams& p);
 void launch_union_h16(bool bf16, unsigned n_slabs, hipStream_t st, const UnionParams& p);   // 16-bit handles: p.B = the row-major 16-bit B, side.A = 16-bit slices
 // k_sddmm.hip: one workgroup per work item (n_items <= 2^31 - 1); dtype = SPARTA_F32 / F16 / BF16
 void launch_sddmm(int dtype, unsigned n_items, hipStream_t st, const SddmmParams& p);
+// k_update.hip (sparta_vbs_set_values): new values, nztot floats in the mab layout, into the images of an updatable handle
+void launch_update_copy(hipStream_t st, const float* mab, int64_t n, float* A);        // the reference-layout image (fp32 handles)
+// the fragment image of the fp32 one-tile plan, k-compaction redone per step (position table, fragments, STEP_KPAIRS of steps[q].mt_flags);
+// A_out != nullptr: the steps cover every stored element, the reference-layout image is written from the same read
+void launch_update_f32_frag(hipStream_t st, StepRec* steps, int64_t n_steps, const float* mab, float* a_frag, float* A_out);
+// 16-bit slices of tms rows x kp columns ([k / 8][row][8]; hub: the swizzled 64 x 64 image of k_hub16.hip), rounded as to_h16 rounds
+void launch_update_h16(bool bf16, bool hub, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, const float* mab, uint16_t* dst);
 // k_colres.hip
 int launch_colres(int nc, const ColresParams& p, size_t lds_bytes, hipStream_t st);     // nc = 1..4 columns per workgroup; 0 or a hipError_t
 int colres_max_slices(int nc);                                                          // slices the nc-column kernel holds sums for
@@ -456,6 +483,7 @@ struct StreamPlanIn {
     const int64_t* row_part; const int64_t* nzcount; const int64_t* jab; const float* mab;
     int32_t dtype, device;
     const uint8_t* skip;                      // [br1 - br0] block-rows handled by the sparse-row path (no tiles), or nullptr
+    bool updatable = false;                   // SPARTA_CREATE_UPDATABLE: record the source of every 16-bit slice (StreamPlanHost::upd_map / upd_hub)
 };
 struct StreamPlanHost {
     std::vector<StepRec> steps[2];            // per tile type: [0] <= 32 rows, [1] 33..64 rows
@@ -483,6 +511,9 @@ struct StreamPlanHost {
     int hub_workers = 0;
     int64_t n_hub_steps = 0, hub_area = 0, hub_union_area = 0;    // steps; stored elements of the hub tiles; elements the kernel multiplies (absent sub-tiles included)
     int64_t n_hub_tiles = 0, n_hub_groups = 0, hub_chunks = 0, hub_segments = 0;    // K chunks of the step order; segments (runs of one group on one worker)
+    // updatable 16-bit handles: where every slice of a16_steps[ty] / hub_a16 comes from, in image order (sparta_vbs_set_values)
+    std::vector<UpdSlice> upd_map[2];
+    std::vector<UpdSlice> upd_hub;
 };
 // vbs_union.cpp: the device form of the column-compacted tiles -- tiles dealt to workers longest first, a worker's steps back to back
 struct UnionDevPlan {

@@ -5,6 +5,35 @@
 
 namespace sparta_dev {
 
+// ---- k-compaction of the fp32 fragment image: ONE rule for the host packer (vbs_plan.cpp) and the update kernel (k_update.hip) --------------
+// `nonempty` bit k: column k of the step's 32-deep slice of A has a non-zero in the tile's rows.  The columns are handed out class by class
+// (sequence index s = 4 m + e names column k = 4 m + ((e + m) & 3), so that a class k mod 4 spreads over the four residues of pos mod 4),
+// the non-empty ones first; compact index c sits at fragment position (c >> 1) + 16 (c & 1).  The positions are a permutation of 0..31.
+__host__ __device__ inline uint32_t frag_seq_mask(uint32_t nonempty) {        // bit s = the sequence's s-th column is non-empty
+    uint32_t seq = 0;
+    for (int m = 0; m < 8; m++) {
+        const uint32_t nib = (nonempty >> (4 * m)) & 15u, r = (uint32_t)(m & 3);
+        seq |= (((nib >> r) | (nib << (4 - r))) & 15u) << (4 * m);            // bit e of the group = column bit (e + m) & 3
+    }
+    return seq;
+}
+__host__ __device__ inline int frag_position(uint32_t nonempty, int k) {     // fragment position of column k of the slice
+    const uint32_t seq = frag_seq_mask(nonempty);
+    const int m = k >> 2, s = 4 * m + (((k & 3) - m) & 3);
+    const uint32_t before = (1u << s) - 1u;
+    const int c = ((nonempty >> k) & 1u) ? __builtin_popcount(seq & before) : __builtin_popcount(seq) + __builtin_popcount(~seq & before);
+    return (c >> 1) + 16 * (c & 1);
+}
+__host__ __device__ inline int frag_pairs(uint32_t nonempty) {               // MFMA pairs the step issues (STEP_KPAIRS holds this - 1)
+    const int nk = __builtin_popcount(nonempty), n_mfma = nk + 1 >= 2 ? (nk + 1) / 2 : 1;
+    return (n_mfma + 1) / 2;
+}
+
+}  // namespace sparta_dev
+
+#ifdef __HIP__            // what follows is device code: the host translation units stop here
+namespace sparta_dev {
+
 // Clock probe: s_memtime counts shader-clock cycles, s_memrealtime a constant 100 MHz; the ratio over a kernel's lifetime is
 // the clock the MFMA pipes actually ran at (the board drops it under a dense fp32 MFMA load: DESIGN.md, "clock").
 // Developer instrumentation (make TIMELINE=1 -> libsparta_amd_tl.so; never in the product build): s_memtime stamps inside the steps
@@ -129,3 +158,4 @@ struct CRing {
 };
 
 }  // namespace sparta_dev
+#endif  // __HIP__

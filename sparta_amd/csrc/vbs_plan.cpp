@@ -4,7 +4,7 @@
 #include <cstdio>
 #include <queue>
 
-#include "vbs_device.hpp"
+#include "vbs_kernel_common.hpp"
 
 namespace sparta_dev {
 
@@ -540,6 +540,7 @@ int build_stream_plans(const StreamPlanIn& in, StreamPlanHost& P) {
                 a16_steps[ty].assign((size_t)S * slice, 0);
                 const bool bf = dtype == SPARTA_BF16;
                 uint16_t* all = a16_steps[ty].data();
+                if (in.updatable) P.upd_map[ty].assign((size_t)S, UpdSlice{0, 0, 0, 0, 0, 0});      // (r.a_off is overwritten below: the map keeps where a slice came from)
                 sparta::parallel_for_dynamic(S, 256, [&](int64_t lo, int64_t hi, int) {
                     for (int64_t q = lo; q < hi; q++) {
                         StepRec& r = st[(size_t)q];
@@ -557,6 +558,8 @@ int build_stream_plans(const StreamPlanIn& in, StreamPlanHost& P) {
                                     for (int64_t rr = 0; rr < ps.rows_hi; rr++) d2[(32 + rr) * 8] = to_h16(colp[rr], bf);
                                 }
                             }
+                            if (in.updatable)
+                                P.upd_map[ty][(size_t)q] = UpdSlice{ps.lo_present ? r.a_off : 0, ps.hi_present ? ps.a_off_hi : 0, r.h, ps.h_hi, ps.lo_present ? 32 : 0, ps.hi_present ? ps.rows_hi : 0};
                             r.pad = 0;
                             r.a_off = (int64_t)(base + (size_t)q * slice);
                             continue;
@@ -568,6 +571,7 @@ int build_stream_plans(const StreamPlanIn& in, StreamPlanHost& P) {
                             uint16_t* d2 = dst + (kk >> 3) * tms * 8 + (kk & 7);
                             for (int64_t rr = 0; rr < mt; rr++) d2[rr * 8] = to_h16(colp[rr], bf);
                         }
+                        if (in.updatable) P.upd_map[ty][(size_t)q] = UpdSlice{r.a_off, 0, r.h, 0, (int32_t)mt, 0};
                         r.a_off = (int64_t)(base + (size_t)q * slice);
                     }
                 });
@@ -596,30 +600,26 @@ int build_stream_plans(const StreamPlanIn& in, StreamPlanHost& P) {
                             StepRec& r = st[(size_t)q];
                             const float* blk = mab + mab_lo + r.a_off;              // element (row, k) of the slice at blk[k * h + row]
                             const int64_t hh = r.h, mt = r.mt_flags & 0xffff;
-                            bool nonempty[32];
-                            int nk = 0;
+                            uint32_t nonempty = 0;
                             for (int k = 0; k < 32; k++) {
                                 bool any = false;
                                 for (int64_t m = 0; m < mt && !any; m++) any = blk[(int64_t)k * hh + m] != 0.0f;
-                                nonempty[k] = any; nk += any;
+                                nonempty |= (uint32_t)any << k;
                             }
                             // positions: the first nk compact indices for the non-empty columns, the rest for the empty ones; inside each group the
                             // columns are handed out class by class (k mod 4 = e) so that a class spreads over the four residues of pos mod 4
+                            // (frag_position, vbs_kernel_common.hpp: the rule the update kernel of sparta_vbs_set_values applies too)
                             uint8_t pos[32];
-                            int order[32], no = 0;
-                            for (int pass = 0; pass < 2; pass++)
-                                for (int m = 0; m < 8; m++)
-                                    for (int e = 0; e < 4; e++) { const int k = 4 * m + ((e + m) & 3); if (nonempty[k] == (pass == 0)) order[no++] = k; }
-                            for (int c = 0; c < 32; c++) pos[order[c]] = (uint8_t)((c >> 1) + 16 * (c & 1));
+                            for (int k = 0; k < 32; k++) pos[k] = (uint8_t)frag_position(nonempty, k);
                             float* dst = af.data() + (size_t)q * (size_t)kAFragSlice;
                             std::memcpy(dst, pos, 32);
                             float* frag = dst + 16;
                             for (int k = 0; k < 32; k++) {
-                                if (!nonempty[k]) continue;
+                                if (!((nonempty >> k) & 1u)) continue;
                                 const int kp = pos[k], g = kp >> 4, j = (kp & 15) >> 2, e = kp & 3;     // k' = 16 g + 4 j + e
                                 for (int64_t m = 0; m < mt; m++) frag[((j * 2 + g) * 32 + m) * 4 + e] = blk[(int64_t)k * hh + m];
                             }
-                            const int n_mfma = std::max(1, (nk + 1) / 2), pairs = (n_mfma + 1) / 2;
+                            const int pairs = frag_pairs(nonempty);
                             r.mt_flags = (r.mt_flags & ~(7 << STEP_KPAIRS_SHIFT)) | ((pairs - 1) << STEP_KPAIRS_SHIFT);
                         }
                     });
@@ -868,6 +868,7 @@ int build_stream_plans(const StreamPlanIn& in, StreamPlanHost& P) {
             if (!P.hub_a16) return fail(SPARTA_ERR_ALLOC, "sparta_vbs_create: out of host memory for the hub slices");
             const bool bf = dtype == SPARTA_BF16;
             uint16_t* all = P.hub_a16.get();
+            if (in.updatable) P.upd_hub.assign(P.hub_a16_elems / (64 * 64), UpdSlice{0, 0, 0, 0, 0, 0});
             sparta::parallel_for_dynamic(S, 64, [&](int64_t lo, int64_t hi, int) {
                 for (int64_t q = lo; q < hi; q++) {
                     const ORef& o = order[(size_t)q];
@@ -877,6 +878,7 @@ int build_stream_plans(const StreamPlanIn& in, StreamPlanHost& P) {
                         if (!((x.mask >> k) & 1)) continue;
                         const int64_t ib = hub_groups[(size_t)o.g].ib[k], hh = row_part[ib + 1] - row_part[ib];
                         const float* blk = mab + mab_lo + mo_of[(size_t)(ib - br0)] + ((int64_t)x.bidx[k] * w + o.ks) * hh;     // column-major hh x w block, k slice o.ks
+                        if (in.updatable) P.upd_hub[(size_t)((dst - all) / (64 * 64))] = UpdSlice{blk - (mab + mab_lo), 0, (int32_t)hh, 0, (int32_t)hh, 0};
                         if (hh < 64) std::memset(dst + hh * 64, 0, (size_t)(64 - hh) * 64 * sizeof(uint16_t));              // rows past the sub-tile's height
                         for (int64_t kk = 0; kk < 64; kk++) {
                             const float* colp = blk + kk * hh;

@@ -16,7 +16,9 @@ def device_count():
 class DeviceVBS:
     """Opaque device image of a VBS matrix + its tile plan (sparta_vbs_t)."""
 
-    def __init__(self, vbmat, device=0, dtype=_lib.F32, block_row_range=None):
+    def __init__(self, vbmat, device=0, dtype=_lib.F32, block_row_range=None, updatable=False):
+        """updatable=True (SPARTA_CREATE_UPDATABLE): the handle takes new values for the same block pattern through set_values; it keeps every
+        block-row on the dense-block kernels (none moves to the sparse-row kernels)."""
         self.device = int(device)
         self.dtype = dtype
         self.h = C.c_void_p(None)
@@ -27,9 +29,10 @@ class DeviceVBS:
         jab = np.ascontiguousarray(vbmat.jab, np.int64)
         mab = np.ascontiguousarray(vbmat.mab, np.float32)
         b0, b1 = (0, vbmat.block_rows) if block_row_range is None else block_row_range
-        check(lib.sparta_vbs_create_range(C.byref(self.h), vbmat.rows, vbmat.cols, vbmat.block_rows, vbmat.block_col_size,
-                                          rp.ctypes.data_as(_i64p), nz.ctypes.data_as(_i64p), jab.ctypes.data_as(_i64p),
-                                          mab.ctypes.data_as(_f32p), int(b0), int(b1), int(dtype), self.device))
+        check(lib.sparta_vbs_create_range_ex(C.byref(self.h), vbmat.rows, vbmat.cols, vbmat.block_rows, vbmat.block_col_size,
+                                             rp.ctypes.data_as(_i64p), nz.ctypes.data_as(_i64p), jab.ctypes.data_as(_i64p),
+                                             mab.ctypes.data_as(_f32p), int(b0), int(b1), int(dtype), self.device,
+                                             _lib.CREATE_UPDATABLE if updatable else 0))
         info = self.info()
         self.rows, self.cols = info["rows"], info["cols"]
 
@@ -216,6 +219,37 @@ class DeviceVBS:
                                    C.cast(C.c_void_p(G_out.data_ptr()), _f32p), int(bool(accumulate)), _lib.PTR_DEVICE, C.c_void_p(st),
                                    C.byref(dt) if timed else None))
         return dt.value if timed else None
+
+    @property
+    def updatable(self):
+        """was the handle created with updatable=True (sparta_vbs_flags)?"""
+        f = C.c_int32(0)
+        check(lib.sparta_vbs_flags(self.h, C.byref(f)))
+        return bool(f.value & _lib.CREATE_UPDATABLE)
+
+    def set_values(self, mab, timed=False, stream=None):
+        """sparta_vbs_set_values, device tensor: new values for the stored blocks (same pattern), a contiguous float32 tensor of nztot elements
+        on this device in the layout of VBR.mab (= G of sddmm; for a range handle the slice of its block-rows).  Stream-ordered on torch's current
+        stream; every later product behaves as if the handle had been created from these values.  Needs updatable=True.  Returns kernel ms if timed."""
+        import torch
+        if not (mab.is_cuda and mab.dtype == torch.float32 and mab.device.index == self.device and mab.is_contiguous()):
+            raise ValueError("mab must be a contiguous float32 tensor on device %d" % self.device)
+        if mab.numel() != self._nztot():
+            raise ValueError("mab must hold nztot = %d elements" % self._nztot())
+        st = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+        dt = C.c_float(0)
+        check(lib.sparta_vbs_set_values(self.h, C.cast(C.c_void_p(mab.data_ptr()), _f32p), _lib.PTR_DEVICE, C.c_void_p(st),
+                                        C.byref(dt) if timed else None))
+        return dt.value if timed else None
+
+    def set_values_host(self, mab):
+        """set_values with a host array (numpy, fp32, nztot elements), staged through scratch of the handle.  Returns kernel ms."""
+        mab = np.ascontiguousarray(mab, np.float32).reshape(-1)
+        if mab.size != self._nztot():
+            raise ValueError("mab must hold nztot = %d elements" % self._nztot())
+        dt = C.c_float(0)
+        check(lib.sparta_vbs_set_values(self.h, mab.ctypes.data_as(_f32p), _lib.PTR_HOST, None, C.byref(dt)))
+        return dt.value
 
     def sddmm_host(self, X, Y, k, G_out, accumulate=True):
         """sddmm with host buffers (numpy, fp32; rounded on the device for 16-bit handles): X rows x k, Y cols x k, column-major;

@@ -337,9 +337,26 @@ class VBR:
         finally:
             lib.sparta_vbs_host_free(C.byref(h))
 
-    def to_device(self, device=0, dtype=_lib.F32, block_row_range=None):
+    def to_device(self, device=0, dtype=_lib.F32, block_row_range=None, updatable=False):
         from .device import DeviceVBS
-        return DeviceVBS(self, device=device, dtype=dtype, block_row_range=block_row_range)
+        return DeviceVBS(self, device=device, dtype=dtype, block_row_range=block_row_range, updatable=updatable)
+
+    def set_values(self, mab):
+        """New values for the stored blocks, same pattern: replaces self.mab (nztot float32 values in its layout).  A cached device image of A that
+        is updatable (self._dev = self.to_device(updatable=True)) takes the values in place (sparta_vbs_set_values); any other cached image
+        describes the old values and is dropped, so that the next multiply re-creates it."""
+        mab = np.ascontiguousarray(mab, np.float32).reshape(-1)
+        if mab.size != int(self.nztot):
+            raise ValueError("mab must hold nztot = %d elements" % int(self.nztot))
+        self.mab = mab.copy()
+        dev = self._dev if self._dev is not None and self._dev.updatable else None
+        if dev is not None:
+            self._dev = None                               # (kept out of _drop_device_images' reach)
+        self._drop_device_images()
+        if dev is not None:
+            dev.set_values_host(self.mab)
+            self._dev = dev
+        return self
 
     def multiply_BA(self, B, B_rows, C_out, device=0):
         """C += B * A (dense x VBS), host buffers, column-major: B is B_rows x rows, C is B_rows x cols.  The reference's
