@@ -266,8 +266,15 @@ int sparta_vbs_create_range(sparta_vbs_t** out, int64_t rows, int64_t cols, int6
  * SPARTA_CREATE_UPDATABLE: the handle can take new values for the same block pattern through sparta_vbs_set_values.  Such a handle keeps
  * every block-row in its dense-block images (no block-row moves to the sparse-row kernels, whose image holds only what was non-zero at
  * creation) and, for 16-bit handles, 32 bytes per 2-8 KB slice that say where in mab the slice came from.  Everything else -- plans,
- * kernels, products -- is as for flags = 0.  Unknown bits: SPARTA_ERR_INVALID. */
+ * kernels, products -- is as for flags = 0.  Unknown bits (flags & ~3): SPARTA_ERR_INVALID.
+ * SPARTA_CREATE_TRANSPOSE: the handle also takes sparta_vbs_spmm_t (Ct = A^T * X on its own stored blocks).  It holds a block-column index
+ * (16 bytes per block + 16 per block column and 32-column panel) and an image that product can read: an fp32 handle KEEPS its
+ * reference-layout image (plain handles shed that second fp32 image after the first product; on the benchmark's headline handle this
+ * costs about 90 MB), a 16-bit handle gets a second 16-bit image of about nztot * 2 bytes (counted in info[10]).  The forward product --
+ * plans, kernels, which block-rows go to the sparse-row kernels -- is that of a handle without the bit.  Combines with
+ * SPARTA_CREATE_UPDATABLE: sparta_vbs_set_values then rewrites what the transposed product reads, too. */
 #define SPARTA_CREATE_UPDATABLE 1
+#define SPARTA_CREATE_TRANSPOSE 2
 int sparta_vbs_create_range_ex(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t block_rows, int64_t block_col_size,
                                const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, const float* mab,
                                int64_t block_row_begin, int64_t block_row_end, int32_t dtype, int32_t device, int32_t flags);
@@ -385,6 +392,30 @@ int sparta_vbs_sddmm(sparta_vbs_t* A, const void* X, int64_t ldx, const void* Y,
  * SPARTA_ERR_UNSUPPORTED on a handle made without the flag (including sparta_vbs_create_from_csr and sparta_vbs_create_transposed);
  * SPARTA_ERR_INVALID on a NULL handle, or a NULL mab with nztot > 0. */
 int sparta_vbs_set_values(sparta_vbs_t* A, const float* mab, int32_t ptr_space, void* stream, float* dt_ms);
+
+/* Ct (+)= A^T * X on the stored blocks of A: the gradient of the dense operand of C = A * B (X = dC, Ct = dB), on the handle itself, so that
+ * it follows sparta_vbs_set_values in stream order.  Only handles made with SPARTA_CREATE_TRANSPOSE take the call; every other handle
+ * (flags without the bit, sparta_vbs_create, _create_range, _create_from_csr, _create_transposed): SPARTA_ERR_UNSUPPORTED.
+ * X : rows x n_cols, column-major, ldx >= rows -- the layout of C of sparta_vbs_spmm (rows in the VBS's reordered order; a range handle:
+ *     its own rows, local numbering; a force_fixed_size padding row is a row like any other).
+ * Ct: cols x n_cols, column-major, ldo >= cols -- the layout of B of sparta_vbs_spmm; always fp32.
+ * fp32 handles: fp32 X.  16-bit handles: X in the handle's type with even ldx (SPARTA_PTR_DEVICE) or fp32 rounded on the device
+ * (SPARTA_PTR_HOST); products of the 16-bit values, fp32 accumulation.
+ * accumulate = 0 writes every one of the cols x n_cols elements (zeros for columns of A that no stored block covers), 1 adds.  Nothing is
+ * written at or beyond row `cols` of a column of Ct: the positions of a ragged last block column that lie past `cols` take no part.
+ * Any n_cols >= 1.  Offsets are 64-bit; ldx * n_cols and ldo * n_cols must stay below 2^61 (else SPARTA_ERR_UNSUPPORTED).
+ * Deterministic: every element of Ct is summed by one wave in one fixed order (no atomics).  ptr_space / stream / dt_ms as for
+ * sparta_vbs_sddmm.  The block-column index and the image are built at creation: a device-pointer call is kernel launches only and can
+ * be captured into a hipGraph; SPARTA_PTR_HOST calls stage X and Ct in scratch the handle owns. */
+int sparta_vbs_spmm_t(sparta_vbs_t* A, const void* X, int64_t ldx, int32_t n_cols, float* Ct, int64_t ldo, int32_t accumulate,
+                      int32_t ptr_space, void* stream, float* dt_ms);
+/* The block-column index of sparta_vbs_spmm_t for the CPU suite (no GPU; not a product path): builds the index create builds for the
+ * block-rows [block_row_begin, block_row_end) and walks it for one vector: y[cols] = A^T x (x: the range's rows, local numbering).
+ * info_out[8] = {block columns with at least one block, work items, longest list of blocks of one item, segments of split columns (0:
+ * a block column is never split between workgroups), 0, 0, 0, 0}. */
+int sparta_spmm_t_host_check(int64_t rows, int64_t cols, int64_t block_rows, int64_t block_col_size, const int64_t* row_part,
+                             const int64_t* nzcount, const int64_t* jab, const float* mab, int64_t block_row_begin, int64_t block_row_end,
+                             const float* x, double* y, int64_t* info_out);
 /* The k-compaction rule of the fp32 fragment image, for the CPU suite (no GPU): nonempty[k] != 0 says column k of a step's 32-deep slice
  * has a non-zero; pos[k] is its fragment position (a permutation of 0..31, non-empty columns first: compact index c at (c >> 1) + 16 (c & 1)),
  * *pairs the MFMA pairs the step issues.  The host packer and the update kernel both call the function behind this entry. */

@@ -24,6 +24,7 @@ COL_MAJOR, ROW_MAJOR = 0, 1
 PTR_HOST, PTR_DEVICE = 0, 1
 SPMM_MFMA, SPMM_EXACT = 0, 1
 CREATE_UPDATABLE = 1
+CREATE_TRANSPOSE = 2
 FMT_EL, FMT_MTX = 0, 1
 IO_COMPAT, IO_STRICT = 0, 1
 
@@ -41,6 +42,7 @@ SYMBOLS = [
     "sparta_vbs_prepare_b", "sparta_vbs_spmm_prepared", "sparta_b_destroy",
     "sparta_vbs_sddmm",
     "sparta_vbs_create_range_ex", "sparta_vbs_set_values", "sparta_vbs_flags", "sparta_frag_positions",
+    "sparta_vbs_spmm_t", "sparta_spmm_t_host_check",
 ]
 
 
@@ -121,6 +123,8 @@ def _load():
                                              C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]
     L.sparta_vbs_set_values.argtypes = [vp, f32p, C.c_int32, vp, f32p]
     L.sparta_vbs_flags.argtypes = [vp, i32p]
+    L.sparta_vbs_spmm_t.argtypes = [vp, vp, C.c_int64, C.c_int32, f32p, C.c_int64, C.c_int32, C.c_int32, vp, f32p]
+    L.sparta_spmm_t_host_check.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, i64p, i64p, i64p, f32p, C.c_int64, C.c_int64, f32p, C.POINTER(C.c_double), i64p]
     L.sparta_frag_positions.argtypes = [C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), i32p]
     L.sparta_vbs_create_from_csr.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, i64p, i32p, f32p, i64p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]
     L.sparta_vbs_plan_stats.argtypes = [C.c_int64, C.c_int64, i64p, i32p, f32p, i64p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, i64p]

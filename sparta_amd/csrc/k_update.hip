@@ -3,6 +3,7 @@
 //   vbs_update_copy_kernel      the reference-layout image of an fp32 handle (d_A is mab itself)
 //   vbs_update_f32_frag_kernel  the fragment image of the fp32 one-tile plan (k_f32_direct.hip), k-compaction redone per step
 //   vbs_update_h16_kernel       the 16-bit slices of the stream plans and of the hub plan (k_h16.hip, k_hub16.hip)
+//   vbs_spmm_t_image_kernel     the 16-bit image of the transposed product (k_spmm_t.hip), handles made with SPARTA_CREATE_TRANSPOSE as well
 // Every kernel writes exactly the elements creation wrote (the slices behind the end of an image keep what creation left there) and reads mab
 // only where the plan says a stored element is: nothing is read past mab + nztot.  Offsets are 64-bit throughout.
 #include "vbs_kernel_common.hpp"
@@ -115,6 +116,29 @@ __global__ __launch_bounds__(kThreads) void vbs_update_h16_kernel(const UpdSlice
     }
 }
 
+// The image of sparta_vbs_spmm_t: per block [ceil(h / 8)][w][8] -- chunk c = kc * w + q holds rows 8 kc .. 8 kc + 7 of stored column q (rows past h: zeros), what
+// pack_spmm_t_block (vbs_plan.cpp) writes at creation.  One wave per block and pass; a lane writes one 16-byte chunk from 8 consecutive floats of one column of mab.
+template <bool BF16>
+__global__ __launch_bounds__(kThreads) void vbs_spmm_t_image_kernel(const SpmmTSrc* __restrict__ src, int64_t n_blocks, int w, const float* __restrict__ mab, uint16_t* __restrict__ dst) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int64_t bi = (int64_t)blockIdx.x * (kThreads / 64) + wave; bi < n_blocks; bi += (int64_t)gridDim.x * (kThreads / 64)) {
+        const SpmmTSrc s = src[bi];
+        const int64_t chunks = (int64_t)((s.h + 7) / 8) * w;
+        for (int64_t c = lane; c < chunks; c += 64) {
+            const int64_t kc = c / w, q = c - kc * w;
+            const float* sp = mab + s.src + q * s.h + kc * 8;
+            const int rem = s.h - (int)(kc * 8);
+            float x[8];
+#pragma unroll
+            for (int e = 0; e < 8; e++) x[e] = e < rem ? sp[e] : 0.0f;
+            u32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; e++) o[e] = upd_h16<BF16>(x[2 * e]) | (upd_h16<BF16>(x[2 * e + 1]) << 16);
+            *reinterpret_cast<u32x4*>(dst + s.dst + c * 8) = o;
+        }
+    }
+}
+
 unsigned upd_grid(int64_t work_items) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(work_items, kUpdMaxGrid)); }
 
 template <bool BF16>
@@ -143,6 +167,13 @@ void launch_update_h16(bool bf16, bool hub, int tms, int kp, hipStream_t st, con
     if (n_slices <= 0) return;
     if (bf16) launch_update_h16_t<true>(hub, tms, kp, st, map, n_slices, mab, dst);
     else launch_update_h16_t<false>(hub, tms, kp, st, map, n_slices, mab, dst);
+}
+
+void launch_update_h16_t(bool bf16, hipStream_t st, const SpmmTSrc* src, int64_t n_blocks, int w, const float* mab, uint16_t* dst) {
+    if (n_blocks <= 0) return;
+    const dim3 grid(upd_grid((n_blocks + kThreads / 64 - 1) / (kThreads / 64))), block(kThreads);
+    if (bf16) hipLaunchKernelGGL(vbs_spmm_t_image_kernel<true>, grid, block, 0, st, src, n_blocks, w, mab, dst);
+    else hipLaunchKernelGGL(vbs_spmm_t_image_kernel<false>, grid, block, 0, st, src, n_blocks, w, mab, dst);
 }
 
 }  // namespace sparta_dev

@@ -122,6 +122,12 @@ void destroy_impl(sparta_vbs* v) {
         if (v->d_upd_map[ty]) (void)hipFree(v->d_upd_map[ty]);
     if (v->d_upd_hub) (void)hipFree(v->d_upd_hub);
     if (v->d_upd_ws) (void)hipFree(v->d_upd_ws);
+    if (v->d_t_items) (void)hipFree(v->d_t_items);
+    if (v->d_t_blocks) (void)hipFree(v->d_t_blocks);
+    if (v->d_t_A) (void)hipFree(v->d_t_A);
+    if (v->d_t_src) (void)hipFree(v->d_t_src);
+    if (v->d_t_ws) (void)hipFree(v->d_t_ws);
+    if (v->d_t_h16) (void)hipFree(v->d_t_h16);
     if (v->ev0) (void)hipEventDestroy(v->ev0);
     if (v->ev1) (void)hipEventDestroy(v->ev1);
     for (int c = 0; c < 4; c++)
@@ -364,8 +370,10 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
                        int32_t device, const sparta::HybridSparse* ext, int32_t flags = 0) {
     using sparta::fail;
     if (!out) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: out is NULL");
-    if (flags & ~SPARTA_CREATE_UPDATABLE) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create_range_ex: unknown bits in flags");
+    if (flags & ~(SPARTA_CREATE_UPDATABLE | SPARTA_CREATE_TRANSPOSE)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create_range_ex: unknown bits in flags");
     const bool updatable = (flags & SPARTA_CREATE_UPDATABLE) != 0;        // every block-row stays in the dense-block images; the slices' sources are kept
+    const bool transposable = (flags & SPARTA_CREATE_TRANSPOSE) != 0;     // sparta_vbs_spmm_t: block-column index + an image it can read (changes nothing of the forward product)
+    if (transposable && ext) return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_create: SPARTA_CREATE_TRANSPOSE needs the dense blocks of every block-row");
     *out = nullptr;
     sparta::BuildTrace trace("vbs_create");
     if (rows <= 0 || cols <= 0 || block_rows <= 0 || w <= 0 || !row_part || !nzcount)
@@ -988,6 +996,32 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
             }
         }
     }
+    if (transposable) {
+        // the block-column index (pattern only) and, for 16-bit handles, the [ceil(h / 8)][w][8] image of k_spmm_t.hip; fp32 handles read d_A (kept: drop_legacy_image)
+        SpmmTIndexHost T;
+        if (int rc = build_spmm_t_index(cols, w, br0, br1, row_part, nzcount, jab, jab_lo, h16, T)) return rc;
+        v->n_t_items = (int64_t)T.items.size();
+        CREATE_TRY(hipMalloc((void**)&v->d_t_items, T.items.size() * sizeof(SpmmTItem)));
+        CREATE_TRY(hipMemcpy(v->d_t_items, T.items.data(), T.items.size() * sizeof(SpmmTItem), hipMemcpyHostToDevice));
+        if (!T.blocks.empty()) {
+            CREATE_TRY(hipMalloc((void**)&v->d_t_blocks, T.blocks.size() * sizeof(SpmmTBlock)));
+            CREATE_TRY(hipMemcpy(v->d_t_blocks, T.blocks.data(), T.blocks.size() * sizeof(SpmmTBlock), hipMemcpyHostToDevice));
+        }
+        if (h16 && T.image_elems > 0) {
+            std::unique_ptr<uint16_t[]> img(new uint16_t[(size_t)T.image_elems]);
+            sparta::parallel_for_dynamic((int64_t)T.src.size(), 64, [&](int64_t lo, int64_t hi, int) {
+                for (int64_t q = lo; q < hi; q++) pack_spmm_t_block(mab + mab_lo + T.src[(size_t)q].src, T.src[(size_t)q].h, w, bf16h, img.get() + T.src[(size_t)q].dst);
+            });
+            CREATE_TRY(hipMalloc((void**)&v->d_t_A, (size_t)T.image_elems * sizeof(uint16_t)));
+            CREATE_TRY(hipMemcpy(v->d_t_A, img.get(), (size_t)T.image_elems * sizeof(uint16_t), hipMemcpyHostToDevice));
+            v->a_bytes += T.image_elems * (int64_t)sizeof(uint16_t);
+            if (updatable) {
+                v->n_t_src = (int64_t)T.src.size();
+                CREATE_TRY(hipMalloc((void**)&v->d_t_src, T.src.size() * sizeof(SpmmTSrc)));
+                CREATE_TRY(hipMemcpy(v->d_t_src, T.src.data(), T.src.size() * sizeof(SpmmTSrc), hipMemcpyHostToDevice));
+            }
+        }
+    }
     CREATE_TRY(hipEventCreate(&v->ev0));
     CREATE_TRY(hipEventCreate(&v->ev1));
     CREATE_TRY(hipEventCreate(&v->tev0));
@@ -1424,6 +1458,7 @@ int ensure_legacy_image(sparta_vbs_t* A, hipStream_t st) {
 }
 void drop_legacy_image(sparta_vbs_t* A) {
     static const bool keep = [] { const char* e = std::getenv("SPARTA_F32_KEEP_LEGACY"); return e && atoi(e) != 0; }();
+    if (A->create_flags & SPARTA_CREATE_TRANSPOSE) return;      // sparta_vbs_spmm_t reads the reference-layout image
     if (keep || g_capturing || A->legacy_dropped || !A->d_A || !A->d_a_frag || A->dtype != SPARTA_F32 || A->n_steps[1] != 0 || A->n_sp_rows != 0 || A->class_timing) return;
     (void)hipFree(A->d_A);                               // (synchronises: the autotune's launches that read it are done)
     A->d_A = nullptr;
@@ -2327,6 +2362,7 @@ int set_values_impl(sparta_vbs_t* A, const float* mab, int32_t ptr_space, void* 
                 if (A->n_steps[ty] > 0)
                     launch_update_h16(bf16, false, ty ? 64 : 32, A->kp16, st, A->d_upd_map[ty], A->n_steps[ty], src, (uint16_t*)A->d_A + A->upd_base[ty]);
             if (A->n_upd_hub > 0) launch_update_h16(bf16, true, 64, 64, st, A->d_upd_hub, A->n_upd_hub, src, A->d_hub_A);
+            if (A->n_t_src > 0) launch_update_h16_t(bf16, st, A->d_t_src, A->n_t_src, (int)A->w, src, A->d_t_A);      // the image of sparta_vbs_spmm_t
         }
         HIP_TRY(hipGetLastError());
     }
@@ -2345,4 +2381,116 @@ extern "C" int sparta_vbs_set_values(sparta_vbs_t* A, const float* mab, int32_t 
     SPARTA_GUARD_BEGIN
     return set_values_impl(A, mab, ptr_space, stream, dt_ms);
     SPARTA_GUARD_END("sparta_vbs_set_values")
+}
+
+// ---- sparta_vbs_spmm_t (k_spmm_t.hip) ---------------------------------------------------------------------------------------------------
+namespace {
+
+int spmm_t_impl(sparta_vbs_t* A, const void* X, int64_t ldx, int32_t n_cols, float* Ct, int64_t ldo, int32_t accumulate, int32_t ptr_space, void* stream,
+                float* dt_ms) {
+    using sparta::fail;
+    if (!A || !X || !Ct) return fail(SPARTA_ERR_INVALID, "sparta_vbs_spmm_t: NULL argument");
+    if (n_cols <= 0) return fail(SPARTA_ERR_INVALID, "sparta_vbs_spmm_t: n_cols must be > 0");
+    if (ptr_space != SPARTA_PTR_HOST && ptr_space != SPARTA_PTR_DEVICE) return fail(SPARTA_ERR_INVALID, "sparta_vbs_spmm_t: bad ptr_space");
+    if (!(A->create_flags & SPARTA_CREATE_TRANSPOSE))
+        return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_spmm_t: the handle was not made with SPARTA_CREATE_TRANSPOSE (sparta_vbs_create_range_ex; handles of "
+                                            "sparta_vbs_create_from_csr and sparta_vbs_create_transposed cannot take the flag)");
+    if (ldx < A->rows || ldo < A->cols) return fail(SPARTA_ERR_INVALID, "sparta_vbs_spmm_t: ldx < rows or ldo < cols");
+    if (ldx > (INT64_C(1) << 61) / n_cols || ldo > (INT64_C(1) << 61) / n_cols) return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_spmm_t: ldx * n_cols or ldo * n_cols beyond 2^61");
+    const bool h16 = A->dtype != SPARTA_F32;
+    if (h16 && ptr_space == SPARTA_PTR_DEVICE && (ldx & 1)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_spmm_t: 16-bit handles need an even ldx");
+
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, "sparta_vbs_spmm_t: hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, ptr_space == SPARTA_PTR_DEVICE);
+    if (g_capturing && dt_ms) return capture_refusal("time the product (dt_ms != NULL synchronises)", "sparta_vbs_spmm_t");
+
+    const void* dX = X;
+    float* dC = Ct;
+    int64_t kx = ldx;
+    const size_t x_elems = (size_t)ldx * (size_t)(n_cols - 1) + (size_t)A->rows, c_elems = (size_t)ldo * (size_t)(n_cols - 1) + (size_t)A->cols;
+    if (ptr_space == SPARTA_PTR_HOST) {
+        // host in, host out: X and Ct staged in one device buffer (Ct whole, so that its padding rows come back as they went); 16-bit handles round X on the device
+        if (int rc = ensure_scratch(&A->d_t_ws, &A->d_t_ws_bytes, (x_elems + c_elems) * sizeof(float))) return rc;
+        float* ws = (float*)A->d_t_ws;
+        HIP_TRY(hipMemcpyAsync(ws, X, x_elems * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ws + x_elems, Ct, c_elems * sizeof(float), hipMemcpyHostToDevice, st));
+        dX = ws; dC = ws + x_elems;
+        if (h16) {
+            kx = (A->rows + 7) / 8 * 8;
+            if (int rc = ensure_scratch(&A->d_t_h16, &A->d_t_h16_bytes, (size_t)kx * (size_t)n_cols * sizeof(uint16_t))) return rc;
+            launch_convert_h16(A->dtype == SPARTA_BF16, st, ws, ldx, A->rows, n_cols, (uint16_t*)A->d_t_h16, kx);
+            HIP_TRY(hipGetLastError());
+            dX = A->d_t_h16;
+        }
+    }
+    SpmmTParams p;
+    p.items = A->d_t_items; p.blocks = A->d_t_blocks;
+    p.A = h16 ? (const void*)A->d_t_A : (const void*)A->d_A;
+    p.X = dX; p.Ct = dC;
+    p.ldx = kx; p.ldo = ldo; p.cols = A->cols;
+    p.n_cols = n_cols; p.w = (int32_t)A->w; p.accumulate = accumulate != 0; p.pad = 0;
+    if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
+    launch_spmm_t(A->dtype, (unsigned)A->n_t_items, st, p);
+    HIP_TRY(hipGetLastError());
+    if (dt_ms) {
+        HIP_TRY(hipEventRecord(A->ev1, st));
+        HIP_TRY(hipEventSynchronize(A->ev1));
+        HIP_TRY(hipEventElapsedTime(dt_ms, A->ev0, A->ev1));
+    }
+    if (ptr_space == SPARTA_PTR_HOST) {
+        HIP_TRY(hipMemcpyAsync(Ct, dC, c_elems * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return SPARTA_OK;
+}
+
+}  // namespace
+
+extern "C" int sparta_vbs_spmm_t(sparta_vbs_t* A, const void* X, int64_t ldx, int32_t n_cols, float* Ct, int64_t ldo, int32_t accumulate, int32_t ptr_space,
+                                 void* stream, float* dt_ms) {
+    SPARTA_GUARD_BEGIN
+    return spmm_t_impl(A, X, ldx, n_cols, Ct, ldo, accumulate, ptr_space, stream, dt_ms);
+    SPARTA_GUARD_END("sparta_vbs_spmm_t")
+}
+
+// the block-column index of sparta_vbs_spmm_t, built by the function create calls and walked on the HOST the way k_spmm_t.hip walks it (an item's stored columns,
+// each summed over the item's list in list order) for one vector: what the CPU suite checks the builder with (no GPU involved; not a product path)
+extern "C" int sparta_spmm_t_host_check(int64_t rows, int64_t cols, int64_t block_rows, int64_t w, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab,
+                                        const float* mab, int64_t br0, int64_t br1, const float* x, double* y, int64_t* info_out) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    if (rows <= 0 || cols <= 0 || block_rows <= 0 || w <= 0 || !row_part || !nzcount || !x || !y || !info_out)
+        return fail(SPARTA_ERR_INVALID, "sparta_spmm_t_host_check: bad dimensions or NULL argument");
+    if (br0 < 0 || br1 > block_rows || br0 >= br1) return fail(SPARTA_ERR_INVALID, "sparta_spmm_t_host_check: bad block-row range");
+    if (row_part[0] != 0 || row_part[block_rows] != rows) return fail(SPARTA_ERR_INVALID, "sparta_spmm_t_host_check: row_part must span [0, rows]");
+    const int64_t block_cols = (cols - 1) / w + 1;
+    int64_t jab_lo = 0, mab_lo = 0, nblocks = 0;
+    for (int64_t ib = 0; ib < br1; ib++) {
+        const int64_t h = row_part[ib + 1] - row_part[ib];
+        if (h < 0 || nzcount[ib] < 0 || nzcount[ib] > block_cols) return fail(SPARTA_ERR_INVALID, "sparta_spmm_t_host_check: invalid row_part / nzcount");
+        if (ib < br0) { jab_lo += nzcount[ib]; mab_lo += nzcount[ib] * h * w; }
+        else nblocks += nzcount[ib];
+    }
+    if (nblocks > 0 && (!jab || !mab)) return fail(SPARTA_ERR_INVALID, "sparta_spmm_t_host_check: jab / mab is NULL");
+    SpmmTIndexHost T;
+    if (int rc = build_spmm_t_index(cols, w, br0, br1, row_part, nzcount, jab, jab_lo, false, T)) return rc;
+    for (int64_t c = 0; c < cols; c++) y[c] = 0.0;
+    for (const SpmmTItem& it : T.items)
+        for (int64_t q = it.q0; q < std::min<int64_t>(it.q0 + 32, w); q++) {
+            const int64_t col = (int64_t)it.jb * w + q;
+            if (col >= cols) continue;
+            double sum = 0.0;
+            for (int32_t l = it.l0; l < it.l1; l++) {
+                const SpmmTBlock& b = T.blocks[(size_t)l];
+                const float* a = mab + mab_lo + b.off + q * b.h;
+                for (int32_t i = 0; i < b.h; i++) sum += (double)a[i] * (double)x[b.r0 + i];
+            }
+            y[col] = sum;
+        }
+    std::memset(info_out, 0, 8 * sizeof(int64_t));
+    info_out[0] = T.cols_with_blocks; info_out[1] = (int64_t)T.items.size(); info_out[2] = T.max_list; info_out[3] = 0;
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_spmm_t_host_check")
 }

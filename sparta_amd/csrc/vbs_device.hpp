@@ -3,6 +3,7 @@
 //   k_f32_stream.hip  persistent fp32 stream kernels, fix-up, B-tail copy, zero fill
 //   k_h16.hip         fp16 / bf16 storage: LDS-staged and direct stream kernels, conversions
 //   k_sparse.hip      sparse-row kernels, layout transposes, row-block pack
+//   k_spmm_t.hip      the transposed product on a handle's own stored blocks (sparta_vbs_spmm_t)
 //   k_update.hip      new values for the images of an updatable handle (sparta_vbs_set_values)
 //   vbs_plan.cpp      host: stream plans (step lists, worker ranges, split tiles)
 //   vbs_capi.cpp      host: device image (sparta_vbs), sparta_vbs_create* / sparta_vbs_spmm* (include/sparta_amd.h)
@@ -265,6 +266,26 @@ struct UpdSlice {
 };
 static_assert(sizeof(UpdSlice) == 32, "UpdSlice must stay 32 bytes");
 
+// sparta_vbs_spmm_t (k_spmm_t.hip): Ct (+)= A^T X walks A by block column.  The index (pattern only, built at creation): per block column the list of
+// its blocks, in block-row order; a work item = one panel of <= 32 stored columns of one block column x its whole list.  The image the kernel reads:
+// fp32 handles the reference-layout image (block = column-major h x w: column q is h consecutive floats at off + q * h); 16-bit handles an image of
+// their own, per block [ceil(h / 8)][w][8]: chunk (kc, q) = rows 8 kc .. 8 kc + 7 of stored column q at off + (kc * w + q) * 8, rows past h zero.
+struct SpmmTBlock { int64_t off; int32_t h, r0; };            // element offset of the block in the image, its height, its first row of X
+static_assert(sizeof(SpmmTBlock) == 16, "SpmmTBlock must stay 16 bytes");
+struct SpmmTItem { int32_t jb, q0, l0, l1; };                 // block column, first stored column of the panel, blocks[l0 .. l1) (empty: the item writes zeros)
+struct SpmmTSrc { int64_t src, dst; int32_t h, pad0; int64_t pad1; };   // 16-bit image: block at mab + src (column-major h x w) -> image + dst
+static_assert(sizeof(SpmmTSrc) == 32, "SpmmTSrc must stay 32 bytes");
+struct SpmmTParams {
+    const SpmmTItem* items;
+    const SpmmTBlock* blocks;
+    const void* A;                  // the image (fp32 / 16-bit)
+    const void* X;                  // rows x n_cols, column-major (fp32, or the handle's 16-bit type)
+    float* Ct;                      // cols x n_cols, column-major
+    int64_t ldx, ldo, cols;
+    int32_t n_cols, w, accumulate, pad;
+};
+constexpr int kSpmmTSlab = 128;     // columns of X / Ct per workgroup (32 per wave)
+
 #define HIP_TRY(expr)                                                                                   \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \
@@ -423,6 +444,17 @@ struct sparta_vbs {
     int64_t n_upd_hub = 0;
     void* d_upd_ws = nullptr;
     size_t d_upd_ws_bytes = 0;
+    // sparta_vbs_spmm_t (SPARTA_CREATE_TRANSPOSE handles only): the block-column index, the 16-bit image, the sources of its blocks; host-pointer calls stage X, Ct
+    sparta_dev::SpmmTItem* d_t_items = nullptr;
+    sparta_dev::SpmmTBlock* d_t_blocks = nullptr;
+    int64_t n_t_items = 0;
+    uint16_t* d_t_A = nullptr;                                 // 16-bit handles: [ceil(h / 8)][w][8] per block, blocks in mab order
+    sparta_dev::SpmmTSrc* d_t_src = nullptr;                   // 16-bit handles with both flags: one record per block (set_values)
+    int64_t n_t_src = 0;
+    void* d_t_ws = nullptr;
+    size_t d_t_ws_bytes = 0;
+    void* d_t_h16 = nullptr;
+    size_t d_t_h16_bytes = 0;
 };
 
 namespace sparta_dev {
@@ -472,6 +504,10 @@ void launch_update_copy(hipStream_t st, const float* mab, int64_t n, float* A); 
 void launch_update_f32_frag(hipStream_t st, StepRec* steps, int64_t n_steps, const float* mab, float* a_frag, float* A_out);
 // 16-bit slices of tms rows x kp columns ([k / 8][row][8]; hub: the swizzled 64 x 64 image of k_hub16.hip), rounded as to_h16 rounds
 void launch_update_h16(bool bf16, bool hub, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, const float* mab, uint16_t* dst);
+// the 16-bit image of the transposed product, one workgroup pass per block (rounded as to_h16 rounds)
+void launch_update_h16_t(bool bf16, hipStream_t st, const SpmmTSrc* src, int64_t n_blocks, int w, const float* mab, uint16_t* dst);
+// k_spmm_t.hip: grid = n_items x slabs of kSpmmTSlab columns; dtype = SPARTA_F32 / F16 / BF16
+void launch_spmm_t(int dtype, unsigned n_items, hipStream_t st, const SpmmTParams& p);
 // k_colres.hip
 int launch_colres(int nc, const ColresParams& p, size_t lds_bytes, hipStream_t st);     // nc = 1..4 columns per workgroup; 0 or a hipError_t
 int colres_max_slices(int nc);                                                          // slices the nc-column kernel holds sums for
@@ -535,6 +571,19 @@ void union_plan_host_apply(const UnionDevPlan& P, const float* x, double* y);
 
 constexpr int64_t kZeroRangeRows = 2048;    // block-rows without blocks at least this tall are zero-filled by vbs_zero_rows_kernel
 int build_stream_plans(const StreamPlanIn& in, StreamPlanHost& P);
+// the block-column index of sparta_vbs_spmm_t for the block-rows [br0, br1) (jab: the whole array, jab_lo its offset of block-row br0); h16: offsets into the
+// 16-bit image (and the `src` records), else into mab from the range's first element
+struct SpmmTIndexHost {
+    std::vector<SpmmTBlock> blocks;
+    std::vector<SpmmTItem> items;
+    std::vector<SpmmTSrc> src;                // h16 only, mab order
+    int64_t image_elems = 0;                  // h16 only
+    int64_t cols_with_blocks = 0, max_list = 0;
+};
+int build_spmm_t_index(int64_t cols, int64_t w, int64_t br0, int64_t br1, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, int64_t jab_lo, bool h16,
+                       SpmmTIndexHost& T);
+// one block of the 16-bit image from its column-major h x w source
+void pack_spmm_t_block(const float* blk, int64_t h, int64_t w, bool bf16, uint16_t* dst);
 uint16_t to_h16(float v, bool bf16);   // fp32 -> fp16 / bf16 bits, round to nearest even (what the device conversion kernel does too)
 
 }  // namespace sparta_dev

@@ -895,4 +895,62 @@ int build_stream_plans(const StreamPlanIn& in, StreamPlanHost& P) {
     return SPARTA_OK;
 }
 
+// ---- sparta_vbs_spmm_t: the block-column index ------------------------------------------------------------------------------------------
+// Counting sort of the range's blocks by block column (block-row order inside a column: the order the kernel adds them in).  One item per
+// block column and panel of <= 32 stored columns, the block columns without a block included (their items write the zeros of accumulate = 0).
+int build_spmm_t_index(int64_t cols, int64_t w, int64_t br0, int64_t br1, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, int64_t jab_lo, bool h16,
+                       SpmmTIndexHost& T) {
+    const int64_t block_cols = (cols - 1) / w + 1, panels = (w + 31) / 32;
+    if (block_cols > INT32_MAX || block_cols * panels > INT32_MAX) return sparta::fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_create: more than 2^31 - 1 work items of the transposed product");
+    std::vector<int64_t> ptr((size_t)block_cols + 1, 0);
+    int64_t jo = 0;
+    for (int64_t ib = br0; ib < br1; ib++) {
+        const int64_t h = row_part[ib + 1] - row_part[ib];
+        for (int64_t b = 0; b < nzcount[ib]; b++) {
+            const int64_t jb = jab[jab_lo + jo + b];
+            if (jb < 0 || jb >= block_cols) return sparta::fail(SPARTA_ERR_INVALID, "sparta_vbs_create: jab entry out of range");
+            if (h > 0) ptr[(size_t)jb + 1]++;
+        }
+        jo += nzcount[ib];
+    }
+    for (int64_t j = 0; j < block_cols; j++) {
+        T.cols_with_blocks += ptr[(size_t)j + 1] > 0;
+        T.max_list = std::max(T.max_list, ptr[(size_t)j + 1]);
+        ptr[(size_t)j + 1] += ptr[(size_t)j];
+    }
+    if (ptr.back() > INT32_MAX) return sparta::fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_create: more than 2^31 - 1 blocks for the transposed product");
+    T.blocks.resize((size_t)ptr.back());
+    std::vector<int64_t> at(ptr.begin(), ptr.end() - 1);
+    const int64_t row0 = row_part[br0];
+    int64_t mo = 0, to = 0;
+    jo = 0;
+    for (int64_t ib = br0; ib < br1; ib++) {
+        const int64_t h = row_part[ib + 1] - row_part[ib];
+        const int64_t t_block = (h + 7) / 8 * 8 * w;                      // elements of one block in the 16-bit image
+        for (int64_t b = 0; b < nzcount[ib] && h > 0; b++) {
+            const int64_t jb = jab[jab_lo + jo + b];
+            T.blocks[(size_t)at[(size_t)jb]++] = SpmmTBlock{h16 ? to : mo, (int32_t)h, (int32_t)(row_part[ib] - row0)};
+            if (h16) T.src.push_back(SpmmTSrc{mo, to, (int32_t)h, 0, 0});
+            mo += h * w;
+            to += t_block;
+        }
+        jo += nzcount[ib];
+    }
+    T.image_elems = to;
+    T.items.reserve((size_t)(block_cols * panels));
+    for (int64_t j = 0; j < block_cols; j++)
+        for (int64_t q0 = 0; q0 < w; q0 += 32) T.items.push_back(SpmmTItem{(int32_t)j, (int32_t)q0, (int32_t)ptr[(size_t)j], (int32_t)ptr[(size_t)j + 1]});
+    return SPARTA_OK;
+}
+
+void pack_spmm_t_block(const float* blk, int64_t h, int64_t w, bool bf16, uint16_t* dst) {
+    const int64_t chunks = (h + 7) / 8;
+    for (int64_t kc = 0; kc < chunks; kc++)
+        for (int64_t q = 0; q < w; q++)
+            for (int64_t e = 0; e < 8; e++) {
+                const int64_t i = kc * 8 + e;
+                dst[(kc * w + q) * 8 + e] = i < h ? to_h16(blk[q * h + i], bf16) : (uint16_t)0;
+            }
+}
+
 }  // namespace sparta_dev

@@ -16,9 +16,10 @@ def device_count():
 class DeviceVBS:
     """Opaque device image of a VBS matrix + its tile plan (sparta_vbs_t)."""
 
-    def __init__(self, vbmat, device=0, dtype=_lib.F32, block_row_range=None, updatable=False):
+    def __init__(self, vbmat, device=0, dtype=_lib.F32, block_row_range=None, updatable=False, transposable=False):
         """updatable=True (SPARTA_CREATE_UPDATABLE): the handle takes new values for the same block pattern through set_values; it keeps every
-        block-row on the dense-block kernels (none moves to the sparse-row kernels)."""
+        block-row on the dense-block kernels (none moves to the sparse-row kernels).  transposable=True (SPARTA_CREATE_TRANSPOSE): the handle
+        also takes spmm_t (Ct = A^T X on its own blocks); its forward product is that of a plain handle."""
         self.device = int(device)
         self.dtype = dtype
         self.h = C.c_void_p(None)
@@ -32,7 +33,7 @@ class DeviceVBS:
         check(lib.sparta_vbs_create_range_ex(C.byref(self.h), vbmat.rows, vbmat.cols, vbmat.block_rows, vbmat.block_col_size,
                                              rp.ctypes.data_as(_i64p), nz.ctypes.data_as(_i64p), jab.ctypes.data_as(_i64p),
                                              mab.ctypes.data_as(_f32p), int(b0), int(b1), int(dtype), self.device,
-                                             _lib.CREATE_UPDATABLE if updatable else 0))
+                                             (_lib.CREATE_UPDATABLE if updatable else 0) | (_lib.CREATE_TRANSPOSE if transposable else 0)))
         info = self.info()
         self.rows, self.cols = info["rows"], info["cols"]
 
@@ -226,6 +227,53 @@ class DeviceVBS:
         f = C.c_int32(0)
         check(lib.sparta_vbs_flags(self.h, C.byref(f)))
         return bool(f.value & _lib.CREATE_UPDATABLE)
+
+    @property
+    def transposable(self):
+        """was the handle created with transposable=True (sparta_vbs_flags)?"""
+        f = C.c_int32(0)
+        check(lib.sparta_vbs_flags(self.h, C.byref(f)))
+        return bool(f.value & _lib.CREATE_TRANSPOSE)
+
+    def spmm_t(self, X, Ct_out, n_cols, accumulate=False, ldx=None, ldo=None, timed=False, stream=None):
+        """Ct (+)= A^T * X on the stored blocks (sparta_vbs_spmm_t), device tensors: X rows x n_cols, column-major (ldx), in the handle's B dtype;
+        Ct_out cols x n_cols, column-major (ldo), float32.  With X = dC of C = A * B, Ct is the gradient of B.  Needs transposable=True.
+        Stream-ordered on torch's current stream.  Returns kernel ms if timed else None."""
+        import torch
+        want = {_lib.F32: torch.float32, _lib.F16: torch.float16, _lib.BF16: torch.bfloat16}[self.dtype]
+        if not (X.is_cuda and Ct_out.is_cuda and X.dtype == want and Ct_out.dtype == torch.float32):
+            raise ValueError("X must be a %s tensor and Ct a float32 tensor, both on the GPU" % want)
+        if X.device.index != self.device or Ct_out.device.index != self.device:
+            raise ValueError("X and Ct must live on device %d" % self.device)
+        n_cols = int(n_cols)
+        if n_cols <= 0:
+            raise ValueError("n_cols must be > 0")
+        ldx = self.rows if ldx is None else int(ldx)
+        ldo = self.cols if ldo is None else int(ldo)
+        if (X.numel() < ldx * (n_cols - 1) + self.rows or Ct_out.numel() < ldo * (n_cols - 1) + self.cols
+                or not X.is_contiguous() or not Ct_out.is_contiguous()):
+            raise ValueError("X or Ct too small / not contiguous for the stated leading dimensions")
+        st = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+        dt = C.c_float(0)
+        check(lib.sparta_vbs_spmm_t(self.h, C.c_void_p(X.data_ptr()), ldx, n_cols, C.cast(C.c_void_p(Ct_out.data_ptr()), _f32p), ldo,
+                                    int(bool(accumulate)), _lib.PTR_DEVICE, C.c_void_p(st), C.byref(dt) if timed else None))
+        return dt.value if timed else None
+
+    def spmm_t_host(self, X, n_cols, Ct_out, accumulate=True):
+        """spmm_t with host buffers (numpy, fp32; X rounded on the device for 16-bit handles): X rows x n_cols, column-major (ld = rows);
+        Ct_out a contiguous float32 array of >= cols * n_cols elements (ld = cols), written in place.  Returns kernel ms."""
+        X = np.ascontiguousarray(X, np.float32).reshape(-1)
+        if not (isinstance(Ct_out, np.ndarray) and Ct_out.dtype == np.float32 and Ct_out.flags.c_contiguous):
+            raise ValueError("Ct must be a contiguous float32 numpy array (it is written in place)")
+        n_cols = int(n_cols)
+        if n_cols <= 0:
+            raise ValueError("n_cols must be > 0")
+        if X.size < self.rows * n_cols or Ct_out.size < self.cols * n_cols:
+            raise ValueError("X or Ct too small")
+        dt = C.c_float(0)
+        check(lib.sparta_vbs_spmm_t(self.h, X.ctypes.data_as(C.c_void_p), self.rows, n_cols, Ct_out.ctypes.data_as(_f32p), self.cols,
+                                    int(bool(accumulate)), _lib.PTR_HOST, None, C.byref(dt)))
+        return dt.value
 
     def set_values(self, mab, timed=False, stream=None):
         """sparta_vbs_set_values, device tensor: new values for the stored blocks (same pattern), a contiguous float32 tensor of nztot elements

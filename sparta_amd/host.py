@@ -207,11 +207,12 @@ class VBR:
         self.block_col_size = 0
         self.nztot = 0
         self.nzcount = self.jab = self.row_part = self.mab = None
-        self._dev = self._dev_t = None
+        self._dev = self._dev_t = self._dev_tp = None
 
     def _drop_device_images(self):
-        """the cached device handles (of A for multiply, of A^T for multiply_BA) describe the OLD arrays: close and forget both"""
-        for name in ("_dev", "_dev_t"):
+        """the cached device handles (of A for multiply, of A^T for multiply_BA, the transposable one of multiply_T) describe the OLD arrays:
+        close and forget them"""
+        for name in ("_dev", "_dev_t", "_dev_tp"):
             d = getattr(self, name, None)
             if d is not None:
                 d.close()
@@ -337,9 +338,9 @@ class VBR:
         finally:
             lib.sparta_vbs_host_free(C.byref(h))
 
-    def to_device(self, device=0, dtype=_lib.F32, block_row_range=None, updatable=False):
+    def to_device(self, device=0, dtype=_lib.F32, block_row_range=None, updatable=False, transposable=False):
         from .device import DeviceVBS
-        return DeviceVBS(self, device=device, dtype=dtype, block_row_range=block_row_range, updatable=updatable)
+        return DeviceVBS(self, device=device, dtype=dtype, block_row_range=block_row_range, updatable=updatable, transposable=transposable)
 
     def set_values(self, mab):
         """New values for the stored blocks, same pattern: replaces self.mab (nztot float32 values in its layout).  A cached device image of A that
@@ -349,14 +350,28 @@ class VBR:
         if mab.size != int(self.nztot):
             raise ValueError("mab must hold nztot = %d elements" % int(self.nztot))
         self.mab = mab.copy()
-        dev = self._dev if self._dev is not None and self._dev.updatable else None
-        if dev is not None:
-            self._dev = None                               # (kept out of _drop_device_images' reach)
+        keep = {}
+        for name in ("_dev", "_dev_tp"):
+            d = getattr(self, name, None)
+            if d is not None and d.updatable:
+                keep[name] = d
+                setattr(self, name, None)                  # (kept out of _drop_device_images' reach)
         self._drop_device_images()
-        if dev is not None:
-            dev.set_values_host(self.mab)
-            self._dev = dev
+        for name, d in keep.items():
+            d.set_values_host(self.mab)
+            setattr(self, name, d)
         return self
+
+    def multiply_T(self, X, n_cols, Ct_out=None, device=0):
+        """Ct += A^T * X (the gradient of B for C = A * B with X = dC): host buffers, column-major, X rows x n_cols (ld = rows), Ct cols x n_cols
+        (ld = cols); Ct_out None starts from zeros.  Executed on the GPU on a cached transposable, updatable image of this matrix
+        (sparta_vbs_spmm_t), which set_values updates in place.  Returns Ct_out.  No reference counterpart."""
+        if Ct_out is None:
+            Ct_out = np.zeros(int(self.cols) * int(n_cols), np.float32)
+        if getattr(self, "_dev_tp", None) is None or self._dev_tp.device != device:
+            self._dev_tp = self.to_device(device, updatable=True, transposable=True)
+        self._dev_tp.spmm_t_host(X, n_cols, Ct_out, accumulate=True)
+        return Ct_out
 
     def multiply_BA(self, B, B_rows, C_out, device=0):
         """C += B * A (dense x VBS), host buffers, column-major: B is B_rows x rows, C is B_rows x cols.  The reference's
