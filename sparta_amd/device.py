@@ -13,7 +13,17 @@ def device_count():
     return int(lib.sparta_device_count())
 
 
-class DeviceVBS:
+class ValuesRecord:
+    """vbs_linear's record, kept on a handle, of which tensor (at which version) the handle's values were last taken from (autograd.py).  Whatever
+    gives the handle other values, or none, calls _values_replaced(); a handle class of its own that vbs_linear is to drive derives from this."""
+    _autograd_values = None                    # (tensor, version) or None
+    _autograd_captured = False                 # a forward was recorded into a graph: replays change the values unseen, so nothing is skipped any more
+
+    def _values_replaced(self):
+        self._autograd_values = None
+
+
+class DeviceVBS(ValuesRecord):
     """Opaque device image of a VBS matrix + its tile plan (sparta_vbs_t)."""
 
     def __init__(self, vbmat, device=0, dtype=_lib.F32, block_row_range=None, updatable=False, transposable=False):
@@ -286,6 +296,7 @@ class DeviceVBS:
             raise ValueError("mab must hold nztot = %d elements" % self._nztot())
         st = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
         dt = C.c_float(0)
+        self._values_replaced()
         check(lib.sparta_vbs_set_values(self.h, C.cast(C.c_void_p(mab.data_ptr()), _f32p), _lib.PTR_DEVICE, C.c_void_p(st),
                                         C.byref(dt) if timed else None))
         return dt.value if timed else None
@@ -296,6 +307,7 @@ class DeviceVBS:
         if mab.size != self._nztot():
             raise ValueError("mab must hold nztot = %d elements" % self._nztot())
         dt = C.c_float(0)
+        self._values_replaced()
         check(lib.sparta_vbs_set_values(self.h, mab.ctypes.data_as(_f32p), _lib.PTR_HOST, None, C.byref(dt)))
         return dt.value
 
@@ -403,6 +415,7 @@ class DeviceVBS:
         return {"class16": float(a[0]), "class32": float(a[1]), "class64": float(a[2])}
 
     def close(self):
+        self._values_replaced()
         if self.h:
             lib.sparta_vbs_destroy(self.h)
             self.h = C.c_void_p(None)

@@ -479,31 +479,32 @@ def test_forward_of_a_transposable_handle_has_the_bits_of_a_plain_one(mats, dtyp
         P.close(); T.close()
 
 
+def dense_and_mask(v, mab):
+    """A (rows x cols, float64) and, per stored position of mab, its (row, column) or column -1 past cols"""
+    w = v.block_col_size
+    A = fwd_oracle(v, mab, np.eye(v.cols))
+    rr, cc = np.zeros(int(v.nztot), np.int64), np.zeros(int(v.nztot), np.int64)
+    jo = mo = 0
+    for ib in range(v.block_rows):
+        r0, h, nb = int(v.row_part[ib]), int(v.row_part[ib + 1] - v.row_part[ib]), int(v.nzcount[ib])
+        for b in range(nb):
+            c = int(v.jab[jo + b]) * w + np.repeat(np.arange(w), h)
+            rr[mo + b * w * h: mo + (b + 1) * w * h] = r0 + np.tile(np.arange(h), w)
+            cc[mo + b * w * h: mo + (b + 1) * w * h] = np.where(c < v.cols, c, -1)
+        jo += nb
+        mo += nb * h * w
+    return A, rr, cc
+
+
 @pytest.mark.parametrize("key,dtype", [("grid32", sa.F32), ("jaccard", sa.F16)], ids=["grid32-f32", "jaccard-f16"])
 def test_vbs_linear_against_torch(mats, key, dtype):
     """the 300 x 517 matrix (fp32; a 16-bit handle takes its operands with an even leading dimension, so the f16 case runs on the 300 x 700 one): y, grad_x,
     grad_values against torch.nn.functional.linear with the dense A (reordered rows) in float64; two SGD steps in a row"""
     from sparta_amd.autograd import vbs_linear
     v = mats[key]
-    w = v.block_col_size
     tdt = TDT[dtype]
     H = v.to_device(0, dtype=dtype, updatable=True, transposable=True)
     n = 24
-
-    def dense_and_mask(mab):
-        """A (rows x cols, float64) and, per stored position of mab, its (row, column) or column -1 past cols"""
-        A = fwd_oracle(v, mab, np.eye(v.cols))
-        rr, cc = np.zeros(int(v.nztot), np.int64), np.zeros(int(v.nztot), np.int64)
-        jo = mo = 0
-        for ib in range(v.block_rows):
-            r0, h, nb = int(v.row_part[ib]), int(v.row_part[ib + 1] - v.row_part[ib]), int(v.nzcount[ib])
-            for b in range(nb):
-                c = int(v.jab[jo + b]) * w + np.repeat(np.arange(w), h)
-                rr[mo + b * w * h: mo + (b + 1) * w * h] = r0 + np.tile(np.arange(h), w)
-                cc[mo + b * w * h: mo + (b + 1) * w * h] = np.where(c < v.cols, c, -1)
-            jo += nb
-            mo += nb * h * w
-        return A, rr, cc
 
     for integer in (True, False):
         V = values(v, 30 + integer, integer=integer)
@@ -515,7 +516,7 @@ def test_vbs_linear_against_torch(mats, key, dtype):
         y = vbs_linear(x, H, W)
         y.backward(gy)
         torch.cuda.synchronize()
-        A, rr, cc = dense_and_mask(rounded(V, dtype))
+        A, rr, cc = dense_and_mask(v, rounded(V, dtype))
         xr = x.detach().double().cpu()
         gyr = gy.to(tdt).double().cpu()
         At = torch.from_numpy(A).requires_grad_(True)
@@ -548,7 +549,7 @@ def test_vbs_linear_against_torch(mats, key, dtype):
     cur = V.astype(np.float64)
     for step in range(2):
         y = vbs_linear(x, H, W)
-        A, rr, cc = dense_and_mask(cur)
+        A, rr, cc = dense_and_mask(v, cur)
         assert np.array_equal(y.detach().cpu().numpy(), (x64 @ A.T).astype(np.float32)), step
         gy64 = np.sign(dense_x(v.rows, 8, 42 + step, integer=True).T)            # entries -1, 0, 1: the updated values stay small integers
         y.backward(torch.from_numpy(gy64).cuda().float())
