@@ -10,6 +10,7 @@ import sparta_amd as sa
 from sparta_amd import _lib
 from sparta_amd._lib import lib
 
+import _util as U
 from test_code_object import _kernel_metadata
 from test_sddmm_gpu import build_mats
 
@@ -101,6 +102,19 @@ def test_index_walk_equals_numpy(mats, key):
     assert info[0] == len(np.unique(v.jab))
     panels = -(-v.block_col_size // 32)
     assert info[1] == (-(-v.cols // v.block_col_size)) * panels and info[3] == 0 and info[2] >= 1
+
+
+@pytest.mark.parametrize("key", sorted(set(U.TRAIN_F32 + U.TRAIN_H16)))
+def test_index_walk_over_the_training_geometries(key):
+    """the geometries of tests/test_train_geometry_gpu.py: w = 3 (29 of a panel's 32 columns masked), 13 with h = 1 and with block-rows of height 0, 48 and 96 (a panel
+    of 16 / 32 behind full ones), 100 (32 + 32 + 32 + 4), 128 to 256 (four to eight panels per block column), heights up to 465, block-rows without a block"""
+    v = with_integer_values(U.train_geometries()[key], 9)
+    x = np.random.default_rng(10).integers(-4, 5, v.rows).astype(np.float32)
+    y, info = host_check(v, x)
+    assert np.array_equal(y, dense_of(v).T @ x.astype(np.float64))
+    assert info[3] == 0                                               # no block column is split: one owner per element of y
+    w = v.block_col_size
+    assert info[0] == len(np.unique(v.jab)) and info[1] == (-(-v.cols // w)) * (-(-w // 32)) and info[2] >= 1
 
 
 def test_index_walk_with_empty_block_columns_and_sub_range():
