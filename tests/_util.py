@@ -116,3 +116,178 @@ def abs_bound(rows, cols, w, row_part, nzcount, jab, mab, B, n):
     """sum_k |a||b| per element of C (oracle arithmetic): the scale of the fp32 tolerance 1e-5 * sum|a||b|"""
     from oracle import oracle as O
     return O.vbr_multiply(rows, cols, w, row_part, nzcount, jab, np.abs(mab), np.abs(B), n)
+
+
+# ---- edge geometries: tiny VBS matrices written out as arrays, shapes a builder-made test matrix never has ------------------------------------------------
+EDGE_F32 = ("one", "rowvec", "colvec", "narrow32", "empty", "corner", "zeros", "tall", "heights", "dense", "w1", "corner64", "heights64")
+EDGE_H16 = ("rowvec", "narrow32", "empty", "corner", "zeros", "tall", "dense", "heights32", "tall64")          # 16-bit handles need w % 32 == 0
+EDGE_HEIGHTS = (0, 1, 0, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 0, 52, 0)
+_edge = {}
+
+
+def _edge_arrays(rows, cols, w, heights, present):
+    """(rows, cols, w, row_part, nzcount, jab) from the heights of the block-rows and, per block-row, the ascending list of its block columns"""
+    heights = [int(h) for h in heights]
+    assert sum(heights) == rows and len(present) == len(heights)
+    row_part = np.concatenate([[0], np.cumsum(heights)]).astype(np.int64)
+    nzcount = np.array([len(p) for p in present], np.int64)
+    jab = np.array([j for p in present for j in p], np.int64)
+    return rows, cols, w, row_part, nzcount, jab
+
+
+def edge_blocks(v, br=None):
+    """(offset into mab, first row, h, first column, stored columns inside the matrix) of every stored block of the block-rows br = (b0, b1); offsets and rows
+    count from the start of the range, as a range handle sees them"""
+    b0, b1 = (0, v.block_rows) if br is None else br
+    w = int(v.block_col_size)
+    out, mo, jo = [], 0, int(np.sum(v.nzcount[:b0]))
+    for ib in range(b0, b1):
+        h = int(v.row_part[ib + 1] - v.row_part[ib])
+        for b in range(int(v.nzcount[ib])):
+            c0 = int(v.jab[jo + b]) * w
+            out.append((mo, int(v.row_part[ib] - v.row_part[b0]), h, c0, min(w, v.cols - c0)))
+            mo += h * w
+        jo += int(v.nzcount[ib])
+    return out
+
+
+def edge_mab_slice(v, br):
+    """(lo, hi): the elements of v.mab that belong to the block-rows br"""
+    hts = np.diff(v.row_part) * v.nzcount * int(v.block_col_size)
+    return int(hts[:br[0]].sum()), int(hts[:br[1]].sum())
+
+
+def _edge_values(arr, kind, seed, zero_blocks=()):
+    """seeded values in the mab layout: 'int' -3..3 without a zero, 'real' uniform(-1, 1).  The positions of a ragged last block column past cols hold seeded
+    NON-ZERO values as well (a builder stores 0 there; a caller of the C-ABI need not): they lie outside the matrix and must take no part in any product, so a
+    kernel that reads rows of B at or past cols meets a non-zero factor.  The stored blocks listed in zero_blocks hold 0.0 everywhere."""
+    rows, cols, w, row_part, nzcount, jab = arr
+    v = sa_vbr(arr, np.zeros(int((np.diff(row_part) * nzcount).sum()) * w, np.float32))
+    rng = np.random.default_rng(seed)
+    if kind == "int":
+        x = rng.integers(-3, 4, v.nztot).astype(np.float32)
+        x[x == 0] = 2.0
+    else:
+        x = rng.uniform(-1, 1, v.nztot).astype(np.float32)
+        x[x == 0] = 0.5
+    for q, (off, _, h, _, _) in enumerate(edge_blocks(v)):
+        if q in zero_blocks:
+            x[off:off + w * h] = 0.0
+    return x
+
+
+def sa_vbr(arr, mab):
+    import sparta_amd as sa
+    rows, cols, w, row_part, nzcount, jab = arr
+    return sa.VBR.from_arrays(rows, cols, w, row_part, nzcount, jab, mab)
+
+
+def edge_geometries(values="int"):
+    """key -> VBR made with VBR.from_arrays from index arrays written out here (no builder involved), with seeded values (_edge_values: the stored positions past cols are non-zero too): values = 'int' (-3 .. 3, no zero
+    inside a stored block unless the geometry says so: every order of additions gives the same bits) or 'real' (uniform(-1, 1)).  Shared by
+    tests/test_edge_geometry_gpu.py and the CPU checks of tests/test_edge_geometry_host.py.  rows x cols, w, and what each one is for:
+      one        1 x 1, w 1       one 1 x 1 block: every tile, panel and slab is almost all padding
+      rowvec     1 x 300, w 32    one block-row of height 1 holding all 10 block columns, the last one ragged (12 real columns)
+      colvec     300 x 1, w 3     cols < w; heights 7 with a ragged last block-row of 6; every third block-row without a block
+      narrow32   100 x 20, w 32   cols < w at an MFMA panel width (the only block column is the ragged one); heights 25
+      empty      130 x 200, w 32  16-row block-rows (last one 2), nzcount all 0, nztot 0, jab and mab empty: every work list of the handle is empty
+      corner     130 x 200, w 32  as empty, with ONE block in the last (2-row) block-row, in the last (ragged, 8-column) block column
+      zeros      96 x 160, w 32   heights 24; blocks at about half the positions; every value of every second stored block is 0.0
+      tall       322 x 96, w 32   two block-rows, heights 257 and 65 (more than four 64-row tiles), each holding all three block columns
+      heights    391 x 112, w 16  heights EDGE_HEIGHTS: zero heights first, in the middle and last; about half the blocks present; the block-rows of
+                                  height 1 and 64 hold no block
+      dense      96 x 128, w 64   heights 48; every block present, every value non-zero
+      w1         70 x 70, w 1     heights 1, 5, 64; about 10 % of the 1-wide blocks present
+      corner64   130 x 200, w 64  corner at the width of the per-class kernels (w % 64 == 0): eight block-rows without a block next to one block, which is ragged
+      heights64  391 x 112, w 64  fp32: the height list of heights at the width of the per-class kernels; the second block column is ragged (48 real columns)
+      heights32  391 x 112, w 32  16-bit: the height list of heights; the last block column is ragged (16 real columns)
+      tall64     322 x 192, w 64  16-bit: tall at w 64: 64-row tiles of 64-wide blocks (pair / hub plan candidates)"""
+    if values not in _edge:
+        seed0 = {"int": 7100, "real": 7200}[values]
+        rng = np.random.default_rng(20261018)                     # the patterns: the same for both value sets
+
+        def half(n_brows, n_bcols, empty=()):
+            out = []
+            for ib in range(n_brows):
+                p = [j for j in range(n_bcols) if rng.random() < 0.5] or [int(rng.integers(n_bcols))]
+                out.append([] if ib in empty else p)
+            return out
+
+        hts = list(EDGE_HEIGHTS)
+        no_block = [i for i, h in enumerate(hts) if h in (0, 1, 64)]
+        h16_pat, h32_pat = half(16, 7, no_block), half(16, 4, no_block)
+        zeros_pat = half(4, 5)
+        w1_pat = [sorted(rng.choice(70, 7, replace=False).tolist()) for _ in range(3)]
+        arrs = {
+            "one": _edge_arrays(1, 1, 1, [1], [[0]]),
+            "rowvec": _edge_arrays(1, 300, 32, [1], [list(range(10))]),
+            "colvec": _edge_arrays(300, 1, 3, [7] * 42 + [6], [[] if ib % 3 == 2 else [0] for ib in range(43)]),
+            "narrow32": _edge_arrays(100, 20, 32, [25] * 4, [[0]] * 4),
+            "empty": _edge_arrays(130, 200, 32, [16] * 8 + [2], [[]] * 9),
+            "corner": _edge_arrays(130, 200, 32, [16] * 8 + [2], [[]] * 8 + [[6]]),
+            "zeros": _edge_arrays(96, 160, 32, [24] * 4, zeros_pat),
+            "tall": _edge_arrays(322, 96, 32, [257, 65], [[0, 1, 2]] * 2),
+            "heights": _edge_arrays(391, 112, 16, hts, h16_pat),
+            "dense": _edge_arrays(96, 128, 64, [48, 48], [[0, 1]] * 2),
+            "w1": _edge_arrays(70, 70, 1, [1, 5, 64], w1_pat),
+            "heights32": _edge_arrays(391, 112, 32, hts, h32_pat),
+            "tall64": _edge_arrays(322, 192, 64, [257, 65], [[0, 1, 2]] * 2),
+            "corner64": _edge_arrays(130, 200, 64, [16] * 8 + [2], [[]] * 8 + [[3]]),
+            "heights64": _edge_arrays(391, 112, 64, hts, half(16, 2, no_block)),
+        }
+        out = {}
+        for i, (k, a) in enumerate(arrs.items()):
+            n_blocks = int(a[4].sum())
+            out[k] = sa_vbr(a, _edge_values(a, values, seed0 + i, zero_blocks=range(0, n_blocks, 2) if k == "zeros" else ()))
+        _edge[values] = out
+    return _edge[values]
+
+
+def edge_round(x, dtype):
+    """x as the storage type of a handle holds it, in float64: dtype 0 fp32, 1 fp16, 2 bf16 (round to nearest even), by numpy alone"""
+    f = np.ascontiguousarray(x, np.float32)
+    if dtype == 1:
+        return f.astype(np.float16).astype(np.float64)
+    if dtype == 2:
+        u = f.view(np.uint32).astype(np.uint64)
+        u = ((u + 0x7fff + ((u >> 16) & 1)) & 0xffff0000).astype(np.uint32)
+        return u.view(np.float32).astype(np.float64).reshape(f.shape)
+    return f.astype(np.float64)
+
+
+def edge_dense(v, dtype=0, mab=None, br=None):
+    """the float64 (rows of the block-rows br) x cols matrix of the stored blocks, expanded from the arrays: element i of stored column q of a block is
+    mab[off + q * h + i] (mab: the whole matrix's values or the range's); the positions of a ragged last block column past cols are dropped; values rounded to the handle's storage type first"""
+    mab = edge_round(v.mab if mab is None else mab, dtype)
+    b0, b1 = (0, v.block_rows) if br is None else br
+    if len(mab) == len(v.mab):                                       # the whole matrix's values: take the range's
+        mab = mab[slice(*edge_mab_slice(v, (b0, b1)))]
+    D = np.zeros((int(v.row_part[b1] - v.row_part[b0]), v.cols))
+    for off, r0, h, c0, valid in edge_blocks(v, br):
+        D[r0:r0 + h, c0:c0 + valid] = mab[off:off + valid * h].reshape(valid, h).T
+    return D
+
+
+def edge_sample(v, M, br=None):
+    """the rows x cols matrix M sampled back into the mab layout of the block-rows br (include/sparta_amd.h: G[off + q * h + i] = M[r0 + i, jb * w + q]);
+    the positions past cols are 0"""
+    w = int(v.block_col_size)
+    blocks = edge_blocks(v, br)
+    G = np.zeros(sum(h * w for _, _, h, _, _ in blocks))
+    for off, r0, h, c0, valid in blocks:
+        G[off:off + valid * h] = M[r0:r0 + h, c0:c0 + valid].T.reshape(-1)
+    return G
+
+
+def spmm_t_host_check(v, x, br=None):
+    """y = A^T x by the host walk of the block-column index that sparta_vbs_create builds for sparta_vbs_spmm_t (sparta_spmm_t_host_check): (y, info)"""
+    import ctypes as C
+    from sparta_amd import _lib
+    i64p, f32p = C.POINTER(C.c_int64), C.POINTER(C.c_float)
+    b0, b1 = (0, v.block_rows) if br is None else br
+    rp, nz, jab = (np.ascontiguousarray(a, np.int64) for a in (v.row_part, v.nzcount, v.jab))
+    mab, x = np.ascontiguousarray(v.mab, np.float32), np.ascontiguousarray(x, np.float32)
+    y, info = np.full(v.cols, np.nan, np.float64), np.full(8, -1, np.int64)
+    _lib.check(_lib.lib.sparta_spmm_t_host_check(v.rows, v.cols, v.block_rows, v.block_col_size, rp.ctypes.data_as(i64p), nz.ctypes.data_as(i64p), jab.ctypes.data_as(i64p),
+                                                 mab.ctypes.data_as(f32p), b0, b1, x.ctypes.data_as(f32p), y.ctypes.data_as(C.POINTER(C.c_double)), info.ctypes.data_as(i64p)))
+    return y, info
