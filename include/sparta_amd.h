@@ -320,7 +320,24 @@ int sparta_vbs_plan_stats(int64_t rows, int64_t cols, const int64_t* rowptr, con
  * streams at once.  The FIRST call of a shape (n_cols, layouts, shard_rows) on a handle may allocate that scratch, and on fp32 handles
  * times its two product paths once; every later call of the shape is kernel launches only and can be captured into a hipGraph.  A call
  * that would have to allocate or time while its stream is being captured returns SPARTA_ERR_UNSUPPORTED (and leaves the capture
- * intact): run it once outside the capture first. */
+ * intact): run it once outside the capture first.
+ *
+ * WHAT AN OUTPUT ELEMENT DEPENDS ON (non-finite operands included: Inf and NaN are ordinary data, and 0 * Inf is NaN, so "multiplied by a zero"
+ * is not "not read"; tests/test_poison_gpu.py).
+ *   Forward products (sparta_vbs_spmm, _gathered, _gathered_ld, _prepared, SPARTA_SPMM_EXACT, sparta_vbs_spmm_ba on B^T): C[i, j] depends only on
+ *   column j of B, and there only on the rows k that lie inside a block column which the block-row of row i stores -- for a handle from
+ *   sparta_vbs_create_from_csr: a block column of the grouping's w-grid in which the block-row has a nonzero.  Stored positions past `cols`, the padding
+ *   of a leading dimension and the gap between two slabs of a gathered B take no part.  However a planner groups block-rows into tiles (pair tiles, hub
+ *   group tiles, union tiles), a block column that only a neighbour in the tile stores does not reach the rows of this block-row: a NaN in one row of B
+ *   makes non-finite exactly the rows of C whose block-rows store that row's block column.
+ *   Stored zeros: whether a stored 0.0 of A times a non-finite element of B gives NaN (the reference's VBR::multiply, the MFMA tiles) or is skipped (the
+ *   sparse-row kernels, the fp32 k-compaction, create_from_csr dropping zeros) is NOT specified: such an element of C may be either.
+ *   sparta_vbs_spmm_t: Ct[c, j] depends only on column j of X, and there only on the rows of the block-rows that store the block column of c.
+ *   sparta_vbs_sddmm: the values of G in block (ib, jb) depend only on X's rows of block-row ib and Y's rows of block column jb (G[off + q * h + i]: row i
+ *   of the block-row, row jb * w + q of Y), and with accumulate = 1 on their own previous value.
+ *   sparta_vbs_set_values: a non-finite value in a stored block reaches only rows of C of that block's block-row (and, through spmm_t, rows of Ct of its
+ *   block column); the next set_values replaces it completely.
+ *   Overwriting calls (accumulate = 0) do not depend on the previous content of the output, NaN included. */
 int sparta_vbs_spmm(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int32_t n_cols,
                     void* C, int64_t ldc, int32_t c_layout, int32_t accumulate,
                     int32_t ptr_space, void* stream, int32_t algo, float* dt_ms);

@@ -137,14 +137,19 @@ __global__ __launch_bounds__(kThreads, 2) void vbs_spmm_h16_stream_kernel(const 
         TL_STAMP(1);
         fq_new = issue_loads(i + AHEAD, wb, wa);
         TL_STAMP(2);
+        // pair tiles (vbs_plan.cpp): the half whose block-row has no block in this step's column is zeros in the slice; it must not meet the panel of B either
+        // (0 x Inf = NaN): its B fragment is ANDed with a wave-uniform 0, see vbs_spmm_h16_direct_kernel
+        const uint32_t m_lo = (MI2 && (flags & STEP_LO_ABSENT)) ? 0u : ~0u, m_hi = (MI2 && (flags & STEP_HI_ABSENT)) ? 0u : ~0u;
 #pragma unroll
         for (int kb = 0; kb < KP; kb += 16) {
             const u32x4 bf = *reinterpret_cast<const u32x4*>(ldsb + lrB + (PAR * STAGE + kb) * 2);
             const u32x4 af0 = *reinterpret_cast<const u32x4*>(ldsb + lrA + (PAR * STAGE + kb) * 2);
-            mfma(bf, af0, acc0);
             if constexpr (MI2) {
                 const u32x4 af1 = *reinterpret_cast<const u32x4*>(ldsb + lrA + (PAR * STAGE + 32 * LDK + kb) * 2);
-                mfma(bf, af1, acc1);
+                mfma(u32x4{bf[0] & m_lo, bf[1] & m_lo, bf[2] & m_lo, bf[3] & m_lo}, af0, acc0);
+                mfma(u32x4{bf[0] & m_hi, bf[1] & m_hi, bf[2] & m_hi, bf[3] & m_hi}, af1, acc1);
+            } else {
+                mfma(bf, af0, acc0);
             }
         }
         TL_STAMP(3);
@@ -444,7 +449,8 @@ __global__ __launch_bounds__(kThreads, (MI2 && WC == 64) ? 1 : 2) void vbs_spmm_
 #pragma unroll
                 for (int q = 0; q < NK; q++) rb.b[c * NK + q] = __builtin_amdgcn_raw_buffer_load_b128(rB, vo_cur, gs * c + qs * q, 0);
         }
-        // (pair tiles, vbs_plan.cpp: a half of the slice whose block-row has no block in this column is zeros -- a descriptor of zero records returns them without a fetch)
+        // (pair tiles, vbs_plan.cpp: a half of the slice whose block-row has no block in this column is zeros -- a descriptor of zero records returns them without a fetch;
+        // the step then clears the B fragments of that half as well, see `half` below)
         const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(A16 + g_aoff), 0, (MI2 && (flags & STEP_LO_ABSENT)) ? 0 : 0x7ffffff0, 0x00020000);
         const __amdgpu_buffer_rsrc_t rA1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(A16 + g_aoff), 0, (MI2 && (flags & STEP_HI_ABSENT)) ? 0 : 0x7ffffff0, 0x00020000);
         if (!(SPARTA_H16_PROBE & 2) && !((SPARTA_H16_PROBE & 16) && wave != 0) && !((SPARTA_H16_PROBE & 32) && (wave & 1))) {   // 16: only wave 0 loads A; 32: waves 0 and 2
@@ -503,13 +509,22 @@ __global__ __launch_bounds__(kThreads, (MI2 && WC == 64) ? 1 : 2) void vbs_spmm_
             if constexpr (!(SPARTA_H16_ILV && MI2 && !DEEP && !TAIL)) write_b(std::integral_constant<int, 1 - PAR>{}, wb);         // W(i + 1)  (two-tile instantiations: between the MFMAs, below)
         }
         constexpr bool ILV = SPARTA_H16_ILV && MI2 && !DEEP && !TAIL && !(SPARTA_H16_PROBE & 8);
+        // pair tiles: the half whose block-row has no block in this step's column must not see the panel of B at all.  Its slice of A is zeros, but 0 x Inf and
+        // 0 x NaN are NaN: an element of C depends only on the rows of B in block columns that ITS block-row stores (include/sparta_amd.h).  The flags are wave-uniform:
+        // the fragments that feed the absent half are ANDed with a scalar 0 (with ~0 otherwise), which clears a NaN as well; no branch around the MFMAs.
+        const uint32_t m_lo = (MI2 && (flags & STEP_LO_ABSENT)) ? 0u : ~0u, m_hi = (MI2 && (flags & STEP_HI_ABSENT)) ? 0u : ~0u;
+        auto half = [&](const u32x4& f, int mi) __attribute__((always_inline)) -> u32x4 {
+            if constexpr (!MI2) return f;
+            const uint32_t m = mi == 0 ? m_lo : m_hi;
+            return u32x4{f[0] & m, f[1] & m, f[2] & m, f[3] & m};
+        };
         if constexpr (!ILV) {
 #pragma unroll
             for (int q = 0; q < NK; q++) {
-                mfma(fb[q], wa.a[0][q], acc0);
-                if constexpr (MI2) mfma(fb[q], wa.a[1][q], acc1);
+                mfma(half(fb[q], 0), wa.a[0][q], acc0);
+                if constexpr (MI2) mfma(half(fb[q], 1), wa.a[1][q], acc1);
                 if constexpr (WC == 64 && !MI2) mfma(fb[NK + q], wa.a[0][q], acc1);   // the wave's second 32 columns (acc1: free in the one-tile kernel)
-                if constexpr (QUAD) { mfma(fb[NK + q], wa.a[0][q], acc2); mfma(fb[NK + q], wa.a[1][q], acc3); }
+                if constexpr (QUAD) { mfma(half(fb[NK + q], 0), wa.a[0][q], acc2); mfma(half(fb[NK + q], 1), wa.a[1][q], acc3); }
             }
             fq_new = issue_loads(std::integral_constant<int, i + D>{}, nb, na);   // G(i + D)
         } else {
@@ -532,7 +547,7 @@ __global__ __launch_bounds__(kThreads, (MI2 && WC == 64) ? 1 : 2) void vbs_spmm_
                 constexpr int t = decltype(t_tag)::value;
                 constexpr int q = t / (NA * NG), c = (t / NA) % NG, mi = t % NA;       // k group, column group, row half
                 f32x16& acc = (c == 0) ? (mi == 0 ? acc0 : acc1) : (mi == 0 ? acc2 : acc3);
-                mfma(fb[c * NK + q], wa.a[mi][q], acc);
+                mfma(half(fb[c * NK + q], mi), wa.a[mi][q], acc);
                 __builtin_amdgcn_sched_barrier(0);
                 // what goes behind MFMA t: first the NW writes of W(i + 1), then the loads of step i + D spread over the remaining MFMAs
                 constexpr int slots = NM;

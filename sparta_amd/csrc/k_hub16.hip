@@ -15,7 +15,8 @@
 //   * one barrier per step: wait (counted vmcnt) for this wave's loads of step i, barrier, issue the loads of step i + NS - 1 into the stage that
 //     step i - 1 has just left, multiply step i.  The loads of NS - 2 steps stay in flight across every barrier;
 //   * a sub-tile that has no block in a step's block column (flags bits 0..1) is not fetched: a descriptor of zero records, the LDS-direct load then writes
-//     zeros without touching memory (checked on the hardware: scripts/ubench/glds_probe.hip) and its two waves multiply zeros;
+//     zeros without touching memory (checked on the hardware: scripts/ubench/glds_probe.hip) and its two waves multiply zeros by zeros (they read
+//     their B fragments from that zero slice too: a non-finite value in the panel must not reach a block-row that does not store the column);
 //   * tile ends: the 2 x 4 accumulators go to C (same lane -> element map and store forms as k_h16.hip) or, for a tile shared with other workers, into
 //     the workspace images of its two sub-tiles and two 128-column slabs, in the layout vbs_spmm_f32_fixup_kernel reads.
 // Step records come through SCALAR loads (one s_load_dwordx8 per step, requested one step before the step's loads are issued): a step here is 32 MFMAs per wave
@@ -227,9 +228,13 @@ __global__ __launch_bounds__(64 * 2 * G * (LW ? 2 : 1), (G / 2) * (LW ? 2 : 1) *
         if constexpr (!LW) prepare(rec, jstage);
         const int32_t flags = fq[0];
         // (a sub-tile without a block in this column multiplies the zeros its loads wrote: no branch around the MFMAs -- a join there makes the register allocator
-        // keep a second home for the accumulators and copy all 128 registers into and out of it every step)
+        // keep a second home for the accumulators and copy all 128 registers into and out of it every step.  Zeros on BOTH sides: 0 x Inf and 0 x NaN are NaN, and
+        // an element of C depends only on the rows of B in block columns that its own block-row stores (include/sparta_amd.h).  So the waves of such a sub-tile read
+        // their B fragments from their own slice of A, the 64 rows of zeros in LDS, instead of the panel: a wave-uniform choice of two base addresses.)
         if (!(SPARTA_HUB_PROBE & 4)) {
             const uint32_t sa = (uint32_t)(stage * STAGE + wr * SLICE), sb = (uint32_t)(stage * STAGE + A_BYTES + 128 * wc * RB);
+            const bool here = ((flags >> wr) & 1) != 0;
+            const uint32_t sb01 = here ? sb : sa, sb23 = here ? sb + 64 * RB : sa;       // column groups 0, 1 and 2, 3 of the wave's 128 (absent: the two 32-row halves of the zero slice, twice)
             u32x4 af[NKG][2], bf[NKG][4];
             auto read_frags = [&](auto kg_tag) __attribute__((always_inline)) {
                 constexpr int kg = decltype(kg_tag)::value;
@@ -243,7 +248,7 @@ __global__ __launch_bounds__(64 * 2 * G * (LW ? 2 : 1), (G / 2) * (LW ? 2 : 1) *
 #pragma unroll
                     for (int rt = 0; rt < 2; rt++) af[kg][rt] = *reinterpret_cast<const u32x4*>(lds0 + (sa + fr) + rt * 32 * RB);
 #pragma unroll
-                    for (int ct = 0; ct < 4; ct++) bf[kg][ct] = *reinterpret_cast<const u32x4*>(lds0 + (sb + fr) + ct * 32 * RB);
+                    for (int ct = 0; ct < 4; ct++) bf[kg][ct] = *reinterpret_cast<const u32x4*>(lds0 + ((ct < 2 ? sb01 : sb23) + fr) + (ct & 1) * 32 * RB);
                 }
             };
             read_frags(std::integral_constant<int, 0>{});

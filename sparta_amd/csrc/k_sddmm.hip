@@ -33,25 +33,32 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
-// the 32 x 32 accumulator -> G: lane (i = lane & 31, g = lane >> 5), register r: stored column q0 + (r & 3) + 8 (r >> 2) + 4 g, row i
-__device__ __forceinline__ void sd_store(const f32x16& acc, float* G, int64_t base, int64_t q0, int64_t nq, int h, int mt, int lane, int accumulate) {
-    const int i = lane & 31;
-    if (i >= mt) return;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int64_t q = q0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (q >= nq) continue;
-        float* dst = G + base + q * h + i;
-        *dst = accumulate ? *dst + acc[r] : acc[r];
-    }
-}
-
 // the stored column of lane (lane & 31) in group gi of the item: its column of Y, or -1 (past the block-row's stored columns, or ragged)
 __device__ __forceinline__ int64_t sd_column(const SddmmParams& p, const BlockRowDesc& br, int64_t nq, int64_t q) {
     if (q >= nq) return -1;
     const int64_t b = q / p.w, c = q - b * p.w;
     const int64_t col = (int64_t)p.jab[br.jab_off + b] * p.w + c;
     return col < p.cols ? col : -1;
+}
+
+// the 32 x 32 accumulator -> G: lane (i = lane & 31, g = lane >> 5), register r: stored column q0 + (r & 3) + 8 (r >> 2) + 4 g, row i.  A stored position past
+// cols (ragged last block column) gets 0 whatever X holds: its accumulator is X times the zeros that stand in for a row of Y that does not exist, and
+// Inf x 0 is NaN (include/sparta_amd.h: such a position depends on nothing)
+__device__ __forceinline__ void sd_store(const SddmmParams& p, const BlockRowDesc& br, const f32x16& acc, float* G, int64_t base, int64_t q0, int64_t nq, int h, int mt,
+                                         int lane, int accumulate) {
+    const int i = lane & 31;
+    // bit j: stored position q0 + j is a column of the matrix -- looked up once per group of 32 positions (lane j), not once per stored element
+    const unsigned long long live = __ballot(sd_column(p, br, nq, q0 + i) >= 0);
+    if (i >= mt) return;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int j = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int64_t q = q0 + j;
+        if (q >= nq) continue;
+        float* dst = G + base + q * h + i;
+        const float v = (live >> j) & 1 ? acc[r] : 0.0f;
+        *dst = accumulate ? *dst + v : v;
+    }
 }
 
 __global__ __launch_bounds__(kThreads) void vbs_sddmm_f32_kernel(const SddmmParams p) {
@@ -103,7 +110,7 @@ __global__ __launch_bounds__(kThreads) void vbs_sddmm_f32_kernel(const SddmmPara
 #pragma unroll
     for (int t = 0; t < kSdGpw; t++) {
         if (wv + kSdWaves * t >= it.ng) break;
-        sd_store(acc[t], p.G, base, (int64_t)(it.g0 + wv + kSdWaves * t) * 32, nq, br.h, mt, lane, p.accumulate);
+        sd_store(p, br, acc[t], p.G, base, (int64_t)(it.g0 + wv + kSdWaves * t) * 32, nq, br.h, mt, lane, p.accumulate);
     }
 }
 
@@ -199,7 +206,7 @@ __global__ __launch_bounds__(kThreads) void vbs_sddmm_h16_kernel(const SddmmPara
 #pragma unroll
     for (int t = 0; t < kSdGpw; t++) {
         if (wv + kSdWaves * t >= it.ng) break;
-        sd_store(acc[t], p.G, base, (int64_t)(it.g0 + wv + kSdWaves * t) * 32, nq, br.h, mt, lane, p.accumulate);
+        sd_store(p, br, acc[t], p.G, base, (int64_t)(it.g0 + wv + kSdWaves * t) * 32, nq, br.h, mt, lane, p.accumulate);
     }
 }
 

@@ -291,3 +291,206 @@ def spmm_t_host_check(v, x, br=None):
     _lib.check(_lib.lib.sparta_spmm_t_host_check(v.rows, v.cols, v.block_rows, v.block_col_size, rp.ctypes.data_as(i64p), nz.ctypes.data_as(i64p), jab.ctypes.data_as(i64p),
                                                  mab.ctypes.data_as(f32p), b0, b1, x.ctypes.data_as(f32p), y.ctypes.data_as(C.POINTER(C.c_double)), info.ctypes.data_as(i64p)))
     return y, info
+
+
+# ---- poison geometries: which operands does an output element depend on? ------------------------------------------------------------------------------------
+POISON_F32 = ("P32", "P64", "P13")
+POISON_H16 = ("P32", "P64")                         # 16-bit handles need w % 32 == 0
+POISON_HEIGHTS = {"P32": [32, 32, 32, 20, 32, 32, 64, 7], "P64": [48, 48, 64, 33, 64, 64, 40, 64], "P13": [16, 5, 32, 1, 19, 64, 16, 33]}
+POISON_COLS = {"P32": 8 * 32 - 11, "P64": 8 * 64 - 20, "P13": 8 * 13 - 4}
+POISON_W = {"P32": 32, "P64": 64, "P13": 13}
+PCSR_THIN = (3, 15)                                 # the block columns (w 32) that every third block-row of PCSR, PUNI and PSPLIT does not store
+POISON_GATHERED = {"P32G": "P32", "P64G": "P64"}    # the siblings of P32 / P64 for a gathered B, which has cols = n_shards * shard_rows: the same blocks, cols = 8 w
+_poison = None
+
+
+def poison_present(ib):
+    """the block columns block-row ib of P32 / P64 / P13 stores: all of 0..7 except ib and (ib + 3) % 8 -- no two block-rows store the same set"""
+    return [j for j in range(8) if j not in (ib, (ib + 3) % 8)]
+
+
+def poison_csr():
+    """PCSR: (CSR 512 x 512, grouping rows // 16, w 32).  Per row: with probability 0.85 each one nonzero in block column 3 and one in block column 15 (the
+    columns the poison goes to: a row that stores such a block column then usually has a nonzero in it, which keeps the `open` elements of the reference few),
+    four more anywhere, every 37th row 40 more (rows long enough for the window plan); then every nonzero of block columns 3 and 15 is removed from every third
+    block-row (ib % 3 == 1).  Values: seeded uniform(-1, 1), none 0."""
+    import sparta_amd as sa
+    rng = np.random.default_rng(20261019)
+    rows = cols = 512
+    rr, cc = [], []
+    for i in range(rows):
+        c = [rng.integers(0, cols, 4 + (40 if i % 37 == 5 else 0))]
+        for bc in PCSR_THIN:
+            if rng.random() < 0.85:
+                c.append(bc * 32 + rng.integers(0, 32, 1))
+        c = np.unique(np.concatenate(c))
+        if (i // 16) % 3 == 1:
+            c = c[~np.isin(c // 32, PCSR_THIN)]
+        rr.append(np.full(len(c), i)); cc.append(c)
+    r, c = np.concatenate(rr), np.concatenate(cc)
+    vals = rng.uniform(-1, 1, len(c)).astype(np.float32)
+    vals[vals == 0] = 0.5
+    m = sa.CSR(rows, cols, np.concatenate([[0], np.cumsum(np.bincount(r, minlength=rows))]).astype(np.int64), c.astype(np.int32), vals)
+    return m, np.arange(rows, dtype=np.int64) // 16, 32
+
+
+def _thin(rows_of_groups, r, c, w):
+    """drop every nonzero (r, c) of the block columns PCSR_THIN from every third group (index % 3 == 1); rows_of_groups: per group, its rows"""
+    drop = np.zeros(len(r), bool)
+    for gi, rows in enumerate(rows_of_groups):
+        if gi % 3 == 1:
+            drop |= np.isin(r, rows) & np.isin(c // w, PCSR_THIN)
+    return r[~drop], c[~drop]
+
+
+def _csr_of(rows, cols, r, c, seed):
+    """the CSR of the positions (r, c) with seeded non-zero uniform(-1, 1) values"""
+    import sparta_amd as sa
+    o = np.lexsort((c, r))
+    r, c = r[o], c[o]
+    vals = np.random.default_rng(seed).uniform(-1, 1, len(c)).astype(np.float32)
+    vals[vals == 0] = 0.5
+    return sa.CSR(rows, cols, np.concatenate([[0], np.cumsum(np.bincount(r, minlength=rows))]).astype(np.int64), c.astype(np.int32), vals)
+
+
+PUNI_SHAPE = (9, 48, 1024, 100, 3)                  # clustered(n_groups, rows_per, cols, shared, own): 432 x 1024, 32 block columns of width 32
+
+
+def poison_union():
+    """PUNI: (CSR, grouping, w 32) from the clustered generator of tests/test_union_host.py (the one tests/test_union_gpu.py uses) at a size that still gives one
+    column-compacted tile per cluster: rows of a cluster (scattered over the matrix) share ~80 of 100 columns, about three per block column, so a row of a
+    cluster that stores a block column nearly always has a nonzero in it; then every nonzero of the block columns PCSR_THIN is removed from every third cluster (every third block-row of the handle)."""
+    from test_union_host import clustered, true_grouping
+    ng, rp, cols, shared, own = PUNI_SHAPE
+    m, order = clustered(ng, rp, cols, shared, own, seed=20261021)
+    r = np.repeat(np.arange(m.rows), np.diff(m.rowptr))
+    groups = sorted((order[gi * rp:(gi + 1) * rp] for gi in range(ng)), key=lambda rows: rows.min())          # in the order of the handle's block-rows (group id = smallest row)
+    r, c = _thin(groups, r, np.asarray(m.colidx, np.int64), 32)
+    return _csr_of(m.rows, cols, r, c, 20261022), true_grouping(order, rp), 32
+
+
+def poison_split():
+    """PSPLIT: (CSR 256 x 512, grouping rows // 32, w 32) whose block-rows sparta_vbs_create_from_csr splits into tiles and sparse rows: per row 20 of the 32
+    columns of each of the block columns 3, 9 and 15 (well-filled blocks: tiles) and two nonzeros anywhere else (thin blocks: sparse rows that add); then
+    every nonzero of the block columns PCSR_THIN is removed from every third block-row, which keeps its tile of block column 9 -- a 16-bit pair tile of such a
+    block-row and its neighbour has an absent half in the block columns the poison goes to."""
+    rng = np.random.default_rng(20261023)
+    rows, cols, w = 256, 512, 32
+    rr, cc = [], []
+    for i in range(rows):
+        c = np.unique(np.concatenate([bc * w + rng.choice(w, 20, replace=False) for bc in (3, 9, 15)] + [rng.integers(0, cols, 2)]))
+        rr.append(np.full(len(c), i)); cc.append(c)
+    r, c = _thin([np.arange(32 * gi, 32 * gi + 32) for gi in range(rows // 32)], np.concatenate(rr), np.concatenate(cc), w)
+    return _csr_of(rows, cols, r, c, 20261024), np.arange(rows, dtype=np.int64) // 32, w
+
+
+def poison_geometries():
+    """key -> VBR made with VBR.from_arrays from index arrays written out here: 8 block-rows x 8 block columns, block-row ib stores poison_present(ib); every
+    stored value is a seeded non-zero uniform(-1, 1) (the positions past cols too: they take no part in any product).  Shared by tests/test_poison_gpu.py and
+    tests/test_poison_host.py.
+      P32   w 32, heights 32 32 32 20 32 32 64 7 (16-bit: the pair plan takes (0, 1), (2, 3), (4, 5)), cols 8 * 32 - 11
+      P64   w 64, heights 48 48 64 33 64 64 40 64 (16-bit: candidates of the hub plan), cols 8 * 64 - 20
+      P13   w 13, heights 16 5 32 1 19 64 16 33, cols 8 * 13 - 4 (fp32 only)
+      P32G, P64G   the blocks of P32 / P64 with cols = 8 w: a gathered B is n_shards slabs of cols / n_shards rows, which a ragged cols does not allow"""
+    global _poison
+    if _poison is None:
+        _poison = {}
+        for i, k in enumerate(POISON_F32):
+            hts = POISON_HEIGHTS[k]
+            a = _edge_arrays(sum(hts), POISON_COLS[k], POISON_W[k], hts, [poison_present(ib) for ib in range(8)])
+            _poison[k] = sa_vbr(a, _edge_values(a, "real", 7300 + i))
+        for i, (k, of) in enumerate(POISON_GATHERED.items()):
+            hts = POISON_HEIGHTS[of]
+            a = _edge_arrays(sum(hts), 8 * POISON_W[of], POISON_W[of], hts, [poison_present(ib) for ib in range(8)])
+            _poison[k] = sa_vbr(a, _edge_values(a, "real", 7310 + i))
+    return _poison
+
+
+def stored_mask(v, br=None):
+    """bool (rows of the block-rows br) x cols: the positions inside a stored block"""
+    return edge_dense(v, mab=np.ones(len(v.mab), np.float32), br=br) != 0
+
+
+def csr_dense_and_stored(m, g, w):
+    """(D float64 rows x cols, stored bool) of a CSR under grouping g (groups ascending with the rows) on the w-grid, rows in the order of the handle that
+    sparta_vbs_create_from_csr makes (the grouping's permutation): a block column is stored by a block-row (a group) when one of the group's rows has a nonzero in it"""
+    D = np.zeros((m.rows, m.cols))
+    r = np.repeat(np.arange(m.rows), np.diff(m.rowptr))
+    D[r, m.colidx] = m.vals
+    nbc = (m.cols + w - 1) // w
+    has = np.zeros((int(g.max()) + 1, nbc), bool)
+    has[g[r], m.colidx // w] = True
+    stored = np.repeat(has[g], w, axis=1)[:, :m.cols]
+    import sparta_amd as sa
+    perm = np.asarray(sa.get_permutation(g), np.int64)          # row r of the handle (and of C) is row perm[r] of the CSR: the rows of a group together, groups by their id
+    assert (np.diff(g[perm]) >= 0).all()
+    return D[perm], stored[perm]
+
+
+def poison_reference(D, stored, B):
+    """float64 reference of D @ B under the dependency contract of include/sparta_amd.h, for a B that holds non-finite elements (the poison).  D: dense
+    r x c (already rounded to the handle's storage type), stored: bool r x c, the positions inside stored blocks, B: c x n float64.  Row i of the product is
+    D[i, stored[i]] @ B[stored[i]] (computed for all rows of one stored pattern at once): the rows of B outside the block columns that the row's block-row stores are not read (a dense D @ B would multiply them by
+    0).  Returns (product, clean, dirty, open): clean -- no poisoned element of B lies in a stored block column of the row, in this column of B: the element
+    must equal the unpoisoned product; dirty -- a non-zero of D meets a poisoned element: must be non-finite; open -- only stored zeros of A meet poison."""
+    bad = ~np.isfinite(B)
+    want = np.zeros((D.shape[0], B.shape[1]))
+    with np.errstate(all="ignore"):
+        pats, which = np.unique(stored, axis=0, return_inverse=True)            # rows of one block-row share their pattern: one product per pattern
+        for q, s in enumerate(pats):
+            rows = np.flatnonzero(which.reshape(-1) == q)
+            want[rows] = D[np.ix_(rows, np.flatnonzero(s))] @ B[s]
+    may = (stored.astype(np.float64) @ bad.astype(np.float64)) > 0
+    dirty = ((D != 0).astype(np.float64) @ bad.astype(np.float64)) > 0
+    assert not (dirty & ~may).any()
+    return want, ~may, dirty, may & ~dirty
+
+
+def poison_reference_t(D, stored, X):
+    """the same for Ct = A^T X (sparta_vbs_spmm_t): row c of Ct reads the rows of X of the block-rows that store the block column of c"""
+    return poison_reference(np.ascontiguousarray(D.T), np.ascontiguousarray(stored.T), X)
+
+
+def poison_reference_sddmm(v, X, Y, br=None):
+    """G = (X Y^T) sampled on the stored blocks, in the mab layout, float64: (G, clean, dirty).  G[i, c] reads row i of X and row c of Y and nothing else, so
+    an element is dirty when one of the two rows holds poison (whatever the other row holds: a * Inf and 0 * Inf are both non-finite) and clean otherwise;
+    the positions past cols are 0 and clean."""
+    with np.errstate(all="ignore"):
+        M = X @ Y.T
+    bad = np.logical_or.outer(~np.isfinite(X).all(axis=1), ~np.isfinite(Y).all(axis=1))
+    G = edge_sample(v, np.where(bad, 0.0, M), br)
+    dirty = edge_sample(v, bad.astype(np.float64), br) != 0
+    G[dirty] = edge_sample(v, np.where(bad, M, 0.0), br)[dirty]
+    return G, ~dirty, dirty
+
+
+POISON_VALUES = {"+inf": (np.inf,), "-inf": (-np.inf,), "nan": (np.nan,), "mix": (np.inf, np.nan, -np.inf), "1e5": (1.0e5,)}          # 1e5: finite in fp32 and bf16, Inf once rounded to fp16
+
+
+def poisoned(M, rows, kind, col=None):
+    """a copy of M (float64) with the poison `kind` in the rows `rows` (a slice or an index array): in every column, or in column `col` alone; 'mix' gives
+    consecutive rows +Inf, NaN, -Inf in turn; '1e5' is stored as Inf (what the conversion to fp16 makes of it: the caller hands the device 1e5)"""
+    M = M.copy()
+    idx = np.arange(M.shape[0])[rows]
+    vals = np.array([np.inf if x == 1.0e5 else x for x in POISON_VALUES[kind]])
+    fill = vals[np.arange(len(idx)) % len(vals)]
+    if col is None:
+        M[idx, :] = fill[:, None]
+    else:
+        M[idx, col] = fill
+    return M
+
+
+def block_col_rows(v, c):
+    """the rows of B (columns of A) of block column c, inside the matrix"""
+    w = int(v.block_col_size)
+    return slice(c * w, min((c + 1) * w, v.cols))
+
+
+def block_row_rows(v, r, br=None):
+    """the rows of block-row r, counted from the start of the range br"""
+    b0 = 0 if br is None else br[0]
+    return slice(int(v.row_part[r] - v.row_part[b0]), int(v.row_part[r + 1] - v.row_part[b0]))
+
+
+POISON_B_PLACEMENTS = [(c, j) for c in (1, 7) for j in (None, 0, 37, -1)]          # (block column c*, column j* of B: None = all of them, -1 = the last)
