@@ -247,11 +247,15 @@ def edge_round(x, dtype):
     """x as the storage type of a handle holds it, in float64: dtype 0 fp32, 1 fp16, 2 bf16 (round to nearest even), by numpy alone"""
     f = np.ascontiguousarray(x, np.float32)
     if dtype == 1:
-        return f.astype(np.float16).astype(np.float64)
+        with np.errstate(over="ignore"):
+            return f.astype(np.float16).astype(np.float64)
     if dtype == 2:
         u = f.view(np.uint32).astype(np.uint64)
         u = ((u + 0x7fff + ((u >> 16) & 1)) & 0xffff0000).astype(np.uint32)
-        return u.view(np.float32).astype(np.float64).reshape(f.shape)
+        with np.errstate(invalid="ignore"):
+            out = u.view(np.float32).astype(np.float64).reshape(f.shape)
+        out[np.isnan(f)] = np.nan          # (the carry of the rounding would take a NaN with only low mantissa bits set to Inf: a NaN stays a NaN)
+        return out
     return f.astype(np.float64)
 
 
@@ -494,3 +498,223 @@ def block_row_rows(v, r, br=None):
 
 
 POISON_B_PLACEMENTS = [(c, j) for c in (1, 7) for j in (None, 0, 37, -1)]          # (block column c*, column j* of B: None = all of them, -1 = the last)
+
+
+# ---- accuracy inputs: is the arithmetic still fp32? -----------------------------------------------------------------------------------------------------------
+ACC_Q = (1, 2, 3, 4, 8, None)                       # non-zeros row i of a block-row keeps (i % 6); None = all of its stored positions
+ACC_EXP = {0: 12, 1: 8, 2: 12}                      # kind "wide": exponents -E .. E per storage type (f16: products up to 2^18 and sums of them stay far inside fp32, the operands inside fp16's normal range)
+U32 = 2.0 ** -24                                    # the unit roundoff of fp32
+
+
+def accuracy_draw(rng, size, kind, dtype):
+    """float64 full-mantissa values m * 2^e, m uniform in [1, 2), random sign; kind 'wide': e uniform in -E..E (ACC_EXP), 'unit': e = 0; rounded to the storage
+    type with edge_round (every value is then exactly what the device holds)"""
+    m = rng.uniform(1.0, 2.0, size)
+    e = rng.integers(-ACC_EXP[dtype], ACC_EXP[dtype] + 1, size) if kind == "wide" else np.zeros(size, np.int64)
+    s = np.where(rng.random(size) < 0.5, -1.0, 1.0)
+    assert kind in ("wide", "unit")
+    return edge_round(s * m * 2.0 ** e, dtype).reshape(np.shape(m))
+
+
+def accuracy_values(v, kind, dtype, seed, dense=False):
+    """a mab (float32, already rounded to the storage type `dtype`) for the geometry v, index arrays unchanged: row i of each block-row keeps ACC_Q[i % 6]
+    non-zeros among its stored positions inside cols (seeded choice), each an accuracy_draw value; everything else -- the other stored positions and the
+    positions past cols -- is 0.0.  dense: every row keeps all of them (the A of spmm_ba: sparta_vbs_create_transposed drops exact zeros, and blocks that
+    are nearly all zeros become sparse rows; the short sums then come from the other operand, accuracy_dense(few_rows_from=...))"""
+    rng = np.random.default_rng(seed)
+    w = int(v.block_col_size)
+    mab = np.zeros(len(v.mab), np.float64)
+    blocks = edge_blocks(v)
+    for ib in range(v.block_rows):
+        r0, h = int(v.row_part[ib]), int(v.row_part[ib + 1] - v.row_part[ib])
+        mine = [(off, valid) for off, br0, bh, _, valid in blocks if br0 == r0 and bh == h and h > 0]
+        if not mine or h == 0:
+            continue
+        pos = np.concatenate([off + np.arange(valid) * h for off, valid in mine])          # row 0's stored positions; row i: + i
+        for i in range(h):
+            q = None if dense else ACC_Q[i % len(ACC_Q)]
+            sel = pos if q is None or q >= len(pos) else rng.choice(pos, q, replace=False)
+            mab[sel + i] = accuracy_draw(rng, len(sel), kind, dtype)
+    return mab.astype(np.float32)
+
+
+def accuracy_csr(which, kind, dtype, seed):
+    """(CSR, grouping, w) of PCSR / PCSR9 / PSPLIT / PUNI with the pattern unchanged and new values: row i keeps ACC_Q[i % 6] of its nonzeros as accuracy_draw values,
+    the others are stored 0.0 (which the kernels skip or multiply: an exact zero adds no error either way)"""
+    import sparta_amd as sa
+    thin = which == "PCSR9"          # PCSR with ONE non-zero value in every ninth row and 0.0 everywhere else: 57 non-zeros on 512 columns, few enough (8 nnz < cols)
+    #                                  for the sparse-row kernels to read a column-major B in place
+    m, g, w = {"PCSR": poison_csr, "PCSR9": poison_csr, "PSPLIT": poison_split, "PUNI": poison_union}[which]()
+    rng = np.random.default_rng(seed)
+    vals = np.zeros(len(m.colidx), np.float64)
+    for i in range(m.rows):
+        lo, hi = int(m.rowptr[i]), int(m.rowptr[i + 1])
+        q = ACC_Q[i % len(ACC_Q)]
+        if thin:
+            q = 1 if i % 9 == 0 else 0
+        if hi > lo and q != 0:
+            sel = np.arange(lo, hi) if q is None or q >= hi - lo else rng.choice(np.arange(lo, hi), q, replace=False)
+            vals[sel] = accuracy_draw(rng, len(sel), kind, dtype)
+    return sa.CSR(m.rows, m.cols, m.rowptr, m.colidx, vals.astype(np.float32)), g, w
+
+
+def accuracy_dense(shape, kind, dtype, seed, k_sparse=False, few_rows_from=None):
+    """a dense operand (float64, rounded to `dtype`) of accuracy_draw values.  k_sparse (the X / Y of sddmm, rows x k): row i is non-zero in only 1, 3 or all
+    of the k columns (i % 3; the sets are nested and the same for every operand of one k, so a row of X meets a row of Y in min of the two counts).
+    few_rows_from (the X of spmm_t / the B of spmm_ba, rows x n; an index array): column j keeps ACC_Q[j % 6] non-zero rows chosen among these rows."""
+    rng = np.random.default_rng(seed)
+    M = accuracy_draw(rng, shape, kind, dtype)
+    if k_sparse:
+        k = shape[1]
+        order = np.random.default_rng(4242 + k).permutation(k)
+        keep = np.zeros(shape, bool)
+        for i in range(shape[0]):
+            keep[i, order[:(1, 3, k)[i % 3]]] = True
+        M = np.where(keep, M, 0.0)
+    if few_rows_from is not None:
+        keep = np.zeros(shape, bool)
+        for j in range(shape[1]):
+            q = ACC_Q[j % len(ACC_Q)]
+            keep[few_rows_from if q is None or q >= len(few_rows_from) else rng.choice(few_rows_from, q, replace=False), j] = True
+        M = np.where(keep, M, 0.0)
+    return M
+
+
+def gamma_terms(D, B, C0=None):
+    """K of gamma_bound: per element of D @ B, the number of products of two non-zeros, plus 1 where C0 is given"""
+    return (D != 0).astype(np.float64) @ (B != 0).astype(np.float64) + (0.0 if C0 is None else 1.0)
+
+
+def gamma_bound(D, B, C0=None, factor=2.0):
+    """per-element tolerance of an fp32 evaluation of D @ B (+ C0) against the exact product; D, B, C0 float64, already rounded for 16-bit handles.
+
+        K   = (D != 0) @ (B != 0)  (+ 1 where C0 is given)          the number of fp32 terms the element really sums
+        g_K = K u / (1 - K u),  u = 2^-24
+        tol = min(1e-5, 2 g_K) * (|D| @ |B| + |C0|)
+
+    Derivation (Higham, Accuracy and Stability of Numerical Algorithms, section 3.1 and 4.2): each fp32 operation with round to nearest returns the exact result
+    times (1 + d), |d| <= u.  In ANY summation tree of K products every product passes through at most K such factors: one for the rounding of the product (none
+    when the multiply-add is fused, or when the product of two 16-bit values is exact) and at most K - 1 for the additions above it.  So the computed sum is
+    sum a_k b_k (1 + t_k) with |t_k| <= (1 + u)^K - 1 <= g_K, whatever the order and whether fused or not: |computed - exact| <= g_K sum |a_k b_k|.  An exact zero
+    operand gives the product 0 and x + 0 = x exactly, so it adds neither a term nor a rounding: K counts the non-zero products only (an accumulating call adds
+    the previous C as one more term).  The factor 2 covers an adder that truncates instead of rounding to nearest (|d| <= 2 u).  The min keeps the bound at
+    least as tight as the suite's 1e-5 * sum|a||b| for every K (2 g_K passes 1e-5 at K = 84).
+    `factor` is 2 for every caller.  It may take another value only for the kernels of a matrix instruction whose own summation a stand-alone program has
+    measured to be coarser than this model, and then that measured figure ("Parity bar"); nothing else may set it."""
+    K = gamma_terms(D, B, C0)
+    scale = np.abs(D) @ np.abs(B) + (0.0 if C0 is None else np.abs(C0))
+    g = K * U32 / (1.0 - K * U32)
+    return np.minimum(1e-5, factor * g) * scale
+
+
+def fp32_eval(D, B, C0=None, order=None, product=None, store=np.float32, track=False):
+    """sum over k in `order` (default ascending) of D[:, k] * B[k, :] with an unfused multiply and add in np.float32, starting from C0; the loop skips the k
+    where a factor is all zero (x + 0 = x).  product(a, b): another arithmetic for the products (float64 in, float64 out: rounded to fp32 here); store: the
+    type the partial sums are kept in.  Returns (sum as float64, smallest non-zero |partial sum or product|, largest) -- the last two only with track."""
+    D32, B32 = D.astype(np.float32), B.astype(np.float32)
+    acc = np.zeros((D.shape[0], B.shape[1]), store) if C0 is None else C0.astype(np.float32).astype(store)
+    ks = np.flatnonzero((D != 0).any(axis=0) & (B != 0).any(axis=1))
+    ks = ks if order is None else order(ks)
+    lo, hi = np.inf, 0.0
+    with np.errstate(over="ignore", invalid="ignore"):
+        for k in ks:
+            p = D32[:, k, None] * B32[None, k, :] if product is None else product(D[:, k, None], B[None, k, :]).astype(np.float32)
+            acc = (acc.astype(np.float32) + p).astype(store)
+            for x in (p, acc) if track else ():
+                a = np.abs(x[x != 0]).astype(np.float64)
+                if a.size:
+                    lo, hi = min(lo, float(a.min())), max(hi, float(a.max()))
+    return acc.astype(np.float64), lo, hi
+
+
+def _bf16_trunc(x):
+    return (np.ascontiguousarray(x, np.float32).view(np.uint32) & np.uint32(0xffff0000)).view(np.float32).astype(np.float64)
+
+
+def weak_bf16_split(a, b):
+    """the product of two fp32 values each split into three bf16 terms (hi + mid + lo = the value exactly: 3 x 8 bits), without the products of two low terms
+    (mid x mid, mid x lo, lo x lo): a_hi * b + a_low * b_hi.  What is dropped is about 2^-16 of the product."""
+    ah, bh = _bf16_trunc(a), _bf16_trunc(b)
+    return ah * b + (a - ah) * bh
+
+
+def weak_trunc10(a, b):
+    """operands cut to 10 explicit mantissa bits (fp16's / TF32's) before an exact product"""
+    cut = lambda x: (np.ascontiguousarray(x, np.float32).view(np.uint32) & np.uint32(0xffffe000)).view(np.float32).astype(np.float64)  # noqa: E731
+    return cut(a) * cut(b)
+
+
+# the input sets of tests/test_accuracy_gpu.py, by name; tests/test_accuracy_host.py proves the bound on each.  (op, source, dtype, kind, n or k)
+ACC_SETS = (
+    [("fwd", k, 0, "wide", n) for k in POISON_F32 for n in (128, 130)]
+    + [("fwd", k, dt, "wide", n) for dt in (1, 2) for k, n in (("P32", 128), ("P64", 128), ("P64", 256))]
+    + [("fwd", k, dt, "unit", 128) for k, dt in (("P32", 0), ("P64", 0), ("P13", 0), ("P32", 1), ("P64", 2), ("w128h20", 0), ("w128h80", 0), ("w256", 2))]
+    + [("fwd", "P32G", 0, "wide", 128), ("fwd", "P64G", 2, "wide", 128)]
+    + [("csr", "PCSR", 0, "wide", 40), ("csr", "PCSR", 0, "wide", 128), ("csr", "PCSR", 2, "wide", 128), ("csr", "PCSR", 0, "wide", 8),
+       ("csr", "PSPLIT", 0, "wide", 128), ("csr", "PSPLIT", 2, "wide", 128), ("csr", "PUNI", 0, "wide", 128), ("csr", "PUNI", 2, "wide", 128)]
+    + [("t", k, dt, kind, 128) for k, dt in (("P32", 0), ("P13", 0), ("P64", 1), ("P32", 2)) for kind in ("wide", "unit")]
+    + [("ba", "P32", 0, "wide", 128)]
+    + [("sddmm", k, dt, kind, kk) for k, dt in (("P32", 0), ("P13", 0), ("P64", 1), ("P32", 2)) for kk in (128, 37) for kind in (("wide", "unit") if kk == 128 else ("wide",))]
+    + [("csr", "PCSR9", 0, "wide", 128), ("csr", "PCSR9", 2, "wide", 128)]          # (appended: the seed of a set follows its place in this list)
+)
+_acc = {}
+
+
+def acc_id(s):
+    return "%s-%s-%s-%s-%d" % (s[0], s[1], ("f32", "f16", "bf16")[s[2]], s[3], s[4])
+
+
+def accuracy_set(s):
+    """the operands of the input set s (one entry of ACC_SETS), cached and never changed: a dict with L, R (float64: the product under test is L @ R), C0 (the
+    previous output of an accumulating call, fp32 values), check (bool: the elements of L @ R that the entry point writes) and what the op needs besides:
+      fwd    v, mab: C = A B                      csr   m, g, w: the same on a handle made from a CSR (rows in the handle's order)
+      t      v, mab: Ct = A^T X; L = A^T, R = X   ba    v, mab: C^T = A^T B^T on the transposed handle, the same operands
+      sddmm  v, X, Y: L = X, R = Y^T, check = the stored positions inside cols"""
+    if s in _acc:
+        return _acc[s]
+    op, key, dtype, kind, n = s
+    seed = 20261100 + 7 * ACC_SETS.index(s)
+    out = {}
+    if op == "csr":
+        m, g, w = accuracy_csr(key, kind, dtype, seed)
+        D, _ = csr_dense_and_stored(m, g, w)
+        out.update(m=m, g=g, w=w, L=D, R=accuracy_dense((m.cols, n), kind, dtype, seed + 1))
+    else:
+        v = (poison_geometries() if key.startswith("P") else train_geometries())[key]
+        mab = accuracy_values(v, kind, dtype, seed, dense=op == "ba")
+        D = edge_dense(v, dtype, mab=mab)
+        out.update(v=v, mab=mab)
+        if op == "fwd":
+            out.update(L=D, R=accuracy_dense((v.cols, n), kind, dtype, seed + 1))
+        elif op in ("t", "ba"):
+            full = np.flatnonzero(((D != 0).sum(axis=1) == stored_mask(v).sum(axis=1)) & (D != 0).any(axis=1))          # the rows that kept all their positions
+            out.update(L=np.ascontiguousarray(D.T), R=accuracy_dense((v.rows, n), kind, dtype, seed + 1, few_rows_from=full))
+        else:
+            X, Y = accuracy_dense((v.rows, n), kind, dtype, seed + 1, k_sparse=True), accuracy_dense((v.cols, n), kind, dtype, seed + 2, k_sparse=True)
+            out.update(X=X, Y=Y, L=X, R=np.ascontiguousarray(Y.T), check=stored_mask(v))
+    shape = (out["L"].shape[0], out["R"].shape[1])
+    out.setdefault("check", np.ones(shape, bool))
+    out["C0"] = accuracy_draw(np.random.default_rng(seed + 3), shape, kind, 0)
+    for a in out.values():
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    _acc[s] = out
+    return out
+
+
+def _bits(*u):
+    return np.array(u, np.uint32).view(np.float32)
+
+
+# fp32 inputs at the edges of the conversions to fp16 and bf16 (to_h16 at creation, the update and conversion kernels on the device); each also negated (ACC_SPECIALS)
+_SPECIALS_POS = np.concatenate([
+    np.array([1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11, 1 + 2.0 ** -8, 1 + 3 * 2.0 ** -8,          # ties to even in fp16 (down, up) and in bf16 (down, up)
+              1 + 2.0 ** -11 + 2.0 ** -20, 1 + 2.0 ** -8 - 2.0 ** -20,                       # just above / just below a tie
+              65504.0, 65519.99, 65520.0, 70000.0,                                           # fp16: the largest finite value; the last input that rounds to it; the first that rounds to Inf
+              2.0 ** -14, 2.0 ** -14 - 2.0 ** -24, 2.0 ** -24, 3 * 2.0 ** -24, 2.0 ** -25, 2.0 ** -25 * (1 + 2.0 ** -20), 2.0 ** -26, 1.5 * 2.0 ** -24,          # fp16: smallest normal, largest and smallest subnormal, ties and halves below them
+              2.0 ** -126, 2.0 ** -133, 3 * 2.0 ** -133, 2.0 ** -134, 2.0 ** -134 * (1 + 2.0 ** -10), 2.0 ** -149, 2.0 ** -126 - 2.0 ** -133,          # bf16: smallest normal, subnormals (fp32 subnormals all), a tie to 0
+              0.0, 1.0, np.inf], np.float64).astype(np.float32),
+    _bits(0x7f7f0000, 0x7f7fffff, 0x7f7f8000, 0x7f7f7fff,          # bf16's largest finite value; fp32's (Inf in both 16-bit types); the tie that rounds to Inf in bf16; the last input that stays finite
+          0x7f800001, 0x7f80ffff, 0x7fc00000, 0x7f801000),         # NaNs with only low mantissa bits set (a conversion that cuts the mantissa makes them Inf), the quiet NaN
+])
+ACC_SPECIALS = np.concatenate([_SPECIALS_POS, -_SPECIALS_POS])
