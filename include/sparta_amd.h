@@ -410,6 +410,37 @@ int sparta_vbs_sddmm(sparta_vbs_t* A, const void* X, int64_t ldx, const void* Y,
  * SPARTA_ERR_INVALID on a NULL handle, or a NULL mab with nztot > 0. */
 int sparta_vbs_set_values(sparta_vbs_t* A, const float* mab, int32_t ptr_space, void* stream, float* dt_ms);
 
+/* One SGD step on the caller's fp32 master copy AND the update of the handle, in one pass: what `W -= lr * G; sparta_vbs_set_values(A, W)`
+ * does, without reading W a second time.  Device pointers only.  W (the weights), G (the gradient, what sparta_vbs_sddmm writes) and M (the
+ * momentum buffer) hold nztot floats each in the layout of sparta_vbs_host.mab (a range handle: the slice of its block-rows, from 0); they may
+ * start on any 4-byte boundary and must not overlap.  M may be NULL exactly when cfg->momentum == 0 (it is then neither read nor written).
+ * Per stored element i, every operation rounded once to fp32 in this order, never contracted into an FMA:
+ *     g = G[i]
+ *     if (grad_scale   != 1) g = g * grad_scale
+ *     if (weight_decay != 0) g = g + (weight_decay * W[i])
+ *     if (momentum     != 0) { m = (momentum * M[i]) + g;  M[i] = m;  g = m; }
+ *     W[i] = W[i] - (lr * g)
+ * -- torch.optim.SGD with dampening 0, no Nesterov, M starting as zeros; a float32 restatement on the host reproduces W and M bit for bit.
+ * Each of the nztot elements is updated exactly once; positions past `cols` in a ragged last block column are elements like any other.
+ * After the call, in stream order, every entry of the handle behaves exactly as if sparta_vbs_set_values(A, W_new) had run: the fp32 fragment
+ * image (k-compaction redone from the zero pattern of the NEW values), the reference-layout image if held, the 16-bit stream, pair and hub
+ * slices (rounded as creation rounds), the image of sparta_vbs_spmm_t.
+ * Two forms, same results.  Where ONE image of the handle holds every stored element exactly once, the kernel that writes that image can do the
+ * arithmetic in its registers (fp32: the fragment image of a handle without 33..64-row tiles; 16-bit: the slices of the only non-empty stream plan
+ * of a handle without a hub plan, the pair tiles of 32-wide blocks among them); the remaining images are then written from the new W.  Otherwise one
+ * elementwise kernel does the arithmetic and the launches of sparta_vbs_set_values follow.  Every step takes the first form where the handle allows
+ * it (it measured faster); the environment variable SPARTA_SGD_FUSE=0, read at every call, asks for the second form on every
+ * step.  sparta_vbs_step_info says which form the last step took.
+ * Kernel launches only: no allocation, no synchronisation, capturable into a hipGraph from the first call.  *dt_ms (may be NULL) covers the
+ * kernels and synchronises (SPARTA_ERR_UNSUPPORTED while the stream is being captured).
+ * SPARTA_ERR_UNSUPPORTED on a handle made without SPARTA_CREATE_UPDATABLE (including sparta_vbs_create_from_csr and
+ * sparta_vbs_create_transposed); SPARTA_ERR_INVALID on a NULL handle, a NULL W, G or cfg with nztot > 0, a NULL M with momentum != 0. */
+typedef struct sparta_sgd_cfg { float lr, momentum, weight_decay, grad_scale; } sparta_sgd_cfg;
+int sparta_vbs_sgd_step(sparta_vbs_t* A, float* W, const float* G, float* M, const sparta_sgd_cfg* cfg, void* stream, float* dt_ms);
+/* info_out[4] = {1 if the last sparta_vbs_sgd_step on the handle did the arithmetic inside an image kernel, 0 if it took the two-pass form,
+ * -1 if no step has run yet; kernel launches of that step; 0; 0}. */
+int sparta_vbs_step_info(const sparta_vbs_t* A, int64_t* info_out);
+
 /* Ct (+)= A^T * X on the stored blocks of A: the gradient of the dense operand of C = A * B (X = dC, Ct = dB), on the handle itself, so that
  * it follows sparta_vbs_set_values in stream order.  Only handles made with SPARTA_CREATE_TRANSPOSE take the call; every other handle
  * (flags without the bit, sparta_vbs_create, _create_range, _create_from_csr, _create_transposed): SPARTA_ERR_UNSUPPORTED.

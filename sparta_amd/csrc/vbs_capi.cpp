@@ -801,6 +801,7 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
         v->upd_base[1] = (int64_t)a0.size();
         for (int ty = 0; ty < 2 && updatable; ty++) {
             if (plan.upd_map[ty].empty()) continue;
+            for (const UpdSlice& u : plan.upd_map[ty]) v->upd_cover[ty] += (int64_t)(u.rows_lo + u.rows_hi) * kp;
             CREATE_TRY(hipMalloc((void**)&v->d_upd_map[ty], plan.upd_map[ty].size() * sizeof(UpdSlice)));
             CREATE_TRY(hipMemcpy(v->d_upd_map[ty], plan.upd_map[ty].data(), plan.upd_map[ty].size() * sizeof(UpdSlice), hipMemcpyHostToDevice));
         }
@@ -841,6 +842,7 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
             std::vector<StepRec>& st = steps[ty];
             v->n_steps[ty] = (int64_t)st.size();
             if (st.empty()) continue;
+            if (updatable && !h16) for (const StepRec& r : st) v->upd_cover[ty] += (int64_t)(r.mt_flags & 0xffff) * SK_KP;
             // the pipeline prefetches up to 5 steps (and up to two 8-record batches) past a range end: pad with harmless copies
             for (int k = 0; k < 32; k++) { StepRec d = st[(size_t)v->n_steps[ty] - 1]; d.mt_flags = (d.mt_flags & ~(STEP_LAST | STEP_SPLIT)) | STEP_FIRST; st.push_back(d); }
             CREATE_TRY(hipMalloc((void**)&v->d_steps[ty], st.size() * sizeof(StepRec)));
@@ -2328,6 +2330,30 @@ extern "C" int sparta_vbs_sddmm(sparta_vbs_t* A, const void* X, int64_t ldx, con
 // ---- sparta_vbs_set_values (k_update.hip) -----------------------------------------------------------------------------------------------
 namespace {
 
+// every device image of an updatable handle written from `src` (nztot floats in the mab layout, device memory): the launches of sparta_vbs_set_values, which
+// sparta_vbs_sgd_step repeats behind its elementwise kernel.  Returns the number of launches.
+int launch_images_from(sparta_vbs_t* A, hipStream_t st, const float* src) {
+    int launches = 0;
+    if (A->dtype == SPARTA_F32) {
+        // the fragment image holds every stored element when the handle has no 33..64-row tiles: its kernel then writes the reference-layout image (if the
+        // handle still holds it: a dropped one is rebuilt from the fragment image when a call asks for it) from the same read of mab
+        const bool frag = A->d_a_frag != nullptr && A->n_steps[0] > 0;
+        const bool frag_covers = frag && A->n_steps[1] == 0;
+        if (A->d_A && !frag_covers) { launch_update_copy(st, src, A->nztot, A->d_A); launches++; }
+        if (frag) { launch_update_f32_frag(st, A->d_steps[0], A->n_steps[0], src, A->d_a_frag, frag_covers ? A->d_A : nullptr); launches++; }
+    } else {
+        const bool bf16 = A->dtype == SPARTA_BF16;
+        for (int ty = 0; ty < 2; ty++)
+            if (A->n_steps[ty] > 0) {
+                launch_update_h16(bf16, false, ty ? 64 : 32, A->kp16, st, A->d_upd_map[ty], A->n_steps[ty], src, (uint16_t*)A->d_A + A->upd_base[ty]);
+                launches++;
+            }
+        if (A->n_upd_hub > 0) { launch_update_h16(bf16, true, 64, 64, st, A->d_upd_hub, A->n_upd_hub, src, A->d_hub_A); launches++; }
+        if (A->n_t_src > 0) { launch_update_h16_t(bf16, st, A->d_t_src, A->n_t_src, (int)A->w, src, A->d_t_A); launches++; }      // the image of sparta_vbs_spmm_t
+    }
+    return launches;
+}
+
 int set_values_impl(sparta_vbs_t* A, const float* mab, int32_t ptr_space, void* stream, float* dt_ms) {
     using sparta::fail;
     if (!A) return fail(SPARTA_ERR_INVALID, "sparta_vbs_set_values: NULL handle");
@@ -2349,21 +2375,7 @@ int set_values_impl(sparta_vbs_t* A, const float* mab, int32_t ptr_space, void* 
     }
     if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
     if (A->nztot > 0) {
-        if (A->dtype == SPARTA_F32) {
-            // the fragment image holds every stored element when the handle has no 33..64-row tiles: its kernel then writes the reference-layout image (if the
-            // handle still holds it: a dropped one is rebuilt from the fragment image when a call asks for it) from the same read of mab
-            const bool frag = A->d_a_frag != nullptr && A->n_steps[0] > 0;
-            const bool frag_covers = frag && A->n_steps[1] == 0;
-            if (A->d_A && !frag_covers) launch_update_copy(st, src, A->nztot, A->d_A);
-            if (frag) launch_update_f32_frag(st, A->d_steps[0], A->n_steps[0], src, A->d_a_frag, frag_covers ? A->d_A : nullptr);
-        } else {
-            const bool bf16 = A->dtype == SPARTA_BF16;
-            for (int ty = 0; ty < 2; ty++)
-                if (A->n_steps[ty] > 0)
-                    launch_update_h16(bf16, false, ty ? 64 : 32, A->kp16, st, A->d_upd_map[ty], A->n_steps[ty], src, (uint16_t*)A->d_A + A->upd_base[ty]);
-            if (A->n_upd_hub > 0) launch_update_h16(bf16, true, 64, 64, st, A->d_upd_hub, A->n_upd_hub, src, A->d_hub_A);
-            if (A->n_t_src > 0) launch_update_h16_t(bf16, st, A->d_t_src, A->n_t_src, (int)A->w, src, A->d_t_A);      // the image of sparta_vbs_spmm_t
-        }
+        (void)launch_images_from(A, st, src);
         HIP_TRY(hipGetLastError());
     }
     if (dt_ms) {
@@ -2381,6 +2393,89 @@ extern "C" int sparta_vbs_set_values(sparta_vbs_t* A, const float* mab, int32_t 
     SPARTA_GUARD_BEGIN
     return set_values_impl(A, mab, ptr_space, stream, dt_ms);
     SPARTA_GUARD_END("sparta_vbs_set_values")
+}
+
+// ---- sparta_vbs_sgd_step (k_update.hip) ---------------------------------------------------------------------------------------------------
+namespace {
+
+// Which image kernel may own the arithmetic of a step: the one whose image holds every stored element exactly once.  Plan data only:
+//   fp32    the fragment image, when the handle has no 33..64-row tiles (what lets set_values write d_A from the fragment kernel's own read): the rows
+//           m < mt of the steps of a block-row's <= 32-row tiles partition its stored elements, upd_cover[0] == nztot says no block-row is outside
+//   16-bit  the slices of ONE stream image (build_stream_plans: a block-row is in exactly one of the <= 32-row tiles, the 33..64-row / pair tiles, the hub
+//           plan, and the steps of its tiles partition its elements), when the other stream image and the hub image are empty
+// Returns the tile type of that image, -1 for the two-pass form.
+int sgd_fused_image(const sparta_vbs_t* A) {
+    if (A->dtype == SPARTA_F32) return (A->d_a_frag != nullptr && A->n_steps[0] > 0 && A->n_steps[1] == 0 && A->upd_cover[0] == A->nztot) ? 0 : -1;
+    if (A->n_upd_hub > 0) return -1;
+    for (int ty = 0; ty < 2; ty++)
+        if (A->n_steps[ty] > 0 && A->n_steps[1 - ty] == 0 && A->d_upd_map[ty] != nullptr && A->upd_cover[ty] == A->nztot) return ty;
+    return -1;
+}
+
+// Whether a step asks for the image kernel (sgd_fused_image then says whether the handle has one).  By default every step does: on the headline handle the
+// image kernel measured faster than the elementwise kernel + the set_values launches, and than the same update as torch ops + set_values, with and without
+// momentum, fp32 and f16.  SPARTA_SGD_FUSE=0 asks for the two-pass form on every step, 1 is the default spelled out.  Read at every
+// call (no plan depends on it): scripts/sgd_step_record.py and the tests drive both forms of one handle in one process.
+bool sgd_fuse_wanted() {
+    const char* e = std::getenv("SPARTA_SGD_FUSE");
+    return !e || atoi(e) != 0;
+}
+
+int sgd_step_impl(sparta_vbs_t* A, float* W, const float* G, float* M, const sparta_sgd_cfg* cfg, void* stream, float* dt_ms) {
+    using sparta::fail;
+    if (!A) return fail(SPARTA_ERR_INVALID, "sparta_vbs_sgd_step: NULL handle");
+    if (A->nztot > 0 && (!W || !G || !cfg)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_sgd_step: W, G or cfg is NULL");
+    if (cfg && cfg->momentum != 0.0f && !M) return fail(SPARTA_ERR_INVALID, "sparta_vbs_sgd_step: M is NULL with momentum != 0");
+    if (!(A->create_flags & SPARTA_CREATE_UPDATABLE))
+        return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_sgd_step: the handle was not made with SPARTA_CREATE_UPDATABLE (sparta_vbs_create_range_ex; handles of "
+                                            "sparta_vbs_create_from_csr and sparta_vbs_create_transposed cannot take new values)");
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, "sparta_vbs_sgd_step: hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, true);
+    if (g_capturing && dt_ms) return capture_refusal("time the step (dt_ms != NULL synchronises)", "sparta_vbs_sgd_step");
+    if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
+    int launches = 0;
+    int fused = -1;
+    if (A->nztot > 0) {
+        const SgdCfg c{cfg->lr, cfg->momentum, cfg->weight_decay, cfg->grad_scale};
+        if (sgd_fuse_wanted()) fused = sgd_fused_image(A);
+        if (fused >= 0 && A->dtype == SPARTA_F32) {
+            launch_sgd_f32_frag(st, A->d_steps[0], A->n_steps[0], W, G, M, c, A->d_a_frag, A->d_A);
+            launches = 1;
+        } else if (fused >= 0) {
+            const bool bf16 = A->dtype == SPARTA_BF16;
+            launch_sgd_h16(bf16, fused ? 64 : 32, A->kp16, st, A->d_upd_map[fused], A->n_steps[fused], W, G, M, c, (uint16_t*)A->d_A + A->upd_base[fused]);
+            launches = 1;
+            if (A->n_t_src > 0) { launch_update_h16_t(bf16, st, A->d_t_src, A->n_t_src, (int)A->w, W, A->d_t_A); launches++; }   // reads the W written above
+        } else {
+            launch_sgd_step(st, A->nztot, W, G, M, c);
+            launches = 1 + launch_images_from(A, st, W);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    A->sgd_last_fused = fused >= 0 ? 1 : 0;
+    A->sgd_last_launches = launches;
+    if (dt_ms) {
+        HIP_TRY(hipEventRecord(A->ev1, st));
+        HIP_TRY(hipEventSynchronize(A->ev1));
+        HIP_TRY(hipEventElapsedTime(dt_ms, A->ev0, A->ev1));
+    }
+    return SPARTA_OK;
+}
+
+}  // namespace
+
+extern "C" int sparta_vbs_sgd_step(sparta_vbs_t* A, float* W, const float* G, float* M, const sparta_sgd_cfg* cfg, void* stream, float* dt_ms) {
+    SPARTA_GUARD_BEGIN
+    return sgd_step_impl(A, W, G, M, cfg, stream, dt_ms);
+    SPARTA_GUARD_END("sparta_vbs_sgd_step")
+}
+
+extern "C" int sparta_vbs_step_info(const sparta_vbs_t* A, int64_t* info_out) {
+    if (!A || !info_out) return sparta::fail(SPARTA_ERR_INVALID, "sparta_vbs_step_info: NULL argument");
+    info_out[0] = A->sgd_last_fused; info_out[1] = A->sgd_last_launches; info_out[2] = 0; info_out[3] = 0;
+    return SPARTA_OK;
 }
 
 // ---- sparta_vbs_spmm_t (k_spmm_t.hip) ---------------------------------------------------------------------------------------------------

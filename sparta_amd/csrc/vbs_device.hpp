@@ -265,6 +265,8 @@ struct UpdSlice {
     int32_t rows_lo, rows_hi;
 };
 static_assert(sizeof(UpdSlice) == 32, "UpdSlice must stay 32 bytes");
+// sparta_vbs_sgd_step (k_update.hip): the hyper-parameters of one step, as sparta_sgd_cfg carries them
+struct SgdCfg { float lr, momentum, weight_decay, grad_scale; };
 
 // sparta_vbs_spmm_t (k_spmm_t.hip): Ct (+)= A^T X walks A by block column.  The index (pattern only, built at creation): per block column the list of
 // its blocks, in block-row order; a work item = one panel of <= 32 stored columns of one block column x its whole list.  The image the kernel reads:
@@ -444,6 +446,10 @@ struct sparta_vbs {
     int64_t n_upd_hub = 0;
     void* d_upd_ws = nullptr;
     size_t d_upd_ws_bytes = 0;
+    // sparta_vbs_sgd_step: stored elements the slices of each stream image hold (set at creation from the plan: an image that holds nztot of them, the only
+    // non-empty one, holds each exactly once and its kernel may own the arithmetic); what the last step did (sparta_vbs_step_info)
+    int64_t upd_cover[2] = {0, 0};
+    int32_t sgd_last_fused = -1, sgd_last_launches = 0;
     // sparta_vbs_spmm_t (SPARTA_CREATE_TRANSPOSE handles only): the block-column index, the 16-bit image, the sources of its blocks; host-pointer calls stage X, Ct
     sparta_dev::SpmmTItem* d_t_items = nullptr;
     sparta_dev::SpmmTBlock* d_t_blocks = nullptr;
@@ -506,6 +512,12 @@ void launch_update_f32_frag(hipStream_t st, StepRec* steps, int64_t n_steps, con
 void launch_update_h16(bool bf16, bool hub, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, const float* mab, uint16_t* dst);
 // the 16-bit image of the transposed product, one workgroup pass per block (rounded as to_h16 rounds)
 void launch_update_h16_t(bool bf16, hipStream_t st, const SpmmTSrc* src, int64_t n_blocks, int w, const float* mab, uint16_t* dst);
+// k_update.hip (sparta_vbs_sgd_step): W, G, M = nztot floats each in the mab layout (M is not touched when cfg.momentum == 0)
+void launch_sgd_step(hipStream_t st, int64_t n, float* W, const float* G, float* M, const SgdCfg& cfg);     // the arithmetic alone; the set_values launches follow it
+// the arithmetic inside the image kernel whose image holds every stored element exactly once: launch_update_f32_frag / launch_update_h16 (stream slices) with
+// the new weight computed in registers, stored to W (and M) and handed on to the image
+void launch_sgd_f32_frag(hipStream_t st, StepRec* steps, int64_t n_steps, float* W, const float* G, float* M, const SgdCfg& cfg, float* a_frag, float* A_out);
+void launch_sgd_h16(bool bf16, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, float* W, const float* G, float* M, const SgdCfg& cfg, uint16_t* dst);
 // k_spmm_t.hip: grid = n_items x slabs of kSpmmTSlab columns; dtype = SPARTA_F32 / F16 / BF16
 void launch_spmm_t(int dtype, unsigned n_items, hipStream_t st, const SpmmTParams& p);
 // k_colres.hip

@@ -301,6 +301,51 @@ class DeviceVBS(ValuesRecord):
                                         C.byref(dt) if timed else None))
         return dt.value if timed else None
 
+    def sgd_step(self, values, grad, momentum_buf=None, lr=None, momentum=0.0, weight_decay=0.0, grad_scale=1.0, timed=False, stream=None):
+        """sparta_vbs_sgd_step, device tensors: one SGD step on `values` (the float32 master copy, updated in place) with the gradient `grad` (what sddmm
+        writes) and, when momentum != 0, the buffer `momentum_buf` (updated in place; zeros before the first step) -- torch.optim.SGD with dampening 0 and no
+        Nesterov, grad first multiplied by grad_scale -- and the handle's images written from the new values in the same pass: afterwards the handle behaves
+        as after set_values(values).  All three: contiguous float32 tensors of nztot elements on this device, in the layout of VBR.mab.  Stream-ordered on
+        torch's current stream.  The version counter of `values` is bumped (a backward of a forward taken before the step raises, as after any in-place
+        change) and the handle records the new version, so that the next vbs_linear forward with the same tensor skips set_values.  Needs updatable=True.
+        Returns kernel ms if timed else None."""
+        import torch
+        if lr is None:
+            raise ValueError("lr is required")
+        ops = [("values", values), ("grad", grad)] + ([("momentum_buf", momentum_buf)] if momentum_buf is not None else [])
+        for name, t in ops:
+            if not (t.is_cuda and t.dtype == torch.float32 and t.device.index == self.device and t.is_contiguous()):
+                raise ValueError("%s must be a contiguous float32 tensor on device %d" % (name, self.device))
+            if t.numel() != self._nztot():
+                raise ValueError("%s must hold nztot = %d elements" % (name, self._nztot()))
+        st = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+        cfg = _lib.SgdCfg(float(lr), float(momentum), float(weight_decay), float(grad_scale))
+        dt = C.c_float(0)
+        self._values_replaced()
+        check(lib.sparta_vbs_sgd_step(self.h, C.cast(C.c_void_p(values.data_ptr()), _f32p), C.cast(C.c_void_p(grad.data_ptr()), _f32p),
+                                      None if momentum_buf is None else C.cast(C.c_void_p(momentum_buf.data_ptr()), _f32p), C.byref(cfg),
+                                      C.c_void_p(st), C.byref(dt) if timed else None))
+        # the kernels wrote through the raw pointers: tell autograd, then note that the handle holds exactly this version
+        bump = getattr(torch.autograd.graph, "increment_version", None)
+        for t in (values,) + (() if momentum_buf is None else (momentum_buf,)):
+            if bump is not None:
+                bump(t)
+            else:
+                with torch.no_grad():
+                    t.add_(0)
+        if torch.cuda.is_current_stream_capturing():
+            self._autograd_captured = True          # (as a captured forward: replays change the handle's values without passing through Python)
+        if not self._autograd_captured:
+            self._autograd_values = (values, values._version)
+        return dt.value if timed else None
+
+    def step_info(self):
+        """sparta_vbs_step_info: {"fused": 1 the last sgd_step did its arithmetic inside an image kernel / 0 it ran the elementwise kernel and then the
+        set_values launches / -1 no step yet, "launches": kernel launches of that step}"""
+        out = (C.c_int64 * 4)()
+        check(lib.sparta_vbs_step_info(self.h, out))
+        return {"fused": int(out[0]), "launches": int(out[1])}
+
     def set_values_host(self, mab):
         """set_values with a host array (numpy, fp32, nztot elements), staged through scratch of the handle.  Returns kernel ms."""
         mab = np.ascontiguousarray(mab, np.float32).reshape(-1)
