@@ -437,8 +437,47 @@ int sparta_vbs_set_values(sparta_vbs_t* A, const float* mab, int32_t ptr_space, 
  * sparta_vbs_create_transposed); SPARTA_ERR_INVALID on a NULL handle, a NULL W, G or cfg with nztot > 0, a NULL M with momentum != 0. */
 typedef struct sparta_sgd_cfg { float lr, momentum, weight_decay, grad_scale; } sparta_sgd_cfg;
 int sparta_vbs_sgd_step(sparta_vbs_t* A, float* W, const float* G, float* M, const sparta_sgd_cfg* cfg, void* stream, float* dt_ms);
-/* info_out[4] = {1 if the last sparta_vbs_sgd_step on the handle did the arithmetic inside an image kernel, 0 if it took the two-pass form,
- * -1 if no step has run yet; kernel launches of that step; 0; 0}. */
+
+/* One Adam / AdamW step on the caller's fp32 master copy AND the update of the handle, in one pass.  Device pointers only.  W (the weights), G (the
+ * gradient), M (exp_avg) and V (exp_avg_sq) hold nztot floats each in the layout of sparta_vbs_host.mab (a range handle: the slice of its
+ * block-rows, from 0); they may start on any 4-byte boundary and must not overlap.  M and V are zeros before the first step.
+ * S is the step state: 32 bytes of caller-owned device memory on a 4-byte boundary (checkpointing it is the caller's copy), zero-filled for a
+ * fresh optimizer:
+ *     S[0] int32  steps done, t            S[3] fp32  step_size of the last step
+ *     S[1] fp32   running product of beta1 S[4] fp32  d of the last step
+ *     S[2] fp32   running product of beta2 S[5..7]    written as zero
+ * Every operation is rounded once to fp32 in the order written, never contracted into an FMA; division and square root are IEEE correctly
+ * rounded.  Once per step, on the device, before any element is touched:
+ *     if (t == 0) { p1 = beta1; p2 = beta2; } else { p1 = p1 * beta1; p2 = p2 * beta2; }
+ *     t = t + 1
+ *     bc1 = 1 - p1;  bc2 = 1 - p2;  step_size = lr / bc1;  d = sqrt(bc2)
+ * Per stored element i, with omb1 = 1.0f - beta1, omb2 = 1.0f - beta2, dk = 1.0f - (lr * weight_decay) taken in fp32 on the host:
+ *     g = G[i];                       if (grad_scale != 1) g = g * grad_scale
+ *     if (weight_decay != 0 &&  decoupled) w = W[i] * dk        else w = W[i]
+ *     if (weight_decay != 0 && !decoupled) g = g + (weight_decay * w)
+ *     m = (beta1 * M[i]) + (omb1 * g);          M[i] = m
+ *     v = (beta2 * V[i]) + (omb2 * (g * g));    V[i] = v
+ *     den = (sqrt(v) / d) + eps
+ *     W[i] = w - (step_size * (m / den))
+ * decoupled = 1 is torch.optim.AdamW, decoupled = 0 torch.optim.Adam with L2 weight decay, both without amsgrad and without maximize; the running
+ * products differ from torch's beta ** step by roundings only.  A float32 restatement on the host reproduces W, M, V and S bit for bit.
+ * Each of the nztot elements is updated exactly once (positions past `cols` in a ragged last block column are elements like any other), and
+ * after the call, in stream order, every entry of the handle behaves exactly as after sparta_vbs_set_values(A, W_new): every image
+ * sparta_vbs_sgd_step lists.  The two forms are those of sparta_vbs_sgd_step, chosen by the same rule, each behind a one-wave kernel that advances
+ * S; the environment variable SPARTA_ADAM_FUSE=0|1, read at every call, asks for the two-pass form on every step / for the image kernel wherever
+ * the handle has one (the default is the form that measured faster).  sparta_vbs_step_info reports the form taken.
+ * The step count is read and advanced on the device: the call can be captured into a hipGraph from the first call, and a replay advances t as
+ * an eager call does.  lr and the other fields of cfg are call arguments and are BAKED INTO a capture (as sparta_vbs_sgd_step bakes its own): a
+ * learning-rate schedule under capture needs a re-capture.
+ * Kernel launches only: no allocation, no synchronisation.  *dt_ms (may be NULL) covers the kernels and synchronises (SPARTA_ERR_UNSUPPORTED
+ * while the stream is being captured).
+ * SPARTA_ERR_UNSUPPORTED on a handle made without SPARTA_CREATE_UPDATABLE; SPARTA_ERR_INVALID, with nothing launched, on a NULL handle, a NULL
+ * W, G, M, V, S or cfg with nztot > 0, beta1 or beta2 outside [0, 1), eps <= 0, reserved != 0. */
+typedef struct sparta_adam_cfg { float lr, beta1, beta2, eps, weight_decay, grad_scale; int32_t decoupled; int32_t reserved; } sparta_adam_cfg;
+int sparta_vbs_adam_step(sparta_vbs_t* A, float* W, const float* G, float* M, float* V, void* S,
+                         const sparta_adam_cfg* cfg, void* stream, float* dt_ms);
+/* info_out[4] = {1 if the last sparta_vbs_sgd_step / sparta_vbs_adam_step on the handle did the arithmetic inside an image kernel, 0 if it took
+ * the two-pass form, -1 if no step has run yet; kernel launches of that step (an Adam step counts its tick); 0; 0}. */
 int sparta_vbs_step_info(const sparta_vbs_t* A, int64_t* info_out);
 
 /* Ct (+)= A^T * X on the stored blocks of A: the gradient of the dense operand of C = A * B (X = dC, Ct = dB), on the handle itself, so that

@@ -21,7 +21,7 @@ from .host import (CSR, BlockingEngine, VBR, get_permutation, get_partition, get
                    save_blocking_data, CSV_COLUMNS)
 from .device import DeviceVBS, vbs_multiply, device_count  # noqa: F401
 from . import gen, dist, autograd, optim  # noqa: F401
-from .optim import VbsSGD  # noqa: F401
+from .optim import VbsSGD, VbsAdamW  # noqa: F401
 
 # revision tag of the device kernels: PMC-derived numbers kept under profiles/ (HBM traffic per launch) carry it, and bench.py
 # only quotes them for the revision they were measured on

@@ -43,7 +43,7 @@ SYMBOLS = [
     "sparta_vbs_sddmm",
     "sparta_vbs_create_range_ex", "sparta_vbs_set_values", "sparta_vbs_flags", "sparta_frag_positions",
     "sparta_vbs_spmm_t", "sparta_spmm_t_host_check",
-    "sparta_vbs_sgd_step", "sparta_vbs_step_info",
+    "sparta_vbs_sgd_step", "sparta_vbs_step_info", "sparta_vbs_adam_step",
 ]
 
 
@@ -91,6 +91,12 @@ class SgdCfg(C.Structure):
     _fields_ = [("lr", C.c_float), ("momentum", C.c_float), ("weight_decay", C.c_float), ("grad_scale", C.c_float)]
 
 
+class AdamCfg(C.Structure):
+    """sparta_adam_cfg"""
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("grad_scale", C.c_float), ("decoupled", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SpartaError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("sparta_amd error %d: %s" % (code, msg))
@@ -129,6 +135,7 @@ def _load():
                                              C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]
     L.sparta_vbs_set_values.argtypes = [vp, f32p, C.c_int32, vp, f32p]
     L.sparta_vbs_sgd_step.argtypes = [vp, f32p, f32p, f32p, C.POINTER(SgdCfg), vp, f32p]
+    L.sparta_vbs_adam_step.argtypes = [vp, f32p, f32p, f32p, f32p, vp, C.POINTER(AdamCfg), vp, f32p]
     L.sparta_vbs_step_info.argtypes = [vp, i64p]
     L.sparta_vbs_flags.argtypes = [vp, i32p]
     L.sparta_vbs_spmm_t.argtypes = [vp, vp, C.c_int64, C.c_int32, f32p, C.c_int64, C.c_int32, C.c_int32, vp, f32p]

@@ -9,6 +9,8 @@
 // new weight to the code that ballots, rounds and places it.  That is right only where the kernel's image holds every stored element exactly once
 // (sgd_fused_image, vbs_capi.cpp, decides from the plan); everywhere else
 //   vbs_sgd_step_kernel         the same arithmetic, elementwise over nztot floats, runs in front of the set_values launches
+// sparta_vbs_adam_step is a third value source, AdamStep (W, G, M, V and the device-resident step state S): vbs_adam_f32_frag_kernel, vbs_adam_h16_kernel and the
+// elementwise vbs_adam_step_kernel, behind the one-wave vbs_adam_tick_kernel that advances S once per step.
 // Every kernel writes exactly the elements creation wrote (the slices behind the end of an image keep what creation left there) and reads mab
 // only where the plan says a stored element is: nothing is read past mab + nztot.  Offsets are 64-bit throughout.
 #include "vbs_kernel_common.hpp"
@@ -64,6 +66,80 @@ __global__ __launch_bounds__(kThreads) void vbs_sgd_step_kernel(int64_t n, SgdSt
     for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) { float x[1]; s.step<1>(i, 1, x); }
 }
 
+// ---- the value source of sparta_vbs_adam_step ---------------------------------------------------------------------------------------------------
+// The once-per-step block of include/sparta_amd.h: the step count and the running products of the betas live in S (device memory), so that a captured step
+// advances them at every replay.  Every operation rounded once to fp32; the division and the square root are the correctly rounded ones (no fast-math flag
+// on this file).
+__device__ __forceinline__ void adam_tick(float beta1, float beta2, float lr, int32_t& t, float& p1, float& p2, float& step_size, float& d) {
+#pragma clang fp contract(off)
+    if (t == 0) { p1 = beta1; p2 = beta2; } else { p1 = p1 * beta1; p2 = p2 * beta2; }
+    t = t + 1;
+    const float bc1 = 1.0f - p1, bc2 = 1.0f - p2;
+    step_size = lr / bc1;
+    d = sqrtf(bc2);
+}
+
+// One wave, one lane at work: S[0] = t, S[1], S[2] = the running products, S[3] = step_size, S[4] = d, S[5..7] = 0 (4-byte accesses: S may sit on any
+// 4-byte boundary).  The element kernels behind it in the stream read S[3] and S[4].
+__global__ __launch_bounds__(64) void vbs_adam_tick_kernel(uint32_t* S, float beta1, float beta2, float lr) {
+    if (threadIdx.x != 0) return;
+    int32_t t = (int32_t)S[0];
+    float p1 = __uint_as_float(S[1]), p2 = __uint_as_float(S[2]), step_size, d;
+    adam_tick(beta1, beta2, lr, t, p1, p2, step_size, d);
+    S[0] = (uint32_t)t; S[1] = __float_as_uint(p1); S[2] = __float_as_uint(p2); S[3] = __float_as_uint(step_size); S[4] = __float_as_uint(d);
+    S[5] = 0u; S[6] = 0u; S[7] = 0u;
+}
+
+// One element of torch.optim.AdamW (decoupled) / torch.optim.Adam with L2 weight decay (no amsgrad, no maximize) in the order include/sparta_amd.h pins, one
+// rounding per operation, no contraction: a float32 restatement on the host reproduces W, M and V bit for bit.
+__device__ __forceinline__ float adam_element(const AdamCfg& c, float step_size, float d, float w, float g, float& m, float& v) {
+#pragma clang fp contract(off)
+    if (c.grad_scale != 1.0f) g = g * c.grad_scale;
+    if (c.weight_decay != 0.0f) {
+        if (c.decoupled) w = w * c.dk;
+        else g = g + c.weight_decay * w;
+    }
+    m = c.beta1 * m + c.omb1 * g;
+    v = c.beta2 * v + c.omb2 * (g * g);
+    const float den = sqrtf(v) / d + c.eps;
+    return w - step_size * (m / den);
+}
+
+// The interface of SgdStep: all 4 N loads of a lane first, then the arithmetic, then the 3 N stores.  step_size and d are what the tick wrote for this step.
+struct AdamStep {
+    float* __restrict__ W; const float* __restrict__ G; float* __restrict__ M; float* __restrict__ V; const float* __restrict__ S;
+    AdamCfg c;
+    template <int N>
+    __device__ __forceinline__ void step(int64_t i0, int64_t stride, float (&x)[N]) const {
+        const float step_size = S[3], d = S[4];
+        float w[N], g[N], m[N], v[N];
+#pragma unroll
+        for (int e = 0; e < N; e++) { w[e] = W[i0 + e * stride]; g[e] = G[i0 + e * stride]; m[e] = M[i0 + e * stride]; v[e] = V[i0 + e * stride]; }
+#pragma unroll
+        for (int e = 0; e < N; e++) x[e] = adam_element(c, step_size, d, w[e], g[e], m[e], v[e]);
+#pragma unroll
+        for (int e = 0; e < N; e++) { W[i0 + e * stride] = x[e]; M[i0 + e * stride] = m[e]; V[i0 + e * stride] = v[e]; }
+    }
+};
+
+// The two-pass form of sparta_vbs_adam_step, shaped as vbs_sgd_step_kernel: 16 bytes per lane and access, the last n % 4 one by one.
+__global__ __launch_bounds__(kThreads) void vbs_adam_step_kernel(int64_t n, AdamStep s) {
+    const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * kThreads;
+    const float step_size = s.S[3], d = s.S[4];
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += stride) {
+        f32x4 w = *reinterpret_cast<const f32x4u*>(s.W + 4 * i);
+        const f32x4 g = *reinterpret_cast<const f32x4u*>(s.G + 4 * i);
+        f32x4 m = *reinterpret_cast<const f32x4u*>(s.M + 4 * i);
+        f32x4 v = *reinterpret_cast<const f32x4u*>(s.V + 4 * i);
+#pragma unroll
+        for (int e = 0; e < 4; e++) { float me = m[e], ve = v[e]; w[e] = adam_element(s.c, step_size, d, w[e], g[e], me, ve); m[e] = me; v[e] = ve; }
+        *reinterpret_cast<f32x4u*>(s.M + 4 * i) = m;
+        *reinterpret_cast<f32x4u*>(s.V + 4 * i) = v;
+        *reinterpret_cast<f32x4u*>(s.W + 4 * i) = w;
+    }
+    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) { float x[1]; s.step<1>(i, 1, x); }
+}
+
 __global__ __launch_bounds__(kThreads) void vbs_update_copy_kernel(const float* __restrict__ mab, int64_t n, float* __restrict__ A) {
     const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * kThreads;
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += stride)      // (the caller's array may start on any 4-byte boundary)
@@ -85,12 +161,15 @@ __device__ __forceinline__ uint32_t upd_h16(float v) {
 }
 
 // the fragment kernel and the slice kernel, once per value source
-#define UPD_SGD 0
+#define UPD_SOURCE 0
 #include "k_update_image.inc"
-#undef UPD_SGD
-#define UPD_SGD 1
+#undef UPD_SOURCE
+#define UPD_SOURCE 1
 #include "k_update_image.inc"
-#undef UPD_SGD
+#undef UPD_SOURCE
+#define UPD_SOURCE 2
+#include "k_update_image.inc"
+#undef UPD_SOURCE
 
 // The image of sparta_vbs_spmm_t: per block [ceil(h / 8)][w][8] -- chunk c = kc * w + q holds rows 8 kc .. 8 kc + 7 of stored column q (rows past h: zeros), what
 // pack_spmm_t_block (vbs_plan.cpp) writes at creation.  One wave per block and pass; a lane writes one 16-byte chunk from 8 consecutive floats of one column of mab.
@@ -134,6 +213,15 @@ void launch_sgd_h16_t(int tms, int kp, hipStream_t st, const UpdSlice* map, int6
     else if (tms == 64 && kp == 32) hipLaunchKernelGGL((vbs_sgd_h16_kernel<BF16, 64, 32>), dim3(upd_grid(n_slices)), block, 0, st, map, n_slices, vs, dst);
     else if (tms == 32 && kp == 64) hipLaunchKernelGGL((vbs_sgd_h16_kernel<BF16, 32, 64>), dim3(upd_grid(n_slices)), block, 0, st, map, n_slices, vs, dst);
     else hipLaunchKernelGGL((vbs_sgd_h16_kernel<BF16, 64, 64>), dim3(upd_grid(n_slices * 2)), block, 0, st, map, n_slices, vs, dst);
+}
+
+template <bool BF16>
+void launch_adam_h16_t(int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, const AdamStep& vs, uint16_t* dst) {   // the grids of launch_update_h16_t
+    const dim3 block(kThreads);
+    if (tms == 32 && kp == 32) hipLaunchKernelGGL((vbs_adam_h16_kernel<BF16, 32, 32>), dim3(upd_grid((n_slices + 1) / 2)), block, 0, st, map, n_slices, vs, dst);
+    else if (tms == 64 && kp == 32) hipLaunchKernelGGL((vbs_adam_h16_kernel<BF16, 64, 32>), dim3(upd_grid(n_slices)), block, 0, st, map, n_slices, vs, dst);
+    else if (tms == 32 && kp == 64) hipLaunchKernelGGL((vbs_adam_h16_kernel<BF16, 32, 64>), dim3(upd_grid(n_slices)), block, 0, st, map, n_slices, vs, dst);
+    else hipLaunchKernelGGL((vbs_adam_h16_kernel<BF16, 64, 64>), dim3(upd_grid(n_slices * 2)), block, 0, st, map, n_slices, vs, dst);
 }
 
 SgdStep sgd_source(float* W, const float* G, float* M, const SgdCfg& cfg) { return SgdStep{W, G, cfg.momentum != 0.0f ? M : nullptr, cfg}; }
@@ -180,6 +268,30 @@ void launch_sgd_h16(bool bf16, int tms, int kp, hipStream_t st, const UpdSlice* 
     if (n_slices <= 0) return;
     if (bf16) launch_sgd_h16_t<true>(tms, kp, st, map, n_slices, sgd_source(W, G, M, cfg), dst);
     else launch_sgd_h16_t<false>(tms, kp, st, map, n_slices, sgd_source(W, G, M, cfg), dst);
+}
+
+
+// ---- sparta_vbs_adam_step -----------------------------------------------------------------------------------------------------------------
+void launch_adam_tick(hipStream_t st, const AdamArgs& a) {
+    hipLaunchKernelGGL(vbs_adam_tick_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<uint32_t*>(a.S), a.c.beta1, a.c.beta2, a.c.lr);
+}
+
+void launch_adam_step(hipStream_t st, int64_t n, const AdamArgs& a) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(vbs_adam_step_kernel, dim3(upd_grid((n / 4 + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, n, AdamStep{a.W, a.G, a.M, a.V, a.S, a.c});
+}
+
+void launch_adam_f32_frag(hipStream_t st, StepRec* steps, int64_t n_steps, const AdamArgs& a, float* a_frag, float* A_out) {
+    if (n_steps <= 0) return;
+    hipLaunchKernelGGL(vbs_adam_f32_frag_kernel, dim3(upd_grid((n_steps + kThreads / 64 - 1) / (kThreads / 64))), dim3(kThreads), 0, st, steps, n_steps,
+                       AdamStep{a.W, a.G, a.M, a.V, a.S, a.c}, a_frag, A_out);
+}
+
+void launch_adam_h16(bool bf16, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, const AdamArgs& a, uint16_t* dst) {
+    if (n_slices <= 0) return;
+    const AdamStep vs{a.W, a.G, a.M, a.V, a.S, a.c};
+    if (bf16) launch_adam_h16_t<true>(tms, kp, st, map, n_slices, vs, dst);
+    else launch_adam_h16_t<false>(tms, kp, st, map, n_slices, vs, dst);
 }
 
 }  // namespace sparta_dev

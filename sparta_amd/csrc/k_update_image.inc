@@ -1,21 +1,31 @@
-// k_update_image.inc -- the two image kernels of k_update.hip, included once per VALUE SOURCE (the file defines UPD_SGD before each inclusion):
-//   UPD_SGD 0   vbs_update_f32_frag_kernel / vbs_update_h16_kernel: a value is the plain load mab[i] (sparta_vbs_set_values)
-//   UPD_SGD 1   vbs_sgd_f32_frag_kernel / vbs_sgd_h16_kernel: the values of a lane come from SgdStep::step -- W, G (and M) loaded, the arithmetic done in
-//               registers, W (and M) stored, the new weights returned (sparta_vbs_sgd_step, where the kernel's image holds every stored element exactly once)
+// k_update_image.inc -- the two image kernels of k_update.hip, included once per VALUE SOURCE (the file defines UPD_SOURCE before each inclusion):
+//   UPD_SOURCE 0   vbs_update_f32_frag_kernel / vbs_update_h16_kernel: a value is the plain load mab[i] (sparta_vbs_set_values)
+//   UPD_SOURCE 1   vbs_sgd_f32_frag_kernel / vbs_sgd_h16_kernel: the values of a lane come from SgdStep::step -- W, G (and M) loaded, the arithmetic done in
+//                  registers, W (and M) stored, the new weights returned (sparta_vbs_sgd_step, where the kernel's image holds every stored element exactly once)
+//   UPD_SOURCE 2   vbs_adam_f32_frag_kernel / vbs_adam_h16_kernel: the same with AdamStep::step -- W, G, M, V loaded, W, M, V stored (sparta_vbs_adam_step)
 // Everything behind the loads -- ballot, k-compaction, rounding, placement -- is the same text.
+#if UPD_SOURCE == 1
+#define UPD_STEP SgdStep
+#define UPD_FRAG_KERNEL vbs_sgd_f32_frag_kernel
+#define UPD_H16_KERNEL vbs_sgd_h16_kernel
+#elif UPD_SOURCE == 2
+#define UPD_STEP AdamStep
+#define UPD_FRAG_KERNEL vbs_adam_f32_frag_kernel
+#define UPD_H16_KERNEL vbs_adam_h16_kernel
+#endif
 
 // The forward of vbs_f32_legacy_from_frag_kernel.  One wave per step q of the one-tile plan (four steps per workgroup and pass): lane = (row m = lane & 31,
 // half g = lane >> 5).  Load i (0..15) of a lane reads element (m, k = 2 i + g) of the step's slice -- the 32 lanes of a half read 32 consecutive floats of
 // one column -- and its ballot gives the "column has a non-zero in the tile's rows" bits of the columns 2 i and 2 i + 1; rows >= mt belong to the next tile of
 // the block-row (or to nobody) and are neither read nor counted.  The position table follows from the 32 bits by the rule the host packer uses
-// (frag_position).  UPD_SGD: the values are the NEW weights (rows m < mt of the steps are every stored element once), so the ballot sees it.
+// (frag_position).  A stepping source: the values are the NEW weights (rows m < mt of the steps are every stored element once), so the ballot sees it.
 // The values go through a 4 KB image in LDS, [position][row], and leave it as the slice wants them: 16-byte quads [row][e = 0..3] of one
 // (j, g), 1 KB of consecutive addresses per store instruction.  Empty columns and rows >= mt are stored as zeros (their loads were masked to zero).
-#if !UPD_SGD
+#if UPD_SOURCE == 0
 __global__ __launch_bounds__(kThreads) void vbs_update_f32_frag_kernel(StepRec* steps, int64_t n_steps, const float* __restrict__ mab, float* __restrict__ a_frag,
                                                                        float* __restrict__ A_out) {
 #else
-__global__ __launch_bounds__(kThreads) void vbs_sgd_f32_frag_kernel(StepRec* steps, int64_t n_steps, SgdStep vs, float* __restrict__ a_frag, float* __restrict__ A_out) {
+__global__ __launch_bounds__(kThreads) void UPD_FRAG_KERNEL(StepRec* steps, int64_t n_steps, UPD_STEP vs, float* __restrict__ a_frag, float* __restrict__ A_out) {
 #endif
     __shared__ float img[kThreads / 64][32 * 32];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, m = lane & 31, g = lane >> 5;
@@ -28,7 +38,7 @@ __global__ __launch_bounds__(kThreads) void vbs_sgd_f32_frag_kernel(StepRec* ste
         if (active) { a_off = steps[q].a_off; h = steps[q].h; mt = steps[q].mt_flags & 0xffff; }
         float v[16];
         uint32_t nonempty = 0;
-#if !UPD_SGD
+#if UPD_SOURCE == 0
 #pragma unroll
         for (int i = 0; i < 16; i++) {
             const int k = 2 * i + g;
@@ -78,13 +88,13 @@ __global__ __launch_bounds__(kThreads) void vbs_sgd_f32_frag_kernel(StepRec* ste
 // One lane = one 16-byte chunk of one slice: 8 consecutive k of one row.  Chunk c of a slice is (k chunk kc = c / TMS, row rr = c % TMS): neighbouring lanes
 // hold neighbouring rows, so each of the 8 loads of a wave reads runs of consecutive floats of one column.  Stream slices store chunk c at c (the layout
 // [k / 8][row][8]: consecutive lanes, consecutive chunks); hub slices at the swizzled place of k_hub16.hip's LDS image.  Rows the map does not cover are zeros.
-// UPD_SGD (stream slices only): a lane owns the 8 elements of its chunk, and the chunks of the map's covered rows are every stored element once.
-#if !UPD_SGD
+// A stepping source (stream slices only): a lane owns the 8 elements of its chunk, and the chunks of the map's covered rows are every stored element once.
+#if UPD_SOURCE == 0
 template <bool BF16, bool HUB, int TMS, int KP>
 __global__ __launch_bounds__(kThreads) void vbs_update_h16_kernel(const UpdSlice* __restrict__ map, int64_t n_slices, const float* __restrict__ mab, uint16_t* __restrict__ dst) {
 #else
 template <bool BF16, int TMS, int KP>
-__global__ __launch_bounds__(kThreads) void vbs_sgd_h16_kernel(const UpdSlice* __restrict__ map, int64_t n_slices, SgdStep vs, uint16_t* __restrict__ dst) {
+__global__ __launch_bounds__(kThreads) void UPD_H16_KERNEL(const UpdSlice* __restrict__ map, int64_t n_slices, UPD_STEP vs, uint16_t* __restrict__ dst) {
     constexpr bool HUB = false;
 #endif
     constexpr int kChunks = TMS * KP / 8;
@@ -93,7 +103,7 @@ __global__ __launch_bounds__(kThreads) void vbs_sgd_h16_kernel(const UpdSlice* _
         const int64_t s = id / kChunks;
         const int c = (int)(id % kChunks), kc = c / TMS, rr = c % TMS;
         const UpdSlice u = map[s];
-#if !UPD_SGD
+#if UPD_SOURCE == 0
         const float* src = nullptr;
         int64_t ld = 0;
         if (rr < u.rows_lo) { src = mab + u.off_lo + rr; ld = u.h_lo; }
@@ -119,3 +129,9 @@ __global__ __launch_bounds__(kThreads) void vbs_sgd_h16_kernel(const UpdSlice* _
         *reinterpret_cast<u32x4*>(dst + s * (int64_t)(TMS * KP) + at) = o;
     }
 }
+
+#if UPD_SOURCE != 0
+#undef UPD_STEP
+#undef UPD_FRAG_KERNEL
+#undef UPD_H16_KERNEL
+#endif

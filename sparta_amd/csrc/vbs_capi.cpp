@@ -2454,8 +2454,8 @@ int sgd_step_impl(sparta_vbs_t* A, float* W, const float* G, float* M, const spa
         }
         HIP_TRY(hipGetLastError());
     }
-    A->sgd_last_fused = fused >= 0 ? 1 : 0;
-    A->sgd_last_launches = launches;
+    A->step_last_fused = fused >= 0 ? 1 : 0;
+    A->step_last_launches = launches;
     if (dt_ms) {
         HIP_TRY(hipEventRecord(A->ev1, st));
         HIP_TRY(hipEventSynchronize(A->ev1));
@@ -2472,9 +2472,83 @@ extern "C" int sparta_vbs_sgd_step(sparta_vbs_t* A, float* W, const float* G, fl
     SPARTA_GUARD_END("sparta_vbs_sgd_step")
 }
 
+// ---- sparta_vbs_adam_step (k_update.hip) --------------------------------------------------------------------------------------------------
+namespace {
+
+// Whether a step asks for the image kernel (sgd_fused_image says whether the handle has one): the default is the form that measured faster on the headline
+// handle, DESIGN.md section 3.8.  SPARTA_ADAM_FUSE=0 asks for the two-pass form on every step, 1 for the image kernel wherever the handle has one.  Read at
+// every call, as SPARTA_SGD_FUSE is.
+bool adam_fuse_wanted() {
+    const char* e = std::getenv("SPARTA_ADAM_FUSE");
+    return !e || atoi(e) != 0;
+}
+
+int adam_step_impl(sparta_vbs_t* A, float* W, const float* G, float* M, float* V, void* S, const sparta_adam_cfg* cfg, void* stream, float* dt_ms) {
+    using sparta::fail;
+    if (!A) return fail(SPARTA_ERR_INVALID, "sparta_vbs_adam_step: NULL handle");
+    if (A->nztot > 0 && (!W || !G || !M || !V || !S || !cfg)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_adam_step: W, G, M, V, S or cfg is NULL");
+    if (cfg) {
+        if (!(cfg->beta1 >= 0.0f && cfg->beta1 < 1.0f) || !(cfg->beta2 >= 0.0f && cfg->beta2 < 1.0f))
+            return fail(SPARTA_ERR_INVALID, "sparta_vbs_adam_step: beta1 and beta2 must lie in [0, 1)");
+        if (!(cfg->eps > 0.0f)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_adam_step: eps must be > 0");
+        if (cfg->reserved != 0) return fail(SPARTA_ERR_INVALID, "sparta_vbs_adam_step: cfg->reserved must be 0");
+    }
+    if (!(A->create_flags & SPARTA_CREATE_UPDATABLE))
+        return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_adam_step: the handle was not made with SPARTA_CREATE_UPDATABLE (sparta_vbs_create_range_ex; handles of "
+                                            "sparta_vbs_create_from_csr and sparta_vbs_create_transposed cannot take new values)");
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, "sparta_vbs_adam_step: hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, true);
+    if (g_capturing && dt_ms) return capture_refusal("time the step (dt_ms != NULL synchronises)", "sparta_vbs_adam_step");
+    if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
+    int launches = 0;
+    int fused = -1;
+    if (A->nztot > 0) {
+        // the three derived constants, each operation rounded once to fp32 (volatile: no contraction, no wider intermediate)
+        volatile float omb1 = 1.0f - cfg->beta1, omb2 = 1.0f - cfg->beta2, lr_wd = cfg->lr * cfg->weight_decay;
+        volatile float dk = 1.0f - lr_wd;
+        const AdamArgs a{W, G, M, V, (float*)S,
+                         AdamCfg{cfg->lr, cfg->beta1, cfg->beta2, cfg->eps, cfg->weight_decay, cfg->grad_scale, omb1, omb2, dk, cfg->decoupled != 0 ? 1 : 0}};
+        if (adam_fuse_wanted()) fused = sgd_fused_image(A);
+        launch_adam_tick(st, a);
+        launches = 1;
+        if (fused >= 0 && A->dtype == SPARTA_F32) {
+            launch_adam_f32_frag(st, A->d_steps[0], A->n_steps[0], a, A->d_a_frag, A->d_A);
+            launches++;
+        } else if (fused >= 0) {
+            const bool bf16 = A->dtype == SPARTA_BF16;
+            launch_adam_h16(bf16, fused ? 64 : 32, A->kp16, st, A->d_upd_map[fused], A->n_steps[fused], a, (uint16_t*)A->d_A + A->upd_base[fused]);
+            launches++;
+            if (A->n_t_src > 0) { launch_update_h16_t(bf16, st, A->d_t_src, A->n_t_src, (int)A->w, W, A->d_t_A); launches++; }   // reads the W written above
+        } else {
+            launch_adam_step(st, A->nztot, a);
+            launches += 1 + launch_images_from(A, st, W);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    A->step_last_fused = fused >= 0 ? 1 : 0;
+    A->step_last_launches = launches;
+    if (dt_ms) {
+        HIP_TRY(hipEventRecord(A->ev1, st));
+        HIP_TRY(hipEventSynchronize(A->ev1));
+        HIP_TRY(hipEventElapsedTime(dt_ms, A->ev0, A->ev1));
+    }
+    return SPARTA_OK;
+}
+
+}  // namespace
+
+extern "C" int sparta_vbs_adam_step(sparta_vbs_t* A, float* W, const float* G, float* M, float* V, void* S, const sparta_adam_cfg* cfg, void* stream,
+                                    float* dt_ms) {
+    SPARTA_GUARD_BEGIN
+    return adam_step_impl(A, W, G, M, V, S, cfg, stream, dt_ms);
+    SPARTA_GUARD_END("sparta_vbs_adam_step")
+}
+
 extern "C" int sparta_vbs_step_info(const sparta_vbs_t* A, int64_t* info_out) {
     if (!A || !info_out) return sparta::fail(SPARTA_ERR_INVALID, "sparta_vbs_step_info: NULL argument");
-    info_out[0] = A->sgd_last_fused; info_out[1] = A->sgd_last_launches; info_out[2] = 0; info_out[3] = 0;
+    info_out[0] = A->step_last_fused; info_out[1] = A->step_last_launches; info_out[2] = 0; info_out[3] = 0;
     return SPARTA_OK;
 }
 

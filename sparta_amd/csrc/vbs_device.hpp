@@ -267,6 +267,10 @@ struct UpdSlice {
 static_assert(sizeof(UpdSlice) == 32, "UpdSlice must stay 32 bytes");
 // sparta_vbs_sgd_step (k_update.hip): the hyper-parameters of one step, as sparta_sgd_cfg carries them
 struct SgdCfg { float lr, momentum, weight_decay, grad_scale; };
+// sparta_vbs_adam_step (k_update.hip): sparta_adam_cfg and the three constants the host derives from it in fp32 (omb1 = 1 - beta1, omb2 = 1 - beta2,
+// dk = 1 - lr * weight_decay), and the operands of one step: W, G, M, V = nztot floats each, S = the 8-word step state
+struct AdamCfg { float lr, beta1, beta2, eps, weight_decay, grad_scale, omb1, omb2, dk; int32_t decoupled; };
+struct AdamArgs { float* W; const float* G; float* M; float* V; float* S; AdamCfg c; };
 
 // sparta_vbs_spmm_t (k_spmm_t.hip): Ct (+)= A^T X walks A by block column.  The index (pattern only, built at creation): per block column the list of
 // its blocks, in block-row order; a work item = one panel of <= 32 stored columns of one block column x its whole list.  The image the kernel reads:
@@ -447,9 +451,9 @@ struct sparta_vbs {
     void* d_upd_ws = nullptr;
     size_t d_upd_ws_bytes = 0;
     // sparta_vbs_sgd_step: stored elements the slices of each stream image hold (set at creation from the plan: an image that holds nztot of them, the only
-    // non-empty one, holds each exactly once and its kernel may own the arithmetic); what the last step did (sparta_vbs_step_info)
+    // non-empty one, holds each exactly once and its kernel may own the arithmetic); what the last step of either optimizer did (sparta_vbs_step_info)
     int64_t upd_cover[2] = {0, 0};
-    int32_t sgd_last_fused = -1, sgd_last_launches = 0;
+    int32_t step_last_fused = -1, step_last_launches = 0;
     // sparta_vbs_spmm_t (SPARTA_CREATE_TRANSPOSE handles only): the block-column index, the 16-bit image, the sources of its blocks; host-pointer calls stage X, Ct
     sparta_dev::SpmmTItem* d_t_items = nullptr;
     sparta_dev::SpmmTBlock* d_t_blocks = nullptr;
@@ -518,6 +522,11 @@ void launch_sgd_step(hipStream_t st, int64_t n, float* W, const float* G, float*
 // the new weight computed in registers, stored to W (and M) and handed on to the image
 void launch_sgd_f32_frag(hipStream_t st, StepRec* steps, int64_t n_steps, float* W, const float* G, float* M, const SgdCfg& cfg, float* a_frag, float* A_out);
 void launch_sgd_h16(bool bf16, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, float* W, const float* G, float* M, const SgdCfg& cfg, uint16_t* dst);
+// k_update.hip (sparta_vbs_adam_step): the tick advances a.S once per step; the others are the Adam forms of the three launches above and read what it wrote
+void launch_adam_tick(hipStream_t st, const AdamArgs& a);
+void launch_adam_step(hipStream_t st, int64_t n, const AdamArgs& a);
+void launch_adam_f32_frag(hipStream_t st, StepRec* steps, int64_t n_steps, const AdamArgs& a, float* a_frag, float* A_out);
+void launch_adam_h16(bool bf16, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, const AdamArgs& a, uint16_t* dst);
 // k_spmm_t.hip: grid = n_items x slabs of kSpmmTSlab columns; dtype = SPARTA_F32 / F16 / BF16
 void launch_spmm_t(int dtype, unsigned n_items, hipStream_t st, const SpmmTParams& p);
 // k_colres.hip

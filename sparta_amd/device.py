@@ -339,9 +339,51 @@ class DeviceVBS(ValuesRecord):
             self._autograd_values = (values, values._version)
         return dt.value if timed else None
 
+    def adam_step(self, values, grad, exp_avg, exp_avg_sq, state, lr=None, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, grad_scale=1.0,
+                  timed=False, stream=None):
+        """sparta_vbs_adam_step, device tensors: one AdamW (decoupled=True) / Adam with L2 weight decay (decoupled=False) step on `values` (the float32
+        master copy, updated in place) with the gradient `grad`, the moments `exp_avg` and `exp_avg_sq` (updated in place; zeros before the first step) and
+        `state`, a contiguous tensor of 8 int32 or float32 words on this device that holds the step count and the bias corrections (zeros: a fresh optimizer;
+        advanced on the device, so a captured step replays correctly) -- torch.optim.AdamW / Adam without amsgrad and maximize, grad first multiplied by
+        grad_scale -- and the handle's images written from the new values in the same pass: afterwards the handle behaves as after set_values(values).  The
+        four operands: contiguous float32 tensors of nztot elements on this device, in the layout of VBR.mab.  Stream-ordered on torch's current stream.  lr
+        and the other hyper-parameters are baked into a capture.  The version counters of `values`, `exp_avg` and `exp_avg_sq` are bumped and the handle
+        records the new version of `values`, so that the next vbs_linear forward with the same tensor skips set_values.  Needs updatable=True.  Returns kernel
+        ms if timed else None."""
+        import torch
+        if lr is None:
+            raise ValueError("lr is required")
+        for name, t in (("values", values), ("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+            if t is None or not (t.is_cuda and t.dtype == torch.float32 and t.device.index == self.device and t.is_contiguous()):
+                raise ValueError("%s must be a contiguous float32 tensor on device %d" % (name, self.device))
+            if t.numel() != self._nztot():
+                raise ValueError("%s must hold nztot = %d elements" % (name, self._nztot()))
+        if state is None or not (state.is_cuda and state.dtype in (torch.int32, torch.float32) and state.device.index == self.device
+                                 and state.is_contiguous() and state.numel() == 8):
+            raise ValueError("state must be a contiguous tensor of 8 int32 or float32 words on device %d" % self.device)
+        st = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+        cfg = _lib.AdamCfg(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(grad_scale), int(bool(decoupled)), 0)
+        dt = C.c_float(0)
+        self._values_replaced()
+        check(lib.sparta_vbs_adam_step(self.h, *(C.cast(C.c_void_p(t.data_ptr()), _f32p) for t in (values, grad, exp_avg, exp_avg_sq)),
+                                       C.c_void_p(state.data_ptr()), C.byref(cfg), C.c_void_p(st), C.byref(dt) if timed else None))
+        # the kernels wrote through the raw pointers: tell autograd, then note that the handle holds exactly this version
+        bump = getattr(torch.autograd.graph, "increment_version", None)
+        for t in (values, exp_avg, exp_avg_sq):
+            if bump is not None:
+                bump(t)
+            else:
+                with torch.no_grad():
+                    t.add_(0)
+        if torch.cuda.is_current_stream_capturing():
+            self._autograd_captured = True          # (as a captured forward: replays change the handle's values without passing through Python)
+        if not self._autograd_captured:
+            self._autograd_values = (values, values._version)
+        return dt.value if timed else None
+
     def step_info(self):
-        """sparta_vbs_step_info: {"fused": 1 the last sgd_step did its arithmetic inside an image kernel / 0 it ran the elementwise kernel and then the
-        set_values launches / -1 no step yet, "launches": kernel launches of that step}"""
+        """sparta_vbs_step_info: {"fused": 1 the last sgd_step / adam_step did its arithmetic inside an image kernel / 0 it ran the elementwise kernel and then
+        the set_values launches / -1 no step yet, "launches": kernel launches of that step (an Adam step counts its tick)}"""
         out = (C.c_int64 * 4)()
         check(lib.sparta_vbs_step_info(self.h, out))
         return {"fused": int(out[0]), "launches": int(out[1])}
