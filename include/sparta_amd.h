@@ -480,6 +480,73 @@ int sparta_vbs_adam_step(sparta_vbs_t* A, float* W, const float* G, float* M, fl
  * the two-pass form, -1 if no step has run yet; kernel launches of that step (an Adam step counts its tick); 0; 0}. */
 int sparta_vbs_step_info(const sparta_vbs_t* A, int64_t* info_out);
 
+/* Global-norm gradient clipping and loss scaling with skip-on-overflow, decided on the device: between backward and step nothing comes back to the
+ * host, and the sequence [sparta_grad_stats ..., sparta_grad_ctl_finish, sparta_vbs_*_step_ctl ...] is kernel launches only, capturable into a hipGraph
+ * from the first call; a replay reads the gradients and the record afresh (one whose gradient has become non-finite skips).
+ * R, the control record: SPARTA_GRAD_CTL_BYTES of caller-owned device memory on an 8-byte boundary, zero-filled for a fresh run (checkpointing words
+ * 4, 5 and 9 is the caller's copy).  The first 64 bytes, as 32-bit words:
+ *     0-1  fp64   ssq: sum of squares of the FINITE gradient elements folded in so far
+ *     2    int32  nonfinite: number of Inf / NaN elements folded in, saturating at 2^31 - 1
+ *     3           zero
+ *     4    fp32   loss_scale (a zero word means 1.0f)          7  fp32   coef the steps multiply G by
+ *     5    int32  growth_tracker                               8  int32  skip (0 / 1)
+ *     6    fp32   norm of the last finish (unscaled)           9  int32  skipped_total
+ *     10-15       written as zero by sparta_grad_ctl_finish
+ * The rest is scratch of the reduction (the partial sums of its largest grid) with unspecified content: no call allocates.
+ *
+ * sparta_grad_stats folds the n floats of G (device memory, any 4-byte boundary; NULL allowed when n == 0) into words 0-2: accumulate = 0 overwrites
+ * them (also with n == 0: zeros), 1 adds to them.  Handle-free, as sparta_pack_blocks: a global norm spans the dense parameters of a model too.  Each
+ * finite element is widened to fp64 and squared there (exact), and the squares are summed in fp64; an Inf or NaN is counted and adds nothing to ssq.
+ * The grid is a function of n alone -- one workgroup per SPARTA_GRAD_STATS_CHUNK elements, at most SPARTA_GRAD_STATS_MAX_GRID, which walk the chunks
+ * round-robin -- the partials are summed in a fixed order by a second, one-workgroup launch, and no floating-point atomic is used: the three words are
+ * bit-identical from run to run and between an eager call and a replay (for the same n and the same alignment of G modulo 16 bytes), and ssq differs from
+ * the exact sum of the squares by at most n * 2^-53 * ssq.  Kernel launches only (on the current device); *dt_ms (may be NULL) covers them and
+ * synchronises (SPARTA_ERR_UNSUPPORTED while the stream is being captured).  SPARTA_ERR_INVALID for a NULL or misaligned R, a NULL G with n > 0, n < 0.
+ *
+ * sparta_grad_ctl_finish turns the statistics into the coefficient and the skip flag and moves the loss scale -- clip_grad_norm_'s coefficient and
+ * GradScaler.update()'s rule -- in a one-wave kernel.  Every fp32 operation is rounded once, in this order, never contracted into an FMA; division and
+ * square root are IEEE correctly rounded:
+ *     s = loss_scale (1.0f if the word is 0);  inv = 1.0f / s
+ *     bad  = nonfinite != 0
+ *     root = (float) sqrt(ssq)                  -- fp64 square root, then rounded to fp32; may be +Inf
+ *     norm = root * inv;                        if (!isfinite(norm)) bad = 1
+ *     coef = inv
+ *     if (!bad && max_norm > 0) { c = max_norm / (norm + 1e-6f);  if (c < 1.0f) coef = inv * c; }
+ *     if (bad) coef = 0.0f
+ *     skip = bad;  skipped_total += skip
+ *     if (growth_interval > 0) {
+ *         if (skip) { s = s * backoff_factor;  growth_tracker = 0; }
+ *         else { growth_tracker += 1;
+ *                if (growth_tracker >= growth_interval) { s2 = s * growth_factor;  if (isfinite(s2)) s = s2;  growth_tracker = 0; } }
+ *     }
+ *     write loss_scale = s, growth_tracker, norm, coef, skip, skipped_total; words 10..15 = 0
+ * coef is taken with the scale the gradients were produced under; the scale moves afterwards.  max_norm = 0: no clipping; growth_interval = 0: the loss
+ * scale stays.  SPARTA_ERR_INVALID, with nothing launched, for a NULL or misaligned R, a NULL cfg, max_norm negative or NaN, growth_interval < 0, with
+ * growth_interval > 0 a growth_factor < 1 or a backoff_factor outside (0, 1], any non-zero reserved word.
+ *
+ * sparta_vbs_sgd_step_ctl / sparta_vbs_adam_step_ctl are sparta_vbs_sgd_step / sparta_vbs_adam_step with the record R in front of `stream`.  R == NULL
+ * is the plain entry exactly (which calls these with NULL).  With R != NULL the kernels of the step read coef and skip from R on the device, at every
+ * launch and replay:
+ *     per element, after the optional g = g * grad_scale:   g = g * coef     (always, one rounding; the rest of the pinned order is unchanged)
+ * so a float32 restatement given the coef read back from R reproduces W, M, V and S bit for bit.  With skip != 0: W, M, V and S keep their bits (the
+ * Adam step count does not advance), and every image of the handle is still written, from W: afterwards the handle behaves as after
+ * sparta_vbs_set_values(A, W), whatever values it held before.  The flag selects -- G is not read, nothing is multiplied by zero -- so nothing
+ * non-finite in G reaches W, M, V or an image.  Both forms of a step honour it; the routing rule, SPARTA_SGD_FUSE / SPARTA_ADAM_FUSE and
+ * sparta_vbs_step_info are those of the plain entries, launch counts included.  A misaligned R: SPARTA_ERR_INVALID with nothing launched. */
+#define SPARTA_GRAD_CTL_BYTES 16448
+#define SPARTA_GRAD_STATS_CHUNK 4096
+#define SPARTA_GRAD_STATS_MAX_GRID 1024
+typedef struct sparta_grad_ctl_cfg {
+    float max_norm, growth_factor, backoff_factor;
+    int32_t growth_interval;
+    int32_t reserved[4];
+} sparta_grad_ctl_cfg;
+int sparta_grad_stats(const float* G, int64_t n, void* R, int32_t accumulate, void* stream, float* dt_ms);
+int sparta_grad_ctl_finish(void* R, const sparta_grad_ctl_cfg* cfg, void* stream);
+int sparta_vbs_sgd_step_ctl(sparta_vbs_t* A, float* W, const float* G, float* M, const sparta_sgd_cfg* cfg, const void* R, void* stream, float* dt_ms);
+int sparta_vbs_adam_step_ctl(sparta_vbs_t* A, float* W, const float* G, float* M, float* V, void* S,
+                             const sparta_adam_cfg* cfg, const void* R, void* stream, float* dt_ms);
+
 /* Ct (+)= A^T * X on the stored blocks of A: the gradient of the dense operand of C = A * B (X = dC, Ct = dB), on the handle itself, so that
  * it follows sparta_vbs_set_values in stream order.  Only handles made with SPARTA_CREATE_TRANSPOSE take the call; every other handle
  * (flags without the bit, sparta_vbs_create, _create_range, _create_from_csr, _create_transposed): SPARTA_ERR_UNSUPPORTED.

@@ -25,6 +25,9 @@ PTR_HOST, PTR_DEVICE = 0, 1
 SPMM_MFMA, SPMM_EXACT = 0, 1
 CREATE_UPDATABLE = 1
 CREATE_TRANSPOSE = 2
+# the control record of sparta_grad_stats / sparta_grad_ctl_finish: its size in bytes, and the launch rule of the reduction (one workgroup per
+# GRAD_STATS_CHUNK elements, at most GRAD_STATS_MAX_GRID)
+GRAD_CTL_BYTES, GRAD_STATS_CHUNK, GRAD_STATS_MAX_GRID = 16448, 4096, 1024
 FMT_EL, FMT_MTX = 0, 1
 IO_COMPAT, IO_STRICT = 0, 1
 
@@ -44,6 +47,7 @@ SYMBOLS = [
     "sparta_vbs_create_range_ex", "sparta_vbs_set_values", "sparta_vbs_flags", "sparta_frag_positions",
     "sparta_vbs_spmm_t", "sparta_spmm_t_host_check",
     "sparta_vbs_sgd_step", "sparta_vbs_step_info", "sparta_vbs_adam_step",
+    "sparta_grad_stats", "sparta_grad_ctl_finish", "sparta_vbs_sgd_step_ctl", "sparta_vbs_adam_step_ctl",
 ]
 
 
@@ -97,6 +101,12 @@ class AdamCfg(C.Structure):
                 ("grad_scale", C.c_float), ("decoupled", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GradCtlCfg(C.Structure):
+    """sparta_grad_ctl_cfg"""
+    _fields_ = [("max_norm", C.c_float), ("growth_factor", C.c_float), ("backoff_factor", C.c_float), ("growth_interval", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
 class SpartaError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("sparta_amd error %d: %s" % (code, msg))
@@ -137,6 +147,10 @@ def _load():
     L.sparta_vbs_sgd_step.argtypes = [vp, f32p, f32p, f32p, C.POINTER(SgdCfg), vp, f32p]
     L.sparta_vbs_adam_step.argtypes = [vp, f32p, f32p, f32p, f32p, vp, C.POINTER(AdamCfg), vp, f32p]
     L.sparta_vbs_step_info.argtypes = [vp, i64p]
+    L.sparta_grad_stats.argtypes = [f32p, C.c_int64, vp, C.c_int32, vp, f32p]
+    L.sparta_grad_ctl_finish.argtypes = [vp, C.POINTER(GradCtlCfg), vp]
+    L.sparta_vbs_sgd_step_ctl.argtypes = [vp, f32p, f32p, f32p, C.POINTER(SgdCfg), vp, vp, f32p]
+    L.sparta_vbs_adam_step_ctl.argtypes = [vp, f32p, f32p, f32p, f32p, vp, C.POINTER(AdamCfg), vp, vp, f32p]
     L.sparta_vbs_flags.argtypes = [vp, i32p]
     L.sparta_vbs_spmm_t.argtypes = [vp, vp, C.c_int64, C.c_int32, f32p, C.c_int64, C.c_int32, C.c_int32, vp, f32p]
     L.sparta_spmm_t_host_check.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, i64p, i64p, i64p, f32p, C.c_int64, C.c_int64, f32p, C.POINTER(C.c_double), i64p]

@@ -11,6 +11,8 @@
 //   vbs_sgd_step_kernel         the same arithmetic, elementwise over nztot floats, runs in front of the set_values launches
 // sparta_vbs_adam_step is a third value source, AdamStep (W, G, M, V and the device-resident step state S): vbs_adam_f32_frag_kernel, vbs_adam_h16_kernel and the
 // elementwise vbs_adam_step_kernel, behind the one-wave vbs_adam_tick_kernel that advances S once per step.
+// sparta_vbs_sgd_step_ctl / sparta_vbs_adam_step_ctl reach the same kernels with a control record (k_gradctl.hip) in the value source: its coef multiplies g, its
+// skip flag turns the step into sparta_vbs_set_values(A, W) -- W, M, V, S keep their bits, every image is written from W.
 // Every kernel writes exactly the elements creation wrote (the slices behind the end of an image keep what creation left there) and reads mab
 // only where the plan says a stored element is: nothing is read past mab + nztot.  Offsets are 64-bit throughout.
 #include "vbs_kernel_common.hpp"
@@ -22,9 +24,11 @@ constexpr int kUpdMaxGrid = 65536;      // grid cap, as launch_f32_legacy_from_f
 
 // One element of torch.optim.SGD (dampening 0, no Nesterov), every operation rounded once to fp32 in the order include/sparta_amd.h pins: no contraction
 // into FMAs, so a float32 restatement on the host reproduces W and M bit for bit.  m is read and written only when momentum != 0.
-__device__ __forceinline__ float sgd_element(const SgdCfg& c, float w, float g, float& m) {
+// ctl: the step runs under a control record (sparta_vbs_sgd_step_ctl with R != NULL), whose coef then multiplies g, whatever its value.
+__device__ __forceinline__ float sgd_element(const SgdCfg& c, bool ctl, float coef, float w, float g, float& m) {
 #pragma clang fp contract(off)
     if (c.grad_scale != 1.0f) g = g * c.grad_scale;
+    if (ctl) g = g * coef;
     if (c.weight_decay != 0.0f) g = g + c.weight_decay * w;
     if (c.momentum != 0.0f) { m = c.momentum * m + g; g = m; }
     return w - c.lr * g;
@@ -33,33 +37,47 @@ __device__ __forceinline__ float sgd_element(const SgdCfg& c, float w, float g, 
 // The value source of the image kernels of sparta_vbs_sgd_step.  step<N> updates the N elements i0, i0 + stride, ... of W (and M) and returns the new weights:
 // ALL loads first, then the arithmetic, then the stores, so that the N (2 N, 3 N) loads of a lane are in flight together as the N loads of the set_values
 // kernels are -- element by element (load, wait, store, load, ...) the image kernels ran N dependent round trips to memory per lane.
+// R != nullptr: coef and skip are read from the control record at every launch (a replay reads them afresh).  Under skip the values handed on are W as it
+// stands -- G, M are not even loaded, nothing is stored: the image is written from W and nothing non-finite can come near it.
 struct SgdStep {
     float* __restrict__ W; const float* __restrict__ G; float* __restrict__ M;
     SgdCfg c;
+    const uint32_t* __restrict__ R;
+    __device__ __forceinline__ float coef() const { return R != nullptr ? __uint_as_float(R[kGradCtlCoef]) : 1.0f; }
+    __device__ __forceinline__ bool skip() const { return R != nullptr && R[kGradCtlSkip] != 0u; }
     template <int N>
     __device__ __forceinline__ void step(int64_t i0, int64_t stride, float (&x)[N]) const {
-        const bool mom = c.momentum != 0.0f;
+        if (skip()) {
+#pragma unroll
+            for (int e = 0; e < N; e++) x[e] = W[i0 + e * stride];
+            return;
+        }
+        const bool mom = c.momentum != 0.0f, ctl = R != nullptr;
+        const float cf = coef();
         float w[N], g[N], m[N];
 #pragma unroll
         for (int e = 0; e < N; e++) { w[e] = W[i0 + e * stride]; g[e] = G[i0 + e * stride]; m[e] = mom ? M[i0 + e * stride] : 0.0f; }
 #pragma unroll
-        for (int e = 0; e < N; e++) x[e] = sgd_element(c, w[e], g[e], m[e]);
+        for (int e = 0; e < N; e++) x[e] = sgd_element(c, ctl, cf, w[e], g[e], m[e]);
 #pragma unroll
         for (int e = 0; e < N; e++) { W[i0 + e * stride] = x[e]; if (mom) M[i0 + e * stride] = m[e]; }
     }
 };
 
 // The two-pass form of sparta_vbs_sgd_step: W, G, M are the caller's arrays (any 4-byte boundary), 16 bytes per lane and access, the last n % 4 one by one.
+// Under skip it does nothing: the set_values launches behind it write the images from the W that stands.
 __global__ __launch_bounds__(kThreads) void vbs_sgd_step_kernel(int64_t n, SgdStep s) {
+    if (s.skip()) return;
     const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * kThreads;
-    const bool mom = s.c.momentum != 0.0f;
+    const bool mom = s.c.momentum != 0.0f, ctl = s.R != nullptr;
+    const float cf = s.coef();
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += stride) {
         f32x4 w = *reinterpret_cast<const f32x4u*>(s.W + 4 * i);
         const f32x4 g = *reinterpret_cast<const f32x4u*>(s.G + 4 * i);
         f32x4 m = {0.0f, 0.0f, 0.0f, 0.0f};
         if (mom) m = *reinterpret_cast<const f32x4u*>(s.M + 4 * i);
 #pragma unroll
-        for (int e = 0; e < 4; e++) { float me = m[e]; w[e] = sgd_element(s.c, w[e], g[e], me); m[e] = me; }
+        for (int e = 0; e < 4; e++) { float me = m[e]; w[e] = sgd_element(s.c, ctl, cf, w[e], g[e], me); m[e] = me; }
         if (mom) *reinterpret_cast<f32x4u*>(s.M + 4 * i) = m;
         *reinterpret_cast<f32x4u*>(s.W + 4 * i) = w;
     }
@@ -80,9 +98,10 @@ __device__ __forceinline__ void adam_tick(float beta1, float beta2, float lr, in
 }
 
 // One wave, one lane at work: S[0] = t, S[1], S[2] = the running products, S[3] = step_size, S[4] = d, S[5..7] = 0 (4-byte accesses: S may sit on any
-// 4-byte boundary).  The element kernels behind it in the stream read S[3] and S[4].
-__global__ __launch_bounds__(64) void vbs_adam_tick_kernel(uint32_t* S, float beta1, float beta2, float lr) {
+// 4-byte boundary).  The element kernels behind it in the stream read S[3] and S[4].  R: the control record or nullptr; a skipped step leaves S as it is.
+__global__ __launch_bounds__(64) void vbs_adam_tick_kernel(uint32_t* S, float beta1, float beta2, float lr, const uint32_t* R) {
     if (threadIdx.x != 0) return;
+    if (R != nullptr && R[kGradCtlSkip] != 0u) return;
     int32_t t = (int32_t)S[0];
     float p1 = __uint_as_float(S[1]), p2 = __uint_as_float(S[2]), step_size, d;
     adam_tick(beta1, beta2, lr, t, p1, p2, step_size, d);
@@ -92,9 +111,10 @@ __global__ __launch_bounds__(64) void vbs_adam_tick_kernel(uint32_t* S, float be
 
 // One element of torch.optim.AdamW (decoupled) / torch.optim.Adam with L2 weight decay (no amsgrad, no maximize) in the order include/sparta_amd.h pins, one
 // rounding per operation, no contraction: a float32 restatement on the host reproduces W, M and V bit for bit.
-__device__ __forceinline__ float adam_element(const AdamCfg& c, float step_size, float d, float w, float g, float& m, float& v) {
+__device__ __forceinline__ float adam_element(const AdamCfg& c, bool ctl, float coef, float step_size, float d, float w, float g, float& m, float& v) {
 #pragma clang fp contract(off)
     if (c.grad_scale != 1.0f) g = g * c.grad_scale;
+    if (ctl) g = g * coef;                     // (as sgd_element)
     if (c.weight_decay != 0.0f) {
         if (c.decoupled) w = w * c.dk;
         else g = g + c.weight_decay * w;
@@ -106,17 +126,28 @@ __device__ __forceinline__ float adam_element(const AdamCfg& c, float step_size,
 }
 
 // The interface of SgdStep: all 4 N loads of a lane first, then the arithmetic, then the 3 N stores.  step_size and d are what the tick wrote for this step.
+// R as in SgdStep.
 struct AdamStep {
     float* __restrict__ W; const float* __restrict__ G; float* __restrict__ M; float* __restrict__ V; const float* __restrict__ S;
     AdamCfg c;
+    const uint32_t* __restrict__ R;
+    __device__ __forceinline__ float coef() const { return R != nullptr ? __uint_as_float(R[kGradCtlCoef]) : 1.0f; }
+    __device__ __forceinline__ bool skip() const { return R != nullptr && R[kGradCtlSkip] != 0u; }
     template <int N>
     __device__ __forceinline__ void step(int64_t i0, int64_t stride, float (&x)[N]) const {
+        if (skip()) {
+#pragma unroll
+            for (int e = 0; e < N; e++) x[e] = W[i0 + e * stride];
+            return;
+        }
+        const bool ctl = R != nullptr;
+        const float cf = coef();
         const float step_size = S[3], d = S[4];
         float w[N], g[N], m[N], v[N];
 #pragma unroll
         for (int e = 0; e < N; e++) { w[e] = W[i0 + e * stride]; g[e] = G[i0 + e * stride]; m[e] = M[i0 + e * stride]; v[e] = V[i0 + e * stride]; }
 #pragma unroll
-        for (int e = 0; e < N; e++) x[e] = adam_element(c, step_size, d, w[e], g[e], m[e], v[e]);
+        for (int e = 0; e < N; e++) x[e] = adam_element(c, ctl, cf, step_size, d, w[e], g[e], m[e], v[e]);
 #pragma unroll
         for (int e = 0; e < N; e++) { W[i0 + e * stride] = x[e]; M[i0 + e * stride] = m[e]; V[i0 + e * stride] = v[e]; }
     }
@@ -124,7 +155,10 @@ struct AdamStep {
 
 // The two-pass form of sparta_vbs_adam_step, shaped as vbs_sgd_step_kernel: 16 bytes per lane and access, the last n % 4 one by one.
 __global__ __launch_bounds__(kThreads) void vbs_adam_step_kernel(int64_t n, AdamStep s) {
+    if (s.skip()) return;
     const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * kThreads;
+    const bool ctl = s.R != nullptr;
+    const float cf = s.coef();
     const float step_size = s.S[3], d = s.S[4];
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += stride) {
         f32x4 w = *reinterpret_cast<const f32x4u*>(s.W + 4 * i);
@@ -132,7 +166,7 @@ __global__ __launch_bounds__(kThreads) void vbs_adam_step_kernel(int64_t n, Adam
         f32x4 m = *reinterpret_cast<const f32x4u*>(s.M + 4 * i);
         f32x4 v = *reinterpret_cast<const f32x4u*>(s.V + 4 * i);
 #pragma unroll
-        for (int e = 0; e < 4; e++) { float me = m[e], ve = v[e]; w[e] = adam_element(s.c, step_size, d, w[e], g[e], me, ve); m[e] = me; v[e] = ve; }
+        for (int e = 0; e < 4; e++) { float me = m[e], ve = v[e]; w[e] = adam_element(s.c, ctl, cf, step_size, d, w[e], g[e], me, ve); m[e] = me; v[e] = ve; }
         *reinterpret_cast<f32x4u*>(s.M + 4 * i) = m;
         *reinterpret_cast<f32x4u*>(s.V + 4 * i) = v;
         *reinterpret_cast<f32x4u*>(s.W + 4 * i) = w;
@@ -224,7 +258,7 @@ void launch_adam_h16_t(int tms, int kp, hipStream_t st, const UpdSlice* map, int
     else hipLaunchKernelGGL((vbs_adam_h16_kernel<BF16, 64, 64>), dim3(upd_grid(n_slices * 2)), block, 0, st, map, n_slices, vs, dst);
 }
 
-SgdStep sgd_source(float* W, const float* G, float* M, const SgdCfg& cfg) { return SgdStep{W, G, cfg.momentum != 0.0f ? M : nullptr, cfg}; }
+SgdStep sgd_source(float* W, const float* G, float* M, const SgdCfg& cfg, const uint32_t* R) { return SgdStep{W, G, cfg.momentum != 0.0f ? M : nullptr, cfg, R}; }
 
 }  // namespace
 
@@ -253,43 +287,43 @@ void launch_update_h16_t(bool bf16, hipStream_t st, const SpmmTSrc* src, int64_t
 
 
 // ---- sparta_vbs_sgd_step ------------------------------------------------------------------------------------------------------------------
-void launch_sgd_step(hipStream_t st, int64_t n, float* W, const float* G, float* M, const SgdCfg& cfg) {
+void launch_sgd_step(hipStream_t st, int64_t n, float* W, const float* G, float* M, const SgdCfg& cfg, const uint32_t* R) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(vbs_sgd_step_kernel, dim3(upd_grid((n / 4 + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, n, sgd_source(W, G, M, cfg));
+    hipLaunchKernelGGL(vbs_sgd_step_kernel, dim3(upd_grid((n / 4 + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, n, sgd_source(W, G, M, cfg, R));
 }
 
-void launch_sgd_f32_frag(hipStream_t st, StepRec* steps, int64_t n_steps, float* W, const float* G, float* M, const SgdCfg& cfg, float* a_frag, float* A_out) {
+void launch_sgd_f32_frag(hipStream_t st, StepRec* steps, int64_t n_steps, float* W, const float* G, float* M, const SgdCfg& cfg, const uint32_t* R, float* a_frag, float* A_out) {
     if (n_steps <= 0) return;
     hipLaunchKernelGGL(vbs_sgd_f32_frag_kernel, dim3(upd_grid((n_steps + kThreads / 64 - 1) / (kThreads / 64))), dim3(kThreads), 0, st, steps, n_steps,
-                       sgd_source(W, G, M, cfg), a_frag, A_out);
+                       sgd_source(W, G, M, cfg, R), a_frag, A_out);
 }
 
-void launch_sgd_h16(bool bf16, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, float* W, const float* G, float* M, const SgdCfg& cfg, uint16_t* dst) {
+void launch_sgd_h16(bool bf16, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, float* W, const float* G, float* M, const SgdCfg& cfg, const uint32_t* R, uint16_t* dst) {
     if (n_slices <= 0) return;
-    if (bf16) launch_sgd_h16_t<true>(tms, kp, st, map, n_slices, sgd_source(W, G, M, cfg), dst);
-    else launch_sgd_h16_t<false>(tms, kp, st, map, n_slices, sgd_source(W, G, M, cfg), dst);
+    if (bf16) launch_sgd_h16_t<true>(tms, kp, st, map, n_slices, sgd_source(W, G, M, cfg, R), dst);
+    else launch_sgd_h16_t<false>(tms, kp, st, map, n_slices, sgd_source(W, G, M, cfg, R), dst);
 }
 
 
 // ---- sparta_vbs_adam_step -----------------------------------------------------------------------------------------------------------------
 void launch_adam_tick(hipStream_t st, const AdamArgs& a) {
-    hipLaunchKernelGGL(vbs_adam_tick_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<uint32_t*>(a.S), a.c.beta1, a.c.beta2, a.c.lr);
+    hipLaunchKernelGGL(vbs_adam_tick_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<uint32_t*>(a.S), a.c.beta1, a.c.beta2, a.c.lr, a.R);
 }
 
 void launch_adam_step(hipStream_t st, int64_t n, const AdamArgs& a) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(vbs_adam_step_kernel, dim3(upd_grid((n / 4 + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, n, AdamStep{a.W, a.G, a.M, a.V, a.S, a.c});
+    hipLaunchKernelGGL(vbs_adam_step_kernel, dim3(upd_grid((n / 4 + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, n, AdamStep{a.W, a.G, a.M, a.V, a.S, a.c, a.R});
 }
 
 void launch_adam_f32_frag(hipStream_t st, StepRec* steps, int64_t n_steps, const AdamArgs& a, float* a_frag, float* A_out) {
     if (n_steps <= 0) return;
     hipLaunchKernelGGL(vbs_adam_f32_frag_kernel, dim3(upd_grid((n_steps + kThreads / 64 - 1) / (kThreads / 64))), dim3(kThreads), 0, st, steps, n_steps,
-                       AdamStep{a.W, a.G, a.M, a.V, a.S, a.c}, a_frag, A_out);
+                       AdamStep{a.W, a.G, a.M, a.V, a.S, a.c, a.R}, a_frag, A_out);
 }
 
 void launch_adam_h16(bool bf16, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, const AdamArgs& a, uint16_t* dst) {
     if (n_slices <= 0) return;
-    const AdamStep vs{a.W, a.G, a.M, a.V, a.S, a.c};
+    const AdamStep vs{a.W, a.G, a.M, a.V, a.S, a.c, a.R};
     if (bf16) launch_adam_h16_t<true>(tms, kp, st, map, n_slices, vs, dst);
     else launch_adam_h16_t<false>(tms, kp, st, map, n_slices, vs, dst);
 }

@@ -2421,35 +2421,38 @@ bool sgd_fuse_wanted() {
     return !e || atoi(e) != 0;
 }
 
-int sgd_step_impl(sparta_vbs_t* A, float* W, const float* G, float* M, const sparta_sgd_cfg* cfg, void* stream, float* dt_ms) {
-    using sparta::fail;
-    if (!A) return fail(SPARTA_ERR_INVALID, "sparta_vbs_sgd_step: NULL handle");
-    if (A->nztot > 0 && (!W || !G || !cfg)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_sgd_step: W, G or cfg is NULL");
-    if (cfg && cfg->momentum != 0.0f && !M) return fail(SPARTA_ERR_INVALID, "sparta_vbs_sgd_step: M is NULL with momentum != 0");
+// entry: the name the messages carry.  R: the control record of sparta_vbs_sgd_step_ctl, or NULL (the step as it always was)
+int sgd_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G, float* M, const sparta_sgd_cfg* cfg, const void* R, void* stream, float* dt_ms) {
+    const auto fail = [entry](int code, const char* what) { return sparta::fail(code, std::string(entry) + what); };
+    if (!A) return fail(SPARTA_ERR_INVALID, ": NULL handle");
+    if (A->nztot > 0 && (!W || !G || !cfg)) return fail(SPARTA_ERR_INVALID, ": W, G or cfg is NULL");
+    if (cfg && cfg->momentum != 0.0f && !M) return fail(SPARTA_ERR_INVALID, ": M is NULL with momentum != 0");
     if (!(A->create_flags & SPARTA_CREATE_UPDATABLE))
-        return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_sgd_step: the handle was not made with SPARTA_CREATE_UPDATABLE (sparta_vbs_create_range_ex; handles of "
+        return fail(SPARTA_ERR_UNSUPPORTED, ": the handle was not made with SPARTA_CREATE_UPDATABLE (sparta_vbs_create_range_ex; handles of "
                                             "sparta_vbs_create_from_csr and sparta_vbs_create_transposed cannot take new values)");
+    if ((uintptr_t)R % 8 != 0) return fail(SPARTA_ERR_INVALID, ": the control record R must be 8-byte aligned");
     DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, "sparta_vbs_sgd_step: hipSetDevice failed");
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, ": hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
     const CaptureScope capture(st, true);
-    if (g_capturing && dt_ms) return capture_refusal("time the step (dt_ms != NULL synchronises)", "sparta_vbs_sgd_step");
+    if (g_capturing && dt_ms) return capture_refusal("time the step (dt_ms != NULL synchronises)", entry);
     if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
     int launches = 0;
     int fused = -1;
     if (A->nztot > 0) {
         const SgdCfg c{cfg->lr, cfg->momentum, cfg->weight_decay, cfg->grad_scale};
+        const uint32_t* ctl = (const uint32_t*)R;
         if (sgd_fuse_wanted()) fused = sgd_fused_image(A);
         if (fused >= 0 && A->dtype == SPARTA_F32) {
-            launch_sgd_f32_frag(st, A->d_steps[0], A->n_steps[0], W, G, M, c, A->d_a_frag, A->d_A);
+            launch_sgd_f32_frag(st, A->d_steps[0], A->n_steps[0], W, G, M, c, ctl, A->d_a_frag, A->d_A);
             launches = 1;
         } else if (fused >= 0) {
             const bool bf16 = A->dtype == SPARTA_BF16;
-            launch_sgd_h16(bf16, fused ? 64 : 32, A->kp16, st, A->d_upd_map[fused], A->n_steps[fused], W, G, M, c, (uint16_t*)A->d_A + A->upd_base[fused]);
+            launch_sgd_h16(bf16, fused ? 64 : 32, A->kp16, st, A->d_upd_map[fused], A->n_steps[fused], W, G, M, c, ctl, (uint16_t*)A->d_A + A->upd_base[fused]);
             launches = 1;
             if (A->n_t_src > 0) { launch_update_h16_t(bf16, st, A->d_t_src, A->n_t_src, (int)A->w, W, A->d_t_A); launches++; }   // reads the W written above
         } else {
-            launch_sgd_step(st, A->nztot, W, G, M, c);
+            launch_sgd_step(st, A->nztot, W, G, M, c, ctl);
             launches = 1 + launch_images_from(A, st, W);
         }
         HIP_TRY(hipGetLastError());
@@ -2468,8 +2471,15 @@ int sgd_step_impl(sparta_vbs_t* A, float* W, const float* G, float* M, const spa
 
 extern "C" int sparta_vbs_sgd_step(sparta_vbs_t* A, float* W, const float* G, float* M, const sparta_sgd_cfg* cfg, void* stream, float* dt_ms) {
     SPARTA_GUARD_BEGIN
-    return sgd_step_impl(A, W, G, M, cfg, stream, dt_ms);
+    return sgd_step_impl("sparta_vbs_sgd_step", A, W, G, M, cfg, nullptr, stream, dt_ms);
     SPARTA_GUARD_END("sparta_vbs_sgd_step")
+}
+
+extern "C" int sparta_vbs_sgd_step_ctl(sparta_vbs_t* A, float* W, const float* G, float* M, const sparta_sgd_cfg* cfg, const void* R, void* stream,
+                                       float* dt_ms) {
+    SPARTA_GUARD_BEGIN
+    return sgd_step_impl("sparta_vbs_sgd_step_ctl", A, W, G, M, cfg, R, stream, dt_ms);
+    SPARTA_GUARD_END("sparta_vbs_sgd_step_ctl")
 }
 
 // ---- sparta_vbs_adam_step (k_update.hip) --------------------------------------------------------------------------------------------------
@@ -2483,24 +2493,26 @@ bool adam_fuse_wanted() {
     return !e || atoi(e) != 0;
 }
 
-int adam_step_impl(sparta_vbs_t* A, float* W, const float* G, float* M, float* V, void* S, const sparta_adam_cfg* cfg, void* stream, float* dt_ms) {
-    using sparta::fail;
-    if (!A) return fail(SPARTA_ERR_INVALID, "sparta_vbs_adam_step: NULL handle");
-    if (A->nztot > 0 && (!W || !G || !M || !V || !S || !cfg)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_adam_step: W, G, M, V, S or cfg is NULL");
+int adam_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G, float* M, float* V, void* S, const sparta_adam_cfg* cfg, const void* R, void* stream,
+                   float* dt_ms) {
+    const auto fail = [entry](int code, const char* what) { return sparta::fail(code, std::string(entry) + what); };
+    if (!A) return fail(SPARTA_ERR_INVALID, ": NULL handle");
+    if (A->nztot > 0 && (!W || !G || !M || !V || !S || !cfg)) return fail(SPARTA_ERR_INVALID, ": W, G, M, V, S or cfg is NULL");
     if (cfg) {
         if (!(cfg->beta1 >= 0.0f && cfg->beta1 < 1.0f) || !(cfg->beta2 >= 0.0f && cfg->beta2 < 1.0f))
-            return fail(SPARTA_ERR_INVALID, "sparta_vbs_adam_step: beta1 and beta2 must lie in [0, 1)");
-        if (!(cfg->eps > 0.0f)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_adam_step: eps must be > 0");
-        if (cfg->reserved != 0) return fail(SPARTA_ERR_INVALID, "sparta_vbs_adam_step: cfg->reserved must be 0");
+            return fail(SPARTA_ERR_INVALID, ": beta1 and beta2 must lie in [0, 1)");
+        if (!(cfg->eps > 0.0f)) return fail(SPARTA_ERR_INVALID, ": eps must be > 0");
+        if (cfg->reserved != 0) return fail(SPARTA_ERR_INVALID, ": cfg->reserved must be 0");
     }
     if (!(A->create_flags & SPARTA_CREATE_UPDATABLE))
-        return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_adam_step: the handle was not made with SPARTA_CREATE_UPDATABLE (sparta_vbs_create_range_ex; handles of "
+        return fail(SPARTA_ERR_UNSUPPORTED, ": the handle was not made with SPARTA_CREATE_UPDATABLE (sparta_vbs_create_range_ex; handles of "
                                             "sparta_vbs_create_from_csr and sparta_vbs_create_transposed cannot take new values)");
+    if ((uintptr_t)R % 8 != 0) return fail(SPARTA_ERR_INVALID, ": the control record R must be 8-byte aligned");
     DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, "sparta_vbs_adam_step: hipSetDevice failed");
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, ": hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
     const CaptureScope capture(st, true);
-    if (g_capturing && dt_ms) return capture_refusal("time the step (dt_ms != NULL synchronises)", "sparta_vbs_adam_step");
+    if (g_capturing && dt_ms) return capture_refusal("time the step (dt_ms != NULL synchronises)", entry);
     if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
     int launches = 0;
     int fused = -1;
@@ -2509,7 +2521,7 @@ int adam_step_impl(sparta_vbs_t* A, float* W, const float* G, float* M, float* V
         volatile float omb1 = 1.0f - cfg->beta1, omb2 = 1.0f - cfg->beta2, lr_wd = cfg->lr * cfg->weight_decay;
         volatile float dk = 1.0f - lr_wd;
         const AdamArgs a{W, G, M, V, (float*)S,
-                         AdamCfg{cfg->lr, cfg->beta1, cfg->beta2, cfg->eps, cfg->weight_decay, cfg->grad_scale, omb1, omb2, dk, cfg->decoupled != 0 ? 1 : 0}};
+                         AdamCfg{cfg->lr, cfg->beta1, cfg->beta2, cfg->eps, cfg->weight_decay, cfg->grad_scale, omb1, omb2, dk, cfg->decoupled != 0 ? 1 : 0}, (const uint32_t*)R};
         if (adam_fuse_wanted()) fused = sgd_fused_image(A);
         launch_adam_tick(st, a);
         launches = 1;
@@ -2542,8 +2554,66 @@ int adam_step_impl(sparta_vbs_t* A, float* W, const float* G, float* M, float* V
 extern "C" int sparta_vbs_adam_step(sparta_vbs_t* A, float* W, const float* G, float* M, float* V, void* S, const sparta_adam_cfg* cfg, void* stream,
                                     float* dt_ms) {
     SPARTA_GUARD_BEGIN
-    return adam_step_impl(A, W, G, M, V, S, cfg, stream, dt_ms);
+    return adam_step_impl("sparta_vbs_adam_step", A, W, G, M, V, S, cfg, nullptr, stream, dt_ms);
     SPARTA_GUARD_END("sparta_vbs_adam_step")
+}
+
+extern "C" int sparta_vbs_adam_step_ctl(sparta_vbs_t* A, float* W, const float* G, float* M, float* V, void* S, const sparta_adam_cfg* cfg, const void* R,
+                                        void* stream, float* dt_ms) {
+    SPARTA_GUARD_BEGIN
+    return adam_step_impl("sparta_vbs_adam_step_ctl", A, W, G, M, V, S, cfg, R, stream, dt_ms);
+    SPARTA_GUARD_END("sparta_vbs_adam_step_ctl")
+}
+
+// ---- sparta_grad_stats / sparta_grad_ctl_finish (k_gradctl.hip) ---------------------------------------------------------------------------
+static_assert(SPARTA_GRAD_CTL_BYTES == kGradCtlBytes && SPARTA_GRAD_STATS_CHUNK == kGradCtlChunk && SPARTA_GRAD_STATS_MAX_GRID == kGradCtlMaxGrid,
+              "include/sparta_amd.h and vbs_device.hpp disagree on the control record");
+
+extern "C" int sparta_grad_stats(const float* G, int64_t n, void* R, int32_t accumulate, void* stream, float* dt_ms) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    if (!R) return fail(SPARTA_ERR_INVALID, "sparta_grad_stats: R is NULL");
+    if ((uintptr_t)R % 8 != 0) return fail(SPARTA_ERR_INVALID, "sparta_grad_stats: the control record R must be 8-byte aligned");
+    if (n < 0) return fail(SPARTA_ERR_INVALID, "sparta_grad_stats: n < 0");
+    if (n > 0 && !G) return fail(SPARTA_ERR_INVALID, "sparta_grad_stats: G is NULL with n > 0");
+    if ((uintptr_t)G % 4 != 0) return fail(SPARTA_ERR_INVALID, "sparta_grad_stats: G must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, true);
+    if (g_capturing && dt_ms) return capture_refusal("time the reduction (dt_ms != NULL synchronises)", "sparta_grad_stats");
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (dt_ms) {                                // handle-free: the events live for this call (which synchronises anyway)
+        HIP_TRY(hipEventCreate(&ev[0]));
+        if (hipEventCreate(&ev[1]) != hipSuccess) { (void)hipEventDestroy(ev[0]); return fail(SPARTA_ERR_HIP, "sparta_grad_stats: hipEventCreate failed"); }
+        (void)hipEventRecord(ev[0], st);
+    }
+    launch_grad_stats(st, G, n, R, accumulate != 0);
+    hipError_t err = hipGetLastError();
+    if (dt_ms) {
+        if (err == hipSuccess) err = hipEventRecord(ev[1], st);
+        if (err == hipSuccess) err = hipEventSynchronize(ev[1]);
+        if (err == hipSuccess) err = hipEventElapsedTime(dt_ms, ev[0], ev[1]);
+        (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
+    }
+    if (err != hipSuccess) return fail(SPARTA_ERR_HIP, std::string("sparta_grad_stats: ") + hipGetErrorString(err));
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_grad_stats")
+}
+
+extern "C" int sparta_grad_ctl_finish(void* R, const sparta_grad_ctl_cfg* cfg, void* stream) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    if (!R || !cfg) return fail(SPARTA_ERR_INVALID, "sparta_grad_ctl_finish: R or cfg is NULL");
+    if ((uintptr_t)R % 8 != 0) return fail(SPARTA_ERR_INVALID, "sparta_grad_ctl_finish: the control record R must be 8-byte aligned");
+    if (!(cfg->max_norm >= 0.0f)) return fail(SPARTA_ERR_INVALID, "sparta_grad_ctl_finish: max_norm must be >= 0 (0: no clipping)");
+    if (cfg->growth_interval < 0) return fail(SPARTA_ERR_INVALID, "sparta_grad_ctl_finish: growth_interval must be >= 0 (0: the loss scale stays)");
+    if (cfg->growth_interval > 0 && (!(cfg->growth_factor >= 1.0f) || !(cfg->backoff_factor > 0.0f && cfg->backoff_factor <= 1.0f)))
+        return fail(SPARTA_ERR_INVALID, "sparta_grad_ctl_finish: growth_factor must be >= 1 and backoff_factor in (0, 1]");
+    for (int i = 0; i < 4; i++)
+        if (cfg->reserved[i] != 0) return fail(SPARTA_ERR_INVALID, "sparta_grad_ctl_finish: cfg->reserved must be 0");
+    launch_grad_ctl_finish((hipStream_t)stream, R, cfg->max_norm, cfg->growth_factor, cfg->backoff_factor, cfg->growth_interval);
+    HIP_TRY(hipGetLastError());
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_grad_ctl_finish")
 }
 
 extern "C" int sparta_vbs_step_info(const sparta_vbs_t* A, int64_t* info_out) {

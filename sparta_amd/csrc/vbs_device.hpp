@@ -267,10 +267,17 @@ struct UpdSlice {
 static_assert(sizeof(UpdSlice) == 32, "UpdSlice must stay 32 bytes");
 // sparta_vbs_sgd_step (k_update.hip): the hyper-parameters of one step, as sparta_sgd_cfg carries them
 struct SgdCfg { float lr, momentum, weight_decay, grad_scale; };
+// the control record of sparta_grad_stats / sparta_grad_ctl_finish (k_gradctl.hip): 16 words of record + one 16-byte partial per workgroup of the largest grid
+// of the reduction, which takes one workgroup per kGradCtlChunk elements (kGradCtlUnroll 16-byte loads per lane).  The steps read words 7 (coef) and 8 (skip).
+constexpr int kGradCtlUnroll = 4;
+constexpr int64_t kGradCtlChunk = (int64_t)kThreads * 4 * kGradCtlUnroll;
+constexpr int kGradCtlMaxGrid = 1024;
+constexpr size_t kGradCtlBytes = 64 + 16 * (size_t)kGradCtlMaxGrid;
+constexpr int kGradCtlCoef = 7, kGradCtlSkip = 8;
 // sparta_vbs_adam_step (k_update.hip): sparta_adam_cfg and the three constants the host derives from it in fp32 (omb1 = 1 - beta1, omb2 = 1 - beta2,
 // dk = 1 - lr * weight_decay), and the operands of one step: W, G, M, V = nztot floats each, S = the 8-word step state
 struct AdamCfg { float lr, beta1, beta2, eps, weight_decay, grad_scale, omb1, omb2, dk; int32_t decoupled; };
-struct AdamArgs { float* W; const float* G; float* M; float* V; float* S; AdamCfg c; };
+struct AdamArgs { float* W; const float* G; float* M; float* V; float* S; AdamCfg c; const uint32_t* R = nullptr; };   // R: the control record, or nullptr
 
 // sparta_vbs_spmm_t (k_spmm_t.hip): Ct (+)= A^T X walks A by block column.  The index (pattern only, built at creation): per block column the list of
 // its blocks, in block-row order; a work item = one panel of <= 32 stored columns of one block column x its whole list.  The image the kernel reads:
@@ -517,11 +524,12 @@ void launch_update_h16(bool bf16, bool hub, int tms, int kp, hipStream_t st, con
 // the 16-bit image of the transposed product, one workgroup pass per block (rounded as to_h16 rounds)
 void launch_update_h16_t(bool bf16, hipStream_t st, const SpmmTSrc* src, int64_t n_blocks, int w, const float* mab, uint16_t* dst);
 // k_update.hip (sparta_vbs_sgd_step): W, G, M = nztot floats each in the mab layout (M is not touched when cfg.momentum == 0)
-void launch_sgd_step(hipStream_t st, int64_t n, float* W, const float* G, float* M, const SgdCfg& cfg);     // the arithmetic alone; the set_values launches follow it
+// R (all three launches, and AdamArgs::R): the control record whose coef multiplies g and whose skip flag leaves W (and M) as they are, or nullptr
+void launch_sgd_step(hipStream_t st, int64_t n, float* W, const float* G, float* M, const SgdCfg& cfg, const uint32_t* R);     // the arithmetic alone; the set_values launches follow it
 // the arithmetic inside the image kernel whose image holds every stored element exactly once: launch_update_f32_frag / launch_update_h16 (stream slices) with
 // the new weight computed in registers, stored to W (and M) and handed on to the image
-void launch_sgd_f32_frag(hipStream_t st, StepRec* steps, int64_t n_steps, float* W, const float* G, float* M, const SgdCfg& cfg, float* a_frag, float* A_out);
-void launch_sgd_h16(bool bf16, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, float* W, const float* G, float* M, const SgdCfg& cfg, uint16_t* dst);
+void launch_sgd_f32_frag(hipStream_t st, StepRec* steps, int64_t n_steps, float* W, const float* G, float* M, const SgdCfg& cfg, const uint32_t* R, float* a_frag, float* A_out);
+void launch_sgd_h16(bool bf16, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, float* W, const float* G, float* M, const SgdCfg& cfg, const uint32_t* R, uint16_t* dst);
 // k_update.hip (sparta_vbs_adam_step): the tick advances a.S once per step; the others are the Adam forms of the three launches above and read what it wrote
 void launch_adam_tick(hipStream_t st, const AdamArgs& a);
 void launch_adam_step(hipStream_t st, int64_t n, const AdamArgs& a);
@@ -533,6 +541,9 @@ void launch_spmm_t(int dtype, unsigned n_items, hipStream_t st, const SpmmTParam
 int launch_colres(int nc, const ColresParams& p, size_t lds_bytes, hipStream_t st);     // nc = 1..4 columns per workgroup; 0 or a hipError_t
 int colres_max_slices(int nc);                                                          // slices the nc-column kernel holds sums for
 void launch_pack_blocks(dim3 grid, hipStream_t st, const void* src, const int32_t* ids, void* dst, int64_t block_vec);
+// k_gradctl.hip: G (n floats, any 4-byte boundary) folded into words 0..2 of the control record R (8-byte aligned, kGradCtlBytes); the finish kernel
+void launch_grad_stats(hipStream_t st, const float* G, int64_t n, void* R, bool accumulate);
+void launch_grad_ctl_finish(hipStream_t st, void* R, float max_norm, float growth_factor, float backoff_factor, int32_t growth_interval);
 
 // vbs_plan.cpp
 struct StreamPlanIn {

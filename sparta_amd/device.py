@@ -9,6 +9,16 @@ _i64p = C.POINTER(C.c_int64)
 _f32p = C.POINTER(C.c_float)
 
 
+def _ctl_ptr(ctl, device):
+    """the device address of a control record: a sparta_amd.GradCtl, its tensor (GRAD_CTL_BYTES on this device), or None"""
+    if ctl is None:
+        return None
+    R = getattr(ctl, "R", ctl)
+    if not (R.is_cuda and R.device.index == device and R.is_contiguous() and R.numel() * R.element_size() >= _lib.GRAD_CTL_BYTES):
+        raise ValueError("ctl must be a GradCtl, or a contiguous tensor of GRAD_CTL_BYTES = %d bytes, on device %d" % (_lib.GRAD_CTL_BYTES, device))
+    return C.c_void_p(R.data_ptr())
+
+
 def device_count():
     return int(lib.sparta_device_count())
 
@@ -301,13 +311,15 @@ class DeviceVBS(ValuesRecord):
                                         C.byref(dt) if timed else None))
         return dt.value if timed else None
 
-    def sgd_step(self, values, grad, momentum_buf=None, lr=None, momentum=0.0, weight_decay=0.0, grad_scale=1.0, timed=False, stream=None):
+    def sgd_step(self, values, grad, momentum_buf=None, lr=None, momentum=0.0, weight_decay=0.0, grad_scale=1.0, timed=False, stream=None, ctl=None):
         """sparta_vbs_sgd_step, device tensors: one SGD step on `values` (the float32 master copy, updated in place) with the gradient `grad` (what sddmm
         writes) and, when momentum != 0, the buffer `momentum_buf` (updated in place; zeros before the first step) -- torch.optim.SGD with dampening 0 and no
         Nesterov, grad first multiplied by grad_scale -- and the handle's images written from the new values in the same pass: afterwards the handle behaves
         as after set_values(values).  All three: contiguous float32 tensors of nztot elements on this device, in the layout of VBR.mab.  Stream-ordered on
         torch's current stream.  The version counter of `values` is bumped (a backward of a forward taken before the step raises, as after any in-place
         change) and the handle records the new version, so that the next vbs_linear forward with the same tensor skips set_values.  Needs updatable=True.
+        ctl: a GradCtl (or its tensor) after finish() -- sparta_vbs_sgd_step_ctl: the gradient is also multiplied by the record's coef, and a record that says
+        skip leaves values and momentum_buf as they are (the handle is written from values all the same); both are read on the device.
         Returns kernel ms if timed else None."""
         import torch
         if lr is None:
@@ -322,9 +334,10 @@ class DeviceVBS(ValuesRecord):
         cfg = _lib.SgdCfg(float(lr), float(momentum), float(weight_decay), float(grad_scale))
         dt = C.c_float(0)
         self._values_replaced()
-        check(lib.sparta_vbs_sgd_step(self.h, C.cast(C.c_void_p(values.data_ptr()), _f32p), C.cast(C.c_void_p(grad.data_ptr()), _f32p),
-                                      None if momentum_buf is None else C.cast(C.c_void_p(momentum_buf.data_ptr()), _f32p), C.byref(cfg),
-                                      C.c_void_p(st), C.byref(dt) if timed else None))
+        R = _ctl_ptr(ctl, self.device)
+        check(lib.sparta_vbs_sgd_step_ctl(self.h, C.cast(C.c_void_p(values.data_ptr()), _f32p), C.cast(C.c_void_p(grad.data_ptr()), _f32p),
+                                          None if momentum_buf is None else C.cast(C.c_void_p(momentum_buf.data_ptr()), _f32p), C.byref(cfg), R,
+                                          C.c_void_p(st), C.byref(dt) if timed else None))
         # the kernels wrote through the raw pointers: tell autograd, then note that the handle holds exactly this version
         bump = getattr(torch.autograd.graph, "increment_version", None)
         for t in (values,) + (() if momentum_buf is None else (momentum_buf,)):
@@ -340,7 +353,7 @@ class DeviceVBS(ValuesRecord):
         return dt.value if timed else None
 
     def adam_step(self, values, grad, exp_avg, exp_avg_sq, state, lr=None, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, grad_scale=1.0,
-                  timed=False, stream=None):
+                  timed=False, stream=None, ctl=None):
         """sparta_vbs_adam_step, device tensors: one AdamW (decoupled=True) / Adam with L2 weight decay (decoupled=False) step on `values` (the float32
         master copy, updated in place) with the gradient `grad`, the moments `exp_avg` and `exp_avg_sq` (updated in place; zeros before the first step) and
         `state`, a contiguous tensor of 8 int32 or float32 words on this device that holds the step count and the bias corrections (zeros: a fresh optimizer;
@@ -348,8 +361,8 @@ class DeviceVBS(ValuesRecord):
         grad_scale -- and the handle's images written from the new values in the same pass: afterwards the handle behaves as after set_values(values).  The
         four operands: contiguous float32 tensors of nztot elements on this device, in the layout of VBR.mab.  Stream-ordered on torch's current stream.  lr
         and the other hyper-parameters are baked into a capture.  The version counters of `values`, `exp_avg` and `exp_avg_sq` are bumped and the handle
-        records the new version of `values`, so that the next vbs_linear forward with the same tensor skips set_values.  Needs updatable=True.  Returns kernel
-        ms if timed else None."""
+        records the new version of `values`, so that the next vbs_linear forward with the same tensor skips set_values.  Needs updatable=True.  ctl: as for
+        sgd_step (sparta_vbs_adam_step_ctl); a skipped step does not advance the step count either.  Returns kernel ms if timed else None."""
         import torch
         if lr is None:
             raise ValueError("lr is required")
@@ -365,8 +378,9 @@ class DeviceVBS(ValuesRecord):
         cfg = _lib.AdamCfg(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(grad_scale), int(bool(decoupled)), 0)
         dt = C.c_float(0)
         self._values_replaced()
-        check(lib.sparta_vbs_adam_step(self.h, *(C.cast(C.c_void_p(t.data_ptr()), _f32p) for t in (values, grad, exp_avg, exp_avg_sq)),
-                                       C.c_void_p(state.data_ptr()), C.byref(cfg), C.c_void_p(st), C.byref(dt) if timed else None))
+        R = _ctl_ptr(ctl, self.device)
+        check(lib.sparta_vbs_adam_step_ctl(self.h, *(C.cast(C.c_void_p(t.data_ptr()), _f32p) for t in (values, grad, exp_avg, exp_avg_sq)),
+                                           C.c_void_p(state.data_ptr()), C.byref(cfg), R, C.c_void_p(st), C.byref(dt) if timed else None))
         # the kernels wrote through the raw pointers: tell autograd, then note that the handle holds exactly this version
         bump = getattr(torch.autograd.graph, "increment_version", None)
         for t in (values, exp_avg, exp_avg_sq):

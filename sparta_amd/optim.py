@@ -17,7 +17,8 @@ class VbsSGD:
         self.lr, self.momentum, self.weight_decay = float(lr), float(momentum), float(weight_decay)
         self._bufs = [None] * len(self.pairs)
 
-    def step(self, grad_scale=1.0):
+    def step(self, grad_scale=1.0, ctl=None):
+        """ctl: a GradCtl after collect() / finish(): its coefficient (clipping, 1 / loss scale) and its skip flag are read on the device (gradctl.py)"""
         import torch
         for i, (handle, values) in enumerate(self.pairs):
             if values.grad is None:
@@ -25,7 +26,7 @@ class VbsSGD:
             if self.momentum != 0.0 and self._bufs[i] is None:
                 self._bufs[i] = torch.zeros_like(values, requires_grad=False)
             handle.sgd_step(values, values.grad, self._bufs[i], lr=self.lr, momentum=self.momentum, weight_decay=self.weight_decay,
-                            grad_scale=grad_scale)
+                            grad_scale=grad_scale, ctl=ctl)
 
     def zero_grad(self, set_to_none=True):
         for _, values in self.pairs:
@@ -67,13 +68,14 @@ class VbsAdamW:
                               "state": torch.zeros(8, dtype=torch.int32, device=values.device)}
         return self._state[i]
 
-    def step(self, grad_scale=1.0):
+    def step(self, grad_scale=1.0, ctl=None):
+        """ctl: as for VbsSGD.step; a skipped step leaves the step count where it is"""
         for i, (handle, values) in enumerate(self.pairs):
             if values.grad is None:
                 continue
             s = self._state_of(i)
             handle.adam_step(values, values.grad, s["exp_avg"], s["exp_avg_sq"], s["state"], lr=self.lr, betas=self.betas, eps=self.eps,
-                             weight_decay=self.weight_decay, decoupled=self.decoupled, grad_scale=grad_scale)
+                             weight_decay=self.weight_decay, decoupled=self.decoupled, grad_scale=grad_scale, ctl=ctl)
 
     def zero_grad(self, set_to_none=True):
         VbsSGD.zero_grad(self, set_to_none)
