@@ -574,6 +574,17 @@ int sparta_spmm_t_host_check(int64_t rows, int64_t cols, int64_t block_rows, int
  * has a non-zero; pos[k] is its fragment position (a permutation of 0..31, non-empty columns first: compact index c at (c >> 1) + 16 (c & 1)),
  * *pairs the MFMA pairs the step issues.  The host packer and the update kernel both call the function behind this entry. */
 int sparta_frag_positions(const uint8_t* nonempty, uint8_t* pos, int32_t* pairs);
+/* The packing rule of the packed fp32 plan, for the CPU suite (no GPU).  A block of a tile is cut into its eight aligned groups of four columns;
+ * bit m of group_masks[b] says group m of block b has a non-zero.  Whole blocks are packed into steps of at most 8 slots (one slot per non-empty
+ * group), first-fit decreasing by group count, ties in ascending block order.  step_of_block[b] / slot0_of_block[b]: the block's step and the slot
+ * of its first non-empty group (the others follow); *n_steps the steps used.  A function of the masks alone. */
+int sparta_f32_pack_blocks(int32_t n_blocks, const uint8_t* group_masks, int32_t* step_of_block, int32_t* slot0_of_block, int32_t* n_steps);
+/* The packed plan of an fp32 handle: info_out[0] = 1 if its tiles of <= 32 rows run on packed steps (the partly empty blocks of a tile share a
+ * step; chosen at creation for handles made without creation flags, by a rule of the handle's own block-rows -- at least 4096 such steps of which
+ * packing removes at least 5 % -- never by a timing; SPARTA_F32_PLAN=packed|direct forces it), [1] packed steps, [2] slots (= MFMA pairs),
+ * [3] steps of the one-tile plan they replace.  Four values.  A block_row_range handle decides for its own range: where it decides differently from
+ * the whole handle the two agree within the fp32 bound, not bit for bit.  (A separate entry because sparta_vbs_info fills exactly 16 values.) */
+int sparta_vbs_packed_info(const sparta_vbs_t* A, int64_t* info_out);
 
 /* A dense operand that does NOT change between products, prepared once.  The reference's drivers multiply the same B `-x` times
  * (test/cuda/cuda_multiply.cpp:250-269); the sparse-row kernels of a handle read B row-major, so a column-major (the reference's layout)

@@ -26,7 +26,7 @@ from .gradctl import GradCtl  # noqa: F401
 
 # revision tag of the device kernels: PMC-derived numbers kept under profiles/ (HBM traffic per launch) carry it, and bench.py
 # only quotes them for the revision they were measured on
-KERNEL_REV = "r5i"
+KERNEL_REV = "r5j"
 
 # names of the reference's GPU back-ends this path replaces (include/cuda_utilities.h:38-44,
 # include/cutlass_bellpack_lib.h:19-25): all map onto the single fused kernel family.

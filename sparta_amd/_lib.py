@@ -48,6 +48,7 @@ SYMBOLS = [
     "sparta_vbs_spmm_t", "sparta_spmm_t_host_check",
     "sparta_vbs_sgd_step", "sparta_vbs_step_info", "sparta_vbs_adam_step",
     "sparta_grad_stats", "sparta_grad_ctl_finish", "sparta_vbs_sgd_step_ctl", "sparta_vbs_adam_step_ctl",
+    "sparta_f32_pack_blocks", "sparta_vbs_packed_info",
 ]
 
 
@@ -155,6 +156,8 @@ def _load():
     L.sparta_vbs_spmm_t.argtypes = [vp, vp, C.c_int64, C.c_int32, f32p, C.c_int64, C.c_int32, C.c_int32, vp, f32p]
     L.sparta_spmm_t_host_check.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, i64p, i64p, i64p, f32p, C.c_int64, C.c_int64, f32p, C.POINTER(C.c_double), i64p]
     L.sparta_frag_positions.argtypes = [C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), i32p]
+    L.sparta_f32_pack_blocks.argtypes = [C.c_int32, C.POINTER(C.c_uint8), i32p, i32p, i32p]
+    L.sparta_vbs_packed_info.argtypes = [vp, i64p]
     L.sparta_vbs_create_from_csr.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, i64p, i32p, f32p, i64p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]
     L.sparta_vbs_plan_stats.argtypes = [C.c_int64, C.c_int64, i64p, i32p, f32p, i64p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, i64p]
     L.sparta_vbs_prepare_b.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, vp, C.POINTER(vp)]

@@ -66,6 +66,10 @@ void destroy_impl(sparta_vbs* v) {
         if (v->d_wrange[ty]) (void)hipFree(v->d_wrange[ty]);
     }
     if (v->d_a_frag) (void)hipFree(v->d_a_frag);
+    if (v->d_a_pack) (void)hipFree(v->d_a_pack);
+    if (v->d_psteps) (void)hipFree(v->d_psteps);
+    if (v->d_pwrange) (void)hipFree(v->d_pwrange);
+    if (v->d_pack_loc) (void)hipFree(v->d_pack_loc);
     if (v->d_hub_steps) (void)hipFree(v->d_hub_steps);
     if (v->d_hub_steps_g) (void)hipFree(v->d_hub_steps_g);
     if (v->d_hub_tiles) (void)hipFree(v->d_hub_tiles);
@@ -739,7 +743,7 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
     // ---- stream plans (persistent kernels): see build_stream_plans ----
     StreamPlanHost plan;
     {
-        StreamPlanIn pin{cols, w, br0, br1, jab_lo, mab_lo, row_part, nzcount, jab, mab, dtype, device, skip, updatable && h16};
+        StreamPlanIn pin{cols, w, br0, br1, jab_lo, mab_lo, row_part, nzcount, jab, mab, dtype, device, skip, updatable && h16, !h16 && flags == 0};
         trace.lap("tile lists");
         if (int rc = build_stream_plans(pin, plan)) return rc;
         trace.lap("stream plans");
@@ -863,6 +867,26 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
             } else {
                 (void)hipGetLastError();
                 v->d_a_frag = nullptr;
+            }
+        }
+        if (!plan.a_pack.empty()) {
+            // packed handles: the packed image INSTEAD of the fragment image, its step list and worker ranges, and the place of every block in it (for the rebuild
+            // of the reference-layout image).  As above, a device that cannot hold the image leaves a handle that runs the LDS-staged kernel.
+            std::vector<StepRec>& ps = plan.psteps;
+            v->n_psteps = (int64_t)ps.size(); v->pack_slots = plan.pack_slots;
+            for (int k = 0; k < 32; k++) { StepRec d = ps[(size_t)v->n_psteps - 1]; d.mt_flags = (d.mt_flags & ~(STEP_LAST | STEP_SPLIT)) | STEP_FIRST; ps.push_back(d); }
+            if (hipMalloc((void**)&v->d_a_pack, plan.a_pack.size() * sizeof(float)) == hipSuccess) {
+                CREATE_TRY(hipMemcpy(v->d_a_pack, plan.a_pack.data(), plan.a_pack.size() * sizeof(float), hipMemcpyHostToDevice));
+                v->a_bytes += (int64_t)(plan.a_pack.size() * sizeof(float));
+                CREATE_TRY(hipMalloc((void**)&v->d_psteps, ps.size() * sizeof(StepRec)));
+                CREATE_TRY(hipMemcpy(v->d_psteps, ps.data(), ps.size() * sizeof(StepRec), hipMemcpyHostToDevice));
+                CREATE_TRY(hipMalloc((void**)&v->d_pwrange, plan.pwrange.size() * sizeof(int32_t)));
+                CREATE_TRY(hipMemcpy(v->d_pwrange, plan.pwrange.data(), plan.pwrange.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+                CREATE_TRY(hipMalloc((void**)&v->d_pack_loc, plan.pack_loc.size() * sizeof(PackLoc)));
+                CREATE_TRY(hipMemcpy(v->d_pack_loc, plan.pack_loc.data(), plan.pack_loc.size() * sizeof(PackLoc), hipMemcpyHostToDevice));
+            } else {
+                (void)hipGetLastError();
+                v->d_a_pack = nullptr; v->n_psteps = 0; v->pack_slots = 0;
             }
         }
         if (plan.n_hub_steps > 0) {
@@ -1201,6 +1225,22 @@ int sparta_vbs_info(const sparta_vbs_t* A, int64_t* info) {
     return SPARTA_OK;
 }
 
+// the packed plan of an fp32 handle (vbs_plan.cpp, k_f32_packed.hip): {1 if the <= 32-row tiles run on packed steps, packed steps, slots = MFMA pairs they
+// issue, steps of the one-tile plan they replace (= blocks x 32-deep slices)}
+int sparta_vbs_packed_info(const sparta_vbs_t* A, int64_t* info) {
+    if (!A || !info) return sparta::fail(SPARTA_ERR_INVALID, "sparta_vbs_packed_info: NULL argument");
+    info[0] = A->d_a_pack != nullptr; info[1] = A->n_psteps; info[2] = A->pack_slots; info[3] = A->dtype == SPARTA_F32 ? A->n_steps[0] : 0;
+    return SPARTA_OK;
+}
+
+// the packing rule of the packed plan (f32_pack_blocks, vbs_kernel_common.hpp) for the CPU suite: no GPU involved
+int sparta_f32_pack_blocks(int32_t n_blocks, const uint8_t* group_masks, int32_t* step_of_block, int32_t* slot0_of_block, int32_t* n_steps) {
+    if (n_blocks < 0 || !n_steps || (n_blocks > 0 && (!group_masks || !step_of_block || !slot0_of_block)))
+        return sparta::fail(SPARTA_ERR_INVALID, "sparta_f32_pack_blocks: bad argument");
+    *n_steps = f32_pack_blocks(n_blocks, group_masks, step_of_block, slot0_of_block);
+    return SPARTA_OK;
+}
+
 int sparta_vbs_flags(const sparta_vbs_t* A, int32_t* flags_out) {
     if (!A || !flags_out) return sparta::fail(SPARTA_ERR_INVALID, "sparta_vbs_flags: NULL argument");
     *flags_out = A->create_flags;
@@ -1453,7 +1493,8 @@ int ensure_legacy_image(sparta_vbs_t* A, hipStream_t st) {
     const size_t bytes = (size_t)(A->nztot + 128) * sizeof(float);
     HIP_TRY(hipMalloc((void**)&A->d_A, bytes));
     HIP_TRY(hipMemsetAsync(A->d_A, 0, bytes, st));
-    if (A->n_steps[0] > 0) launch_f32_legacy_from_frag(st, A->d_steps[0], A->n_steps[0], A->d_a_frag, A->d_A);
+    if (A->n_steps[0] > 0 && A->d_a_pack) launch_f32_legacy_from_pack(st, A->d_steps[0], A->d_pack_loc, A->n_steps[0], A->d_a_pack, A->d_A);
+    else if (A->n_steps[0] > 0) launch_f32_legacy_from_frag(st, A->d_steps[0], A->n_steps[0], A->d_a_frag, A->d_A);
     HIP_TRY(hipGetLastError());
     A->a_bytes += (int64_t)bytes;
     return SPARTA_OK;
@@ -1461,7 +1502,7 @@ int ensure_legacy_image(sparta_vbs_t* A, hipStream_t st) {
 void drop_legacy_image(sparta_vbs_t* A) {
     static const bool keep = [] { const char* e = std::getenv("SPARTA_F32_KEEP_LEGACY"); return e && atoi(e) != 0; }();
     if (A->create_flags & SPARTA_CREATE_TRANSPOSE) return;      // sparta_vbs_spmm_t reads the reference-layout image
-    if (keep || g_capturing || A->legacy_dropped || !A->d_A || !A->d_a_frag || A->dtype != SPARTA_F32 || A->n_steps[1] != 0 || A->n_sp_rows != 0 || A->class_timing) return;
+    if (keep || g_capturing || A->legacy_dropped || !A->d_A || !(A->d_a_frag || A->d_a_pack) || A->dtype != SPARTA_F32 || A->n_steps[1] != 0 || A->n_sp_rows != 0 || A->class_timing) return;
     (void)hipFree(A->d_A);                               // (synchronises: the autotune's launches that read it are done)
     A->d_A = nullptr;
     A->a_bytes -= (int64_t)((A->nztot + 128) * sizeof(float));
@@ -1930,7 +1971,7 @@ int spmm_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int
             if (shard_rows > 0)
                 if (int rc = ensure_gathered_steps(A, shard_rows, st)) return rc;
             // the LDS-staged kernels (33..64-row tiles; any tile under a row-major or gathered B) read the reference-layout image; the no-barrier kernel the fragment image
-            if (A->n_steps[1] > 0 || !(A->d_a_frag && b_layout == SPARTA_COL_MAJOR && shard_rows == 0))
+            if (A->n_steps[1] > 0 || !((A->d_a_frag || A->d_a_pack) && b_layout == SPARTA_COL_MAJOR && shard_rows == 0))
                 if (int rc = ensure_legacy_image(A, st)) return rc;
             StreamParams sp;
             sp.A = A->d_A; sp.B = dB; sp.C = Cout; sp.ws = (float*)A->d_ws;
@@ -1954,14 +1995,16 @@ int spmm_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int
                     if (A->n_steps[ty] == 0) continue;
                     sp.steps = shard_rows > 0 ? A->d_steps_g[ty] : A->d_steps[ty]; sp.worker_range = A->d_wrange[ty]; sp.c_nt = c_store_nt(A, ty, sp.C, sp.ldc, sp.c_row_major != 0);
                     sp.clk = (prof && ty == probe_ty) ? A->d_clk : nullptr;
-                    if (ty == 0 && A->d_a_frag && b_layout == SPARTA_COL_MAJOR && shard_rows == 0) {
+                    if (ty == 0 && (A->d_a_frag || A->d_a_pack) && b_layout == SPARTA_COL_MAJOR && shard_rows == 0) {
                         StreamParams sd = sp;                 // the <= 32-row tiles without the workgroup stage
-                        sd.A = A->d_a_frag;
+                        sd.A = A->d_a_pack ? A->d_a_pack : A->d_a_frag;
+                        if (A->d_a_pack) { sd.steps = A->d_psteps; sd.worker_range = A->d_pwrange; }      // packed handle: same workers and segments, fewer steps
                         // tiles of arbitrary height + column-major C: finished tiles wait in an LDS ring for whole aligned blocks of 32 rows (k_f32_direct.hip)
                         const int cst = [] { const char* e = std::getenv("SPARTA_CSTAGE"); return e ? atoi(e) : -1; }();     // (read per launch: tests flip it)
                         const bool c_stage = c_layout == SPARTA_COL_MAJOR && (cst >= 0 ? cst != 0 : ring_tiles(A));
                         sd.c_nt = c_store_nt(A, ty, sd.C, sd.ldc, sd.c_row_major != 0, c_stage);
-                        launch_f32_direct(c_stage, grid, st, sd);
+                        if (A->d_a_pack) launch_f32_packed(c_stage, grid, st, sd);
+                        else launch_f32_direct(c_stage, grid, st, sd);
                     } else launch_f32_stream(ty != 0, b_layout == SPARTA_ROW_MAJOR, shard_rows > 0, grid, st, sp);
                 }
                 if (prof) { HIP_TRY(hipEventRecord(A->cev[0][1], st)); A->class_ran[0] = true; }

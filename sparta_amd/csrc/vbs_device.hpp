@@ -1,6 +1,8 @@
 // vbs_device.hpp -- declarations shared by the translation units of the device side of libsparta_amd.so:
 //   k_f32_class.hip   per-class fp32 MFMA kernels + the exact-order parity kernel
 //   k_f32_stream.hip  persistent fp32 stream kernels, fix-up, B-tail copy, zero fill
+//   k_f32_direct.hip  the no-barrier fp32 kernel of the one-tile plan (one block per step)
+//   k_f32_packed.hip  ... and its packed form (partly empty blocks of a tile share a step)
 //   k_h16.hip         fp16 / bf16 storage: LDS-staged and direct stream kernels, conversions
 //   k_sparse.hip      sparse-row kernels, layout transposes, row-block pack
 //   k_spmm_t.hip      the transposed product on a handle's own stored blocks (sparta_vbs_spmm_t)
@@ -92,6 +94,11 @@ struct FixRec {                           // one per split tile
     int32_t c_row, mt;
     int32_t slot_begin, n_slots;          // its partial images: fix_slots[slot_begin .. slot_begin + n_slots)
 };
+
+// packed plan of fp32 handles (vbs_plan.cpp, k_f32_packed.hip)
+constexpr int32_t kPackNoRow = 0x20000000;                // table entry of an unused slot: 4 x this is past the end of every descriptor of B
+constexpr int kPackPadSlices = 8;                         // slices behind the end of the packed image (the pipeline requests tables five steps ahead)
+struct PackLoc { int32_t step; int32_t slot0_mask; };     // per block of the one-tile plan: its packed step; slot0 | mask << 8
 
 struct StreamParams {
     const StepRec* steps;
@@ -358,6 +365,11 @@ struct sparta_vbs {
     bool tiles_row_aligned[2] = {true, true};
     bool wide16 = false;                      // the 16-bit one-tile plan holds two sub-worker ranges per workgroup (vbs_spmm_h16_direct_kernel, WC = 64)
     float* d_a_frag = nullptr;                    // A of the one-tile plan in fragment order (k_f32_direct.hip) or nullptr
+    float* d_a_pack = nullptr;                    // packed handles (k_f32_packed.hip): A per PACKED step, instead of d_a_frag
+    sparta_dev::StepRec* d_psteps = nullptr;      // ... the packed steps, their worker ranges, and where every block of d_steps[0] sits in d_a_pack
+    int32_t* d_pwrange = nullptr;
+    sparta_dev::PackLoc* d_pack_loc = nullptr;
+    int64_t n_psteps = 0, pack_slots = 0;
     bool legacy_dropped = false;                  // fp32: the reference-layout image d_A was freed once the fragment image had won (rebuilt on demand, then kept)
     // hub plan (16-bit handles of 64-wide blocks; vbs_plan.cpp, k_hub16.hip)
     sparta_dev::HubStep* d_hub_steps = nullptr;
@@ -486,6 +498,9 @@ void launch_f32_exact(unsigned n_brows, hipStream_t st, const BlockRowDesc* rows
 void launch_f32_stream(bool mi2, bool b_row_major, bool gathered, dim3 grid, hipStream_t st, const StreamParams& sp);
 void launch_f32_direct(bool c_stage, dim3 grid, hipStream_t st, const StreamParams& sp);
 void launch_f32_legacy_from_frag(hipStream_t st, const StepRec* steps, int64_t n_steps, const float* a_frag, float* A);
+// k_f32_packed.hip
+void launch_f32_packed(bool c_stage, dim3 grid, hipStream_t st, const StreamParams& sp);
+void launch_f32_legacy_from_pack(hipStream_t st, const StepRec* steps, const PackLoc* loc, int64_t n_steps, const float* a_pack, float* A);
 void launch_fixup_group(dim3 grid, hipStream_t st, const FixRec* fix, const int32_t* big, const int32_t* fix_slots, float* ws_all, int64_t ws_slab_stride);
 void launch_fixup(dim3 grid, hipStream_t st, const FixRec* fix, const int32_t* fix_slots, const float* ws_all, int64_t ws_slab_stride, float* C, int64_t ldc,
                   int c_row_major, int accumulate);
@@ -552,6 +567,7 @@ struct StreamPlanIn {
     int32_t dtype, device;
     const uint8_t* skip;                      // [br1 - br0] block-rows handled by the sparse-row path (no tiles), or nullptr
     bool updatable = false;                   // SPARTA_CREATE_UPDATABLE: record the source of every 16-bit slice (StreamPlanHost::upd_map / upd_hub)
+    bool allow_pack = false;                  // fp32 handles made without creation flags: the one-tile plan may become a packed plan (k_f32_packed.hip)
 };
 struct StreamPlanHost {
     std::vector<StepRec> steps[2];            // per tile type: [0] <= 32 rows, [1] 33..64 rows
@@ -568,6 +584,12 @@ struct StreamPlanHost {
     int64_t n_plan_tiles[2] = {0, 0};         // tiles (with at least one block) per plan: steps per tile decides the cache policy of the C stores
     bool tiles_row_aligned[2] = {true, true}; // every tile of the plan starts at a multiple of 32 rows of C (whole 128-byte lines of a column-major C)
     std::vector<float> a_frag;                // fp32 one-tile plan: A per step in MFMA fragment order (vbs_spmm_f32_direct_kernel), or empty
+    // packed plan (fp32 one-tile plan, vbs_spmm_f32_packed_kernel): the blocks of every segment of a tile packed into shared steps.  Either a_frag or a_pack is built.
+    std::vector<StepRec> psteps;              // packed steps in execution order (same workers, segments, slots and fix-up records as steps[0])
+    std::vector<int32_t> pwrange;             // [2 * n_workers] begin / end packed step of every worker
+    std::vector<float> a_pack;                // per packed step: [8 x int32 B row of the slot, padding][fragments], kAFragSlice floats; empty: not a packed handle
+    std::vector<PackLoc> pack_loc;            // per step of steps[0] (= block): where its groups sit in a_pack
+    int64_t pack_slots = 0;                   // non-empty groups = MFMA pairs of the packed plan
     // hub plan (16-bit handles of 64-wide blocks): the long tiles of 33..64 rows, grouped by the similarity of their block columns into group tiles for
     // vbs_spmm_h16_hub_kernel (k_hub16.hip); their block-rows are in none of the two plans above
     std::vector<HubStep> hub_steps;           // in execution order, padded by 32 harmless copies

@@ -29,6 +29,32 @@ __host__ __device__ inline int frag_pairs(uint32_t nonempty) {               // 
     return (n_mfma + 1) / 2;
 }
 
+// ---- packed steps of the fp32 one-tile plan (vbs_plan.cpp, k_f32_packed.hip): ONE rule for the planner and the CPU suite -------------------
+// A block of a tile is cut into its eight aligned 4-column groups (k = 4 m .. 4 m + 3: the 16-byte pieces a lane loads from column-major B);
+// bit m of its mask: the group has a non-zero in the tile's rows.  Whole blocks are packed into steps of at most 8 slots (a slot = one group
+// = one MFMA pair), first-fit decreasing by group count, ties in ascending block order; a block without any group takes no slot and rides
+// in the first step.  step_of_block / slot0_of_block: the block's step and the slot of its first non-empty group (the others follow in
+// ascending m).  Returns the number of steps.  Deterministic, and a function of the masks alone.
+inline int32_t f32_pack_blocks(int32_t n_blocks, const uint8_t* masks, int32_t* step_of_block, int32_t* slot0_of_block) {
+    int32_t fill[8 + 1];                                  // per group count c = 8 .. 0: the blocks in ascending order come from a counting sort
+    std::vector<int32_t> order((size_t)std::max(n_blocks, 0)), used;
+    for (int c = 0; c <= 8; c++) fill[c] = 0;
+    for (int32_t b = 0; b < n_blocks; b++) fill[__builtin_popcount(masks[b])]++;
+    int32_t at = 0, start[9];
+    for (int c = 8; c >= 0; c--) { start[c] = at; at += fill[c]; }
+    for (int32_t b = 0; b < n_blocks; b++) order[(size_t)start[__builtin_popcount(masks[b])]++] = b;
+    for (int32_t q = 0; q < n_blocks; q++) {
+        const int32_t b = order[(size_t)q], c = __builtin_popcount(masks[b]);
+        size_t s = 0;
+        while (s < used.size() && used[s] + c > 8) s++;
+        if (s == used.size()) used.push_back(0);
+        step_of_block[b] = (int32_t)s;
+        slot0_of_block[b] = used[s];
+        used[s] += c;
+    }
+    return (int32_t)used.size();
+}
+
 }  // namespace sparta_dev
 
 #ifdef __HIP__            // what follows is device code: the host translation units stop here

@@ -168,8 +168,81 @@ int build_stream_plans(const StreamPlanIn& in, StreamPlanHost& P) {
                 for (const HubGroup& g : hub_groups) for (int u = 0; u < g.n; u++) hub_role[(size_t)(g.ib[u] - br0)] = 1;
             }
         }
+        // ---- PACKED PLAN, part 1 (fp32 handles made without creation flags; part 2 and the layout: below, behind the one-tile plan): the decision.  Every tile of
+        // <= 32 rows packs its blocks (f32_pack_blocks) on its own; the plan is packed when that removes at least kPackMinSaving of the steps -- a function of
+        // the matrix alone, not of the device or of a timing, so two handles of one matrix run the same kernel -- and has at least kPackMinSteps steps
+        // (the flagship saves 21 % of its steps and gains 7 %: profiles/packed/README.md); SPARTA_F32_PLAN = packed | direct forces the choice.  A packed plan deals its tiles to the workers
+        // by their PACKED step counts (tile_psteps, in tile order).  The group masks are computed here, once (pack_masks: one per step of the one-tile plan, in
+        // the order the tile loop below makes the steps; a step carries its index in StepRec::pad until part 2 has used it).
+        // LIMITATION: the rule looks at the block-rows of THIS handle.  A block_row_range handle packs every tile exactly as the whole handle would, but it decides
+        // for its own range: a range with fewer than kPackMinSteps steps, or with a smaller saving, runs the direct kernel where the whole handle runs the packed
+        // one, and the two then sum a tile in different orders (equal within the fp32 bound, not bit for bit).  SPARTA_F32_PLAN makes the choice uniform.
+        bool pack_decided = false;
+        std::vector<int32_t> tile_psteps;
+        std::vector<uint8_t> pack_masks;
+        {
+            // Both constants against profiles/packed/rule_sweep.jsonl (20 000-step plans saving 3 .. 22 % of their steps; 22 % saved on 1000 .. 16 000 steps):
+            // packed is faster from 2.8 % saved on (-2.8 %; 7.5 % saved: -4.9 %) and slower by up to 1.7 % where nothing is saved (banded 200k), so 5 %.
+            // kPackMinSteps is NOT a break-even (packed wins at 1000 steps too, by 0.7 us): plans of a few steps per worker are left exactly as they were
+            // (same image, same split tiles, same behaviour under graph capture: the suite pins all three on small handles) for a gain below a microsecond.
+            constexpr double kPackMinSaving = 0.05;
+            constexpr int64_t kPackMinSteps = 4096;
+            const char* de = std::getenv("SPARTA_F32_PLAN");
+            const bool never = de && (std::strcmp(de, "direct") == 0 || std::strcmp(de, "legacy") == 0), force = de && std::strcmp(de, "packed") == 0;
+            if (!h16 && in.allow_pack && !never) {
+                const int64_t nbr = br1 - br0, spb = w / SK_KP;
+                std::vector<std::vector<int32_t>> per_row((size_t)nbr);
+                std::vector<std::vector<uint8_t>> row_masks((size_t)nbr);
+                sparta::parallel_for_dynamic(nbr, 4, [&](int64_t lo, int64_t hi, int) {
+                    std::vector<uint8_t> mk;
+                    std::vector<int32_t> sob, s0b;
+                    for (int64_t i = lo; i < hi; i++) {
+                        const int64_t ib = br0 + i, h = row_part[ib + 1] - row_part[ib], nb = nzcount[ib];
+                        if ((in.skip && in.skip[i]) || nb == 0) continue;
+                        for (int64_t r0 = 0; r0 < h; r0 += SK_TM) {
+                            const int64_t mt = std::min<int64_t>(SK_TM, h - r0);
+                            if (mt > 32) continue;
+                            mk.clear();
+                            int32_t tails = 0;
+                            for (int64_t b = 0; b < nb; b++) {
+                                const bool tail = (jab[jab_lo + jo_of[(size_t)i] + b] + 1) * w > cols;
+                                for (int64_t ks = 0; ks < w; ks += SK_KP) {
+                                    const float* blk = mab + mab_lo + mo_of[(size_t)i] + r0 + (b * w + ks) * h;
+                                    uint8_t m8 = 0;
+                                    for (int k = 0; k < 32; k++) {
+                                        bool any = false;
+                                        for (int64_t m = 0; m < mt && !any; m++) any = blk[(int64_t)k * h + m] != 0.0f;
+                                        if (any) m8 |= (uint8_t)(1u << (k >> 2));
+                                    }
+                                    row_masks[(size_t)i].push_back(m8);      // (the block of the zero-padded last block column keeps a step of its own)
+                                    if (tail) tails++; else mk.push_back(m8);
+                                }
+                            }
+                            sob.resize(mk.size()); s0b.resize(mk.size());
+                            per_row[(size_t)i].push_back(f32_pack_blocks((int32_t)mk.size(), mk.data(), sob.data(), s0b.data()) + tails);
+                        }
+                    }
+                });
+                int64_t S0 = 0, PS0 = 0, area0 = 0;
+                for (int64_t i = 0; i < nbr; i++) {
+                    const int64_t ib = br0 + i, h = row_part[ib + 1] - row_part[ib];
+                    size_t t = 0;
+                    for (int64_t r0 = 0; r0 < h && !per_row[(size_t)i].empty(); r0 += SK_TM) {
+                        const int64_t mt = std::min<int64_t>(SK_TM, h - r0);
+                        if (mt > 32) continue;
+                        S0 += nzcount[ib] * spb; area0 += nzcount[ib] * spb * mt * SK_KP; PS0 += per_row[(size_t)i][t];
+                        tile_psteps.push_back(per_row[(size_t)i][t++]);
+                    }
+                }
+                const bool frag_ok0 = S0 > 0 && S0 <= ((int64_t)2 << 20) && S0 * kAFragSlice <= 4 * std::max<int64_t>(area0, 1) + (1 << 20);     // (the rule of the fragment image, below)
+                pack_decided = frag_ok0 && (force || (S0 >= kPackMinSteps && (double)PS0 <= (1.0 - kPackMinSaving) * (double)S0));
+                if (pack_decided) for (const auto& rm : row_masks) pack_masks.insert(pack_masks.end(), rm.begin(), rm.end());
+                else tile_psteps.clear();
+            }
+        }
         for (int ty = 0; ty < 2; ty++) {
             std::vector<StepRec>& st = steps[ty];
+            size_t pack_tile_no = 0, pack_mask_no = 0;
             struct TileSpan { int64_t first, last; int32_t c_row, mt; };     // step range of a tile
             std::vector<TileSpan> spans;
             std::vector<int64_t> cum;                                        // cumulative cost BEFORE step s
@@ -235,6 +308,9 @@ int build_stream_plans(const StreamPlanIn& in, StreamPlanHost& P) {
                             continue;
                         }
                         TileSpan sp{(int64_t)st.size(), 0, c_row, mt};
+                        // packed plan: the tile costs its PACKED steps, spread evenly over its blocks (a split may cut it anywhere)
+                        const int64_t tile_steps = nb * (w / kp), tile_cost = (pack_decided && ty == 0) ? (int64_t)c1 * tile_psteps[pack_tile_no++] : 0;
+                        int64_t step_no = 0;
                         for (int64_t b = 0; b < nb; b++) {
                             const int64_t jb = jab[jab_lo + jo2 + b];
                             for (int64_t ks = 0; ks < w; ks += kp) {
@@ -246,7 +322,7 @@ int build_stream_plans(const StreamPlanIn& in, StreamPlanHost& P) {
                                 r.mt_flags = mt;
                                 if ((jb + 1) * w > cols) { r.mt_flags |= STEP_TAIL; r.b_row = (int32_t)ks; }   // read from the zero-padded B_tail
                                 r.slot = -1;
-                                r.pad = 0;
+                                r.pad = tile_cost ? (int32_t)++pack_mask_no : 0;       // packed plan: 1 + the step's index in pack_masks
                                 if (dbg_probe) {                            // developer probe (timing only, results are wrong): which stream bounds a step
                                     if (dbg_probe & 1) r.b_row = (int32_t)ks;                                   // every panel of B is the same (cache-hot) one
                                     if ((dbg_probe & 2) && h16) r.a_off = (ks) * h;                                  // every tile reads the first block of A
@@ -254,7 +330,8 @@ int build_stream_plans(const StreamPlanIn& in, StreamPlanHost& P) {
                                     if (dbg_probe & 4) r.c_row = 0;                                             // every tile writes the first rows of C
                                 }
                                 cum.push_back(total_cost);
-                                total_cost += ty ? c2 : c1;
+                                total_cost += tile_cost ? tile_cost * (step_no + 1) / tile_steps - tile_cost * step_no / tile_steps : (ty ? c2 : c1);
+                                step_no++;
                                 st.push_back(r);
                             }
                         }
@@ -585,7 +662,112 @@ int build_stream_plans(const StreamPlanIn& in, StreamPlanHost& P) {
                 // keeps the LDS-staged kernel on the legacy image instead of quadrupling the handle)
                 int64_t one_tile_area = 0;
                 for (int64_t q = 0; q < S; q++) one_tile_area += (int64_t)(st[(size_t)q].mt_flags & 0xffff) * SK_KP;
-                if (!off && ty == 0 && !h16 && S <= ((int64_t)2 << 20) && S * kAFragSlice <= 4 * std::max<int64_t>(one_tile_area, 1) + (1 << 20)) {
+                const bool frag_ok = !off && ty == 0 && !h16 && S <= ((int64_t)2 << 20) && S * kAFragSlice <= 4 * std::max<int64_t>(one_tile_area, 1) + (1 << 20);
+                // ---- PACKED PLAN (vbs_spmm_f32_packed_kernel, k_f32_packed.hip).  A step of the plan above is one stored block, and on a FEM matrix more than half of
+                // the blocks are partly empty: the MFMAs of their empty columns are already skipped (k-compaction, below), but everything else a step costs is paid in
+                // full.  Here the blocks of a segment of a tile (a tile, or the part of a split tile one worker owns) are cut into their eight aligned 4-column groups
+                // -- the 16-byte pieces a lane loads from column-major B -- and whole blocks are packed into steps of at most 8 non-empty groups (f32_pack_blocks:
+                // first-fit decreasing): slot s of a step is one group of one block, and MFMA pair s consumes exactly that slot.  A slice of the packed image is
+                //   [8 x int32: first row of B of slot s (kPackNoRow: unused), padding to 64 bytes][fragments: slot s, element e of the group, row m at
+                //    ((j * 2 + g) * 32 + m) * 4 + e' with j = s >> 1, g = e >> 1, e' = 2 (s & 1) + (e & 1)]
+                // i.e. position k' = 16 (e >> 1) + 2 s + (e & 1) of the step's 32 in the numbering of the image below.  The block of the zero-padded last block
+                // column (STEP_TAIL) keeps a step of its own: its groups are read from B_tail.  Workers, segments, workspace slots and fix-up records are those of
+                // the plan above (steps[0] stays as it is: the LDS-staged kernel walks it under a row-major or gathered B); only the step list of the no-barrier
+                // kernel and its image change.  Handles made with creation flags keep the plan above: set_values may change which groups are empty.
+                // Whether a plan is packed was decided above (part 1), from the tiles alone.
+                bool packed = false;
+                if (frag_ok && pack_decided) {
+                    if (pack_tile_no != tile_psteps.size() || pack_mask_no != pack_masks.size() || (int64_t)pack_masks.size() != S)
+                        return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: internal error, the packed plan's tiles do not match the one-tile plan");
+                    std::vector<uint8_t> gmask((size_t)S, 0);
+                    for (int64_t q = 0; q < S; q++) { gmask[(size_t)q] = pack_masks[(size_t)st[(size_t)q].pad - 1]; st[(size_t)q].pad = 0; }
+                    std::vector<StepRec>& ps = P.psteps;
+                    std::vector<PackLoc>& loc = P.pack_loc;
+                    std::vector<int64_t> pstart((size_t)S + 1, 0);           // packed steps before the segment that starts at step q
+                    std::vector<int32_t> slots_of;                            // per packed step: slots in use
+                    loc.assign((size_t)S, PackLoc{0, 0});
+                    std::vector<uint8_t> mk;
+                    std::vector<int32_t> idx, sob, s0b;
+                    int64_t n_slots = 0;
+                    for (int64_t a = 0; a < S;) {
+                        int64_t b = a;
+                        while (!(st[(size_t)b].mt_flags & STEP_LAST)) b++;   // (every worker range ends on a STEP_LAST)
+                        const int64_t base = (int64_t)ps.size();
+                        pstart[(size_t)a] = base;
+                        mk.clear(); idx.clear();
+                        for (int64_t q = a; q <= b; q++)
+                            if (!(st[(size_t)q].mt_flags & STEP_TAIL)) { mk.push_back(gmask[(size_t)q]); idx.push_back((int32_t)(q - a)); }
+                        sob.assign(mk.size(), 0); s0b.assign(mk.size(), 0);
+                        const int32_t ns = f32_pack_blocks((int32_t)mk.size(), mk.data(), sob.data(), s0b.data());
+                        StepRec proto = st[(size_t)a];
+                        proto.mt_flags &= 0xffff; proto.slot = -1; proto.pad = 0; proto.b_row = 0;
+                        ps.insert(ps.end(), (size_t)ns, proto);
+                        slots_of.insert(slots_of.end(), (size_t)ns, 0);
+                        for (size_t u = 0; u < mk.size(); u++) {
+                            const int64_t q = a + idx[u];
+                            const int32_t cnt = __builtin_popcount(mk[u]);
+                            loc[(size_t)q] = PackLoc{(int32_t)(base + sob[u]), s0b[u] | ((int32_t)mk[u] << 8)};
+                            slots_of[(size_t)(base + sob[u])] = std::max(slots_of[(size_t)(base + sob[u])], s0b[u] + cnt);
+                            n_slots += cnt;
+                        }
+                        for (int64_t q = a; q <= b; q++) {
+                            if (!(st[(size_t)q].mt_flags & STEP_TAIL)) continue;
+                            StepRec tr = proto;
+                            tr.mt_flags |= STEP_TAIL;
+                            tr.b_row = st[(size_t)q].b_row;                  // k offset of the step in B_tail
+                            loc[(size_t)q] = PackLoc{(int32_t)ps.size(), (int32_t)gmask[(size_t)q] << 8};
+                            slots_of.push_back(__builtin_popcount(gmask[(size_t)q]));
+                            n_slots += __builtin_popcount(gmask[(size_t)q]);
+                            ps.push_back(tr);
+                        }
+                        for (size_t u = (size_t)base; u < ps.size(); u++)
+                            ps[u].mt_flags |= (std::max(slots_of[u], 1) - 1) << STEP_KPAIRS_SHIFT;
+                        ps[(size_t)base].mt_flags |= STEP_FIRST;
+                        ps.back().mt_flags |= st[(size_t)b].mt_flags & (STEP_LAST | STEP_SPLIT);
+                        ps.back().slot = st[(size_t)b].slot;
+                        a = b + 1;
+                    }
+                    const int64_t PS = (int64_t)ps.size();
+                    pstart[(size_t)S] = PS;
+                    packed = true;
+                    {
+                        P.pack_slots = n_slots;
+                        P.pwrange.assign((size_t)n_workers * 2, 0);
+                        for (int pos = 0; pos < n_workers; pos++) {
+                            P.pwrange[(size_t)wid_of_pos[(size_t)pos] * 2] = (int32_t)pstart[(size_t)bnd[(size_t)pos]];
+                            P.pwrange[(size_t)wid_of_pos[(size_t)pos] * 2 + 1] = (int32_t)pstart[(size_t)bnd[(size_t)pos + 1]];
+                        }
+                        std::vector<float>& ap = P.a_pack;
+                        ap.assign(((size_t)PS + kPackPadSlices) * (size_t)kAFragSlice, 0.0f);
+                        for (size_t u = 0; u < (size_t)PS + kPackPadSlices; u++) {
+                            int32_t* tab = reinterpret_cast<int32_t*>(ap.data() + u * (size_t)kAFragSlice);
+                            for (int sl = 0; sl < 8; sl++) tab[sl] = kPackNoRow;
+                        }
+                        // every block writes its own slots of its step's slice (no two blocks share a float)
+                        sparta::parallel_for_dynamic(S, 256, [&](int64_t lo, int64_t hi, int) {
+                            for (int64_t q = lo; q < hi; q++) {
+                                const StepRec& r = st[(size_t)q];
+                                const float* blk = mab + mab_lo + r.a_off;
+                                const int64_t hh = r.h, mt = r.mt_flags & 0xffff;
+                                float* dst = ap.data() + (size_t)loc[(size_t)q].step * (size_t)kAFragSlice;
+                                int32_t* tab = reinterpret_cast<int32_t*>(dst);
+                                float* frag = dst + 16;
+                                const int32_t mask = (loc[(size_t)q].slot0_mask >> 8) & 0xff;
+                                int sl = loc[(size_t)q].slot0_mask & 0xff;
+                                for (int gm = 0; gm < 8; gm++) {
+                                    if (!((mask >> gm) & 1)) continue;
+                                    tab[sl] = r.b_row + 4 * gm;
+                                    for (int e = 0; e < 4; e++) {
+                                        const int j = sl >> 1, g = e >> 1, e2 = 2 * (sl & 1) + (e & 1);
+                                        for (int64_t m = 0; m < mt; m++) frag[((j * 2 + g) * 32 + m) * 4 + e2] = blk[(int64_t)(4 * gm + e) * hh + m];
+                                    }
+                                    sl++;
+                                }
+                            }
+                        });
+                    }
+                }
+                if (frag_ok && !packed) {
                     // k-COMPACTION.  A stored 32 x 32 block of a FEM matrix has 23 non-empty columns on average (the flagship: 27 % of the MFMAs would
                     // multiply columns of zeros).  The sum over k may run in any order as long as both operands agree, so per step the non-empty columns
                     // K[0..nk) of the slice go FIRST: compact index c sits at fragment position k' = (c >> 1) + 16 (c & 1), i.e. MFMA t (t = 4 j + e) takes

@@ -142,6 +142,12 @@ class DeviceVBS(ValuesRecord):
                 "sparse_rows", "a_bytes", "exec_area", "stream_steps", "stream_workers", "split_tiles", "last_path"]
         return {k: int(a[i]) for i, k in enumerate(keys)}
 
+    def packed_info(self):
+        """the packed plan of an fp32 handle (k_f32_packed.hip): see sparta_vbs_packed_info"""
+        a = np.zeros(4, np.int64)
+        check(lib.sparta_vbs_packed_info(self.h, a.ctypes.data_as(_i64p)))
+        return {"packed": int(a[0]), "steps": int(a[1]), "slots": int(a[2]), "block_steps": int(a[3])}
+
     def sparse_info(self):
         """the part of the matrix on the sparse-row path: rows, nonzeros, rows handled by one wave, hub rows"""
         a = np.zeros(4, np.int64)
