@@ -547,6 +547,44 @@ int sparta_vbs_sgd_step_ctl(sparta_vbs_t* A, float* W, const float* G, float* M,
 int sparta_vbs_adam_step_ctl(sparta_vbs_t* A, float* W, const float* G, float* M, float* V, void* S,
                              const sparta_adam_cfg* cfg, const void* R, void* stream, float* dt_ms);
 
+/* Block pruning: a score per stored block, and chosen blocks made zero -- and kept zero -- in the weights, the optimizer state and the gradient.
+ * The stored blocks of the block-rows [block_row_begin, block_row_end) are numbered in mab order: block-row by block-row, inside a block-row in jab order.
+ * sparta_vbs_block_table_host (pure host code, no GPU) writes four words per block:
+ *     [0] the element offset of the block into the range's slice of mab
+ *     [1] n_in  = h * min(w, cols - jb * w): the elements inside the matrix -- a block is column-major h x w, so these are its FIRST n_in elements
+ *     [2] n_all = h * w
+ *     [3] (ib - block_row_begin) << 32 | jb: the block-row, numbered from the start of the range, and the block column
+ * Blocks of a block-row of height 0 are listed, with n_in = n_all = 0: block b is entry b of the range's jab.  table_out == NULL only counts.  The table a
+ * handle uploads for the two device entries below is built by the function behind this entry.  sparta_vbs_block_count: the blocks of a handle.
+ *
+ * sparta_vbs_block_ssq / sparta_vbs_mask_blocks: device pointers only.  W and T0..T3 hold nztot floats each in the layout of sparta_vbs_host.mab (a range
+ * handle: the slice of its block-rows, from 0) and may start on any 4-byte boundary; ssq_out holds n_blocks fp64 values (8-byte aligned), keep n_blocks
+ * bytes.  Every handle made from VBS arrays takes them (sparta_vbs_create, _create_range, _create_range_ex with any flags, all three dtypes); neither reads
+ * or writes an image of the handle -- to make a handle multiply with masked values, follow with sparta_vbs_set_values or a step.  Handles of
+ * sparta_vbs_create_from_csr / sparta_vbs_create_transposed: SPARTA_ERR_UNSUPPORTED.  SPARTA_ERR_INVALID, with nothing launched, for a NULL handle, a NULL
+ * ssq_out or keep with n_blocks > 0, a NULL W with nztot > 0, a misaligned pointer.  n_blocks == 0 succeeds and launches nothing.  The FIRST call of either
+ * entry on a handle builds and uploads the table (16 bytes per block); every later call is one kernel launch, no allocation, no synchronisation, and can
+ * be captured into a hipGraph -- a first call while the stream is being captured returns SPARTA_ERR_UNSUPPORTED, as does *dt_ms != NULL under capture
+ * (dt_ms covers the kernel and synchronises).  Blocks of 2^31 or more elements: SPARTA_ERR_UNSUPPORTED.
+ *
+ * block_ssq: ssq_out[b] = the sum of the squares of the block's first n_in elements of W; stored positions past `cols` in a ragged last block column take
+ * no part, whatever they hold.  Each element is widened to fp64 and squared there (exact), the squares are summed in fp64 by ONE wave per block in a fixed
+ * order (per lane a head up to the block's first 16-byte boundary, 16-byte loads, a tail; lanes by xor-shuffle), no atomics, one launch: bit-identical from
+ * run to run and between an eager call and a replay for the same alignment of W modulo 16 bytes, and within n_in * 2^-53 * ssq of the exact sum -- the bound
+ * of any order of additions of non-negative terms, valid for n_in < 2^26 (n_in * 2^-53 must stay far below 1 for the first-order bound to hold).  Plain IEEE
+ * arithmetic: an Inf or NaN inside the matrix gives that block a non-finite score.  n_in == 0 gives 0.0.
+ *
+ * mask_blocks: for every block with keep[b] == 0, all n_all elements (the positions past `cols` included) are stored as +0.0f in each non-NULL T; the old
+ * content is not read (an Inf or NaN there is gone).  Blocks with keep[b] != 0 are neither read nor written: their bits, and every byte outside the
+ * tensors, stay.  All four T NULL: valid, nothing launched.  The tensors must not overlap each other or keep.
+ * A zero block stays zero under sparta_vbs_sgd_step / sparta_vbs_adam_step when its gradient is masked too: with W = M = V = +0 and g = +-0 the pinned
+ * arithmetic above gives W = +0 again, with or without momentum and either kind of weight decay. */
+int sparta_vbs_block_table_host(int64_t cols, int64_t block_rows, int64_t block_col_size, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab,
+                                int64_t block_row_begin, int64_t block_row_end, int64_t* table_out /* [n_blocks][4] */, int64_t* n_blocks_out);
+int sparta_vbs_block_count(const sparta_vbs_t* A, int64_t* n_blocks_out);
+int sparta_vbs_block_ssq(sparta_vbs_t* A, const float* W, double* ssq_out, void* stream, float* dt_ms);
+int sparta_vbs_mask_blocks(sparta_vbs_t* A, const uint8_t* keep, float* T0, float* T1, float* T2, float* T3, void* stream, float* dt_ms);
+
 /* Ct (+)= A^T * X on the stored blocks of A: the gradient of the dense operand of C = A * B (X = dC, Ct = dB), on the handle itself, so that
  * it follows sparta_vbs_set_values in stream order.  Only handles made with SPARTA_CREATE_TRANSPOSE take the call; every other handle
  * (flags without the bit, sparta_vbs_create, _create_range, _create_from_csr, _create_transposed): SPARTA_ERR_UNSUPPORTED.

@@ -126,6 +126,7 @@ void destroy_impl(sparta_vbs* v) {
         if (v->d_upd_map[ty]) (void)hipFree(v->d_upd_map[ty]);
     if (v->d_upd_hub) (void)hipFree(v->d_upd_hub);
     if (v->d_upd_ws) (void)hipFree(v->d_upd_ws);
+    if (v->d_prune) (void)hipFree(v->d_prune);
     if (v->d_t_items) (void)hipFree(v->d_t_items);
     if (v->d_t_blocks) (void)hipFree(v->d_t_blocks);
     if (v->d_t_A) (void)hipFree(v->d_t_A);
@@ -775,6 +776,9 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
     v->zero_ranges = plan.zero_ranges;
     v->rows = row_part[br1] - row_part[br0]; v->cols = cols; v->block_rows = br1 - br0; v->w = w;
     v->nblocks = nblocks; v->nztot = nztot; v->exec_area = exec_area;
+    v->h_row_part.resize((size_t)(br1 - br0) + 1);          // what the block table of sparta_vbs_block_ssq / _mask_blocks is built from (with the handle's jab)
+    for (int64_t ib = br0; ib <= br1; ib++) v->h_row_part[(size_t)(ib - br0)] = row_part[ib] - row_part[br0];
+    v->h_nzcount.assign(nzcount + br0, nzcount + br1);
 
     DeviceGuard guard(device);
     if (!guard.ok) return fail(SPARTA_ERR_HIP, "sparta_vbs_create: hipSetDevice failed");
@@ -1062,7 +1066,9 @@ int sparta_vbs_create_range_ex(sparta_vbs_t** out, int64_t rows, int64_t cols, i
                                const int64_t* nzcount, const int64_t* jab, const float* mab, int64_t br0, int64_t br1, int32_t dtype,
                                int32_t device, int32_t flags) {
     SPARTA_GUARD_BEGIN
-    return create_core(out, rows, cols, block_rows, w, row_part, nzcount, jab, mab, br0, br1, dtype, device, nullptr, flags);
+    const int rc = create_core(out, rows, cols, block_rows, w, row_part, nzcount, jab, mab, br0, br1, dtype, device, nullptr, flags);
+    if (rc == SPARTA_OK) (*out)->from_vbs_arrays = true;      // (its blocks are the caller's blocks: sparta_vbs_block_ssq / sparta_vbs_mask_blocks)
+    return rc;
     SPARTA_GUARD_END("sparta_vbs_create")
 }
 
@@ -2663,6 +2669,118 @@ extern "C" int sparta_vbs_step_info(const sparta_vbs_t* A, int64_t* info_out) {
     if (!A || !info_out) return sparta::fail(SPARTA_ERR_INVALID, "sparta_vbs_step_info: NULL argument");
     info_out[0] = A->step_last_fused; info_out[1] = A->step_last_launches; info_out[2] = 0; info_out[3] = 0;
     return SPARTA_OK;
+}
+
+// ---- block pruning: sparta_vbs_block_table_host, sparta_vbs_block_count, sparta_vbs_block_ssq, sparta_vbs_mask_blocks (k_prune.hip) -------
+extern "C" int sparta_vbs_block_table_host(int64_t cols, int64_t block_rows, int64_t w, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, int64_t br0,
+                                           int64_t br1, int64_t* table_out, int64_t* n_blocks_out) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    if (cols <= 0 || block_rows <= 0 || w <= 0 || !row_part || !nzcount || !n_blocks_out)
+        return fail(SPARTA_ERR_INVALID, "sparta_vbs_block_table_host: bad dimensions or NULL argument");
+    if (br0 < 0 || br1 > block_rows || br0 > br1) return fail(SPARTA_ERR_INVALID, "sparta_vbs_block_table_host: bad block-row range");
+    const int64_t block_cols = (cols - 1) / w + 1;
+    int64_t jab_lo = 0, nblocks = 0;
+    for (int64_t ib = 0; ib < br1; ib++) {
+        if (row_part[ib + 1] < row_part[ib] || nzcount[ib] < 0 || nzcount[ib] > block_cols) return fail(SPARTA_ERR_INVALID, "sparta_vbs_block_table_host: invalid row_part / nzcount");
+        if (ib < br0) jab_lo += nzcount[ib];
+        else nblocks += nzcount[ib];
+    }
+    if (nblocks > 0 && table_out && !jab) return fail(SPARTA_ERR_INVALID, "sparta_vbs_block_table_host: jab is NULL");
+    return build_block_table(cols, w, br0, br1, row_part, nzcount, jab, jab_lo, table_out, n_blocks_out);
+    SPARTA_GUARD_END("sparta_vbs_block_table_host")
+}
+
+namespace {
+
+int prune_handle_check(const sparta_vbs_t* A, const char* entry) {
+    using sparta::fail;
+    if (!A) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": NULL handle");
+    if (!A->from_vbs_arrays)
+        return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the handle was not made from VBS arrays (handles of sparta_vbs_create_from_csr and "
+                                            "sparta_vbs_create_transposed do not hold the caller's blocks)");
+    return SPARTA_OK;
+}
+
+// the device table, made at the first call from the heights and counts kept at creation and the handle's jab, through build_block_table
+int ensure_prune_table(sparta_vbs_t* A, const char* entry) {
+    using sparta::fail;
+    if (A->n_prune >= 0) return SPARTA_OK;
+    if (g_capturing) return capture_refusal("build and upload its block table", entry);
+    const int64_t nb = A->nblocks;
+    if (nb > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": more than 2^31 - 1 blocks");
+    std::vector<int32_t> jab32((size_t)nb);
+    if (nb > 0) HIP_TRY(hipMemcpy(jab32.data(), A->d_jab, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<int64_t> jab(jab32.begin(), jab32.end()), table((size_t)nb * 4);
+    int64_t n = 0;
+    if (int rc = build_block_table(A->cols, A->w, 0, A->block_rows, A->h_row_part.data(), A->h_nzcount.data(), jab.data(), 0, table.data(), &n)) return rc;
+    if (n != nb) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": the block table disagrees with the handle's block count");
+    std::vector<PruneBlock> rec((size_t)nb);
+    for (int64_t q = 0; q < nb; q++) {
+        if (table[(size_t)(4 * q + 2)] > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": a block of 2^31 or more elements");
+        rec[(size_t)q] = PruneBlock{table[(size_t)(4 * q)], (int32_t)table[(size_t)(4 * q + 1)], (int32_t)table[(size_t)(4 * q + 2)]};
+    }
+    if (nb > 0) {
+        HIP_TRY(hipMalloc((void**)&A->d_prune, rec.size() * sizeof(PruneBlock)));
+        HIP_TRY(hipMemcpy(A->d_prune, rec.data(), rec.size() * sizeof(PruneBlock), hipMemcpyHostToDevice));
+    }
+    A->n_prune = nb;
+    return SPARTA_OK;
+}
+
+template <class Launch>
+int prune_call(sparta_vbs_t* A, const char* entry, bool nothing_to_do, void* stream, float* dt_ms, Launch launch) {
+    using sparta::fail;
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, true);
+    if (g_capturing && dt_ms) return capture_refusal("time the kernel (dt_ms != NULL synchronises)", entry);
+    if (!nothing_to_do)
+        if (int rc = ensure_prune_table(A, entry)) return rc;
+    if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
+    if (!nothing_to_do) {
+        launch(st);
+        HIP_TRY(hipGetLastError());
+    }
+    if (dt_ms) {
+        HIP_TRY(hipEventRecord(A->ev1, st));
+        HIP_TRY(hipEventSynchronize(A->ev1));
+        HIP_TRY(hipEventElapsedTime(dt_ms, A->ev0, A->ev1));
+    }
+    return SPARTA_OK;
+}
+
+}  // namespace
+
+extern "C" int sparta_vbs_block_count(const sparta_vbs_t* A, int64_t* n_blocks_out) {
+    if (int rc = prune_handle_check(A, "sparta_vbs_block_count")) return rc;
+    if (!n_blocks_out) return sparta::fail(SPARTA_ERR_INVALID, "sparta_vbs_block_count: NULL argument");
+    *n_blocks_out = A->nblocks;
+    return SPARTA_OK;
+}
+
+extern "C" int sparta_vbs_block_ssq(sparta_vbs_t* A, const float* W, double* ssq_out, void* stream, float* dt_ms) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    if (int rc = prune_handle_check(A, "sparta_vbs_block_ssq")) return rc;
+    if (A->nblocks > 0 && (!ssq_out || (!W && A->nztot > 0))) return fail(SPARTA_ERR_INVALID, "sparta_vbs_block_ssq: W or ssq_out is NULL");
+    if ((uintptr_t)W % 4 != 0 || (uintptr_t)ssq_out % 8 != 0) return fail(SPARTA_ERR_INVALID, "sparta_vbs_block_ssq: W must be 4-byte and ssq_out 8-byte aligned");
+    return prune_call(A, "sparta_vbs_block_ssq", A->nblocks == 0, stream, dt_ms,
+                      [&](hipStream_t st) { launch_block_ssq(st, A->d_prune, A->n_prune, W, ssq_out); });
+    SPARTA_GUARD_END("sparta_vbs_block_ssq")
+}
+
+extern "C" int sparta_vbs_mask_blocks(sparta_vbs_t* A, const uint8_t* keep, float* T0, float* T1, float* T2, float* T3, void* stream, float* dt_ms) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    if (int rc = prune_handle_check(A, "sparta_vbs_mask_blocks")) return rc;
+    if (A->nblocks > 0 && !keep) return fail(SPARTA_ERR_INVALID, "sparta_vbs_mask_blocks: keep is NULL");
+    if (((uintptr_t)T0 | (uintptr_t)T1 | (uintptr_t)T2 | (uintptr_t)T3) % 4 != 0) return fail(SPARTA_ERR_INVALID, "sparta_vbs_mask_blocks: the tensors must be 4-byte aligned");
+    const bool none = !T0 && !T1 && !T2 && !T3;
+    return prune_call(A, "sparta_vbs_mask_blocks", A->nblocks == 0 || A->nztot == 0 || none, stream, dt_ms,
+                      [&](hipStream_t st) { launch_mask_blocks(st, A->d_prune, A->n_prune, keep, T0, T1, T2, T3); });
+    SPARTA_GUARD_END("sparta_vbs_mask_blocks")
 }
 
 // ---- sparta_vbs_spmm_t (k_spmm_t.hip) ---------------------------------------------------------------------------------------------------

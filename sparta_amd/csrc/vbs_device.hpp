@@ -7,6 +7,7 @@
 //   k_sparse.hip      sparse-row kernels, layout transposes, row-block pack
 //   k_spmm_t.hip      the transposed product on a handle's own stored blocks (sparta_vbs_spmm_t)
 //   k_update.hip      new values for the images of an updatable handle (sparta_vbs_set_values)
+//   k_prune.hip       block pruning: per-block sums of squares, zero fill of chosen blocks (sparta_vbs_block_ssq, sparta_vbs_mask_blocks)
 //   vbs_plan.cpp      host: stream plans (step lists, worker ranges, split tiles)
 //   vbs_capi.cpp      host: device image (sparta_vbs), sparta_vbs_create* / sparta_vbs_spmm* (include/sparta_amd.h)
 // Every kernel TU exports plain launch functions (namespace sparta_dev); the host TUs never see a __global__ symbol.
@@ -306,6 +307,12 @@ struct SpmmTParams {
 };
 constexpr int kSpmmTSlab = 128;     // columns of X / Ct per workgroup (32 per wave)
 
+// block pruning (k_prune.hip): one record per stored block, mab order (build_block_table, vbs_plan.cpp): its first element, the elements inside the matrix
+// (the block's first n_in), all its elements
+struct PruneBlock { int64_t off; int32_t n_in, n_all; };
+static_assert(sizeof(PruneBlock) == 16, "PruneBlock must stay 16 bytes");
+constexpr int kPruneWaves = kThreads / 64;    // blocks per workgroup: one wave each
+
 #define HIP_TRY(expr)                                                                                   \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \
@@ -484,6 +491,12 @@ struct sparta_vbs {
     size_t d_t_ws_bytes = 0;
     void* d_t_h16 = nullptr;
     size_t d_t_h16_bytes = 0;
+    // block pruning (sparta_vbs_block_ssq / sparta_vbs_mask_blocks; handles made from VBS arrays only): the block-rows' heights and block counts, kept from
+    // creation, and the block table, built from them and the handle's jab and uploaded at the first call
+    bool from_vbs_arrays = false;
+    std::vector<int64_t> h_row_part, h_nzcount;                // [block_rows + 1] (from 0), [block_rows]
+    sparta_dev::PruneBlock* d_prune = nullptr;
+    int64_t n_prune = -1;                                      // -1: not built yet
 };
 
 namespace sparta_dev {
@@ -559,6 +572,10 @@ void launch_pack_blocks(dim3 grid, hipStream_t st, const void* src, const int32_
 // k_gradctl.hip: G (n floats, any 4-byte boundary) folded into words 0..2 of the control record R (8-byte aligned, kGradCtlBytes); the finish kernel
 void launch_grad_stats(hipStream_t st, const float* G, int64_t n, void* R, bool accumulate);
 void launch_grad_ctl_finish(hipStream_t st, void* R, float max_norm, float growth_factor, float backoff_factor, int32_t growth_interval);
+// k_prune.hip: one wave per block of the table.  ssq[b] = the fp64 sum of the exact squares of the block's first n_in elements of W; the blocks with
+// keep[b] == 0 stored as +0.0f (all n_all elements) in each non-NULL T[0..3]
+void launch_block_ssq(hipStream_t st, const PruneBlock* blocks, int64_t n_blocks, const float* W, double* ssq);
+void launch_mask_blocks(hipStream_t st, const PruneBlock* blocks, int64_t n_blocks, const uint8_t* keep, float* T0, float* T1, float* T2, float* T3);
 
 // vbs_plan.cpp
 struct StreamPlanIn {
@@ -636,6 +653,9 @@ struct SpmmTIndexHost {
 };
 int build_spmm_t_index(int64_t cols, int64_t w, int64_t br0, int64_t br1, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, int64_t jab_lo, bool h16,
                        SpmmTIndexHost& T);
+// the block table of block pruning: [n_blocks][4] = {offset, n_in, n_all, (block-row - br0) << 32 | block column}; table == nullptr only counts
+int build_block_table(int64_t cols, int64_t w, int64_t br0, int64_t br1, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, int64_t jab_lo,
+                      int64_t* table, int64_t* n_blocks);
 // one block of the 16-bit image from its column-major h x w source
 void pack_spmm_t_block(const float* blk, int64_t h, int64_t w, bool bf16, uint16_t* dst);
 uint16_t to_h16(float v, bool bf16);   // fp32 -> fp16 / bf16 bits, round to nearest even (what the device conversion kernel does too)

@@ -1135,4 +1135,28 @@ void pack_spmm_t_block(const float* blk, int64_t h, int64_t w, bool bf16, uint16
             }
 }
 
+// ---- block pruning (k_prune.hip): the block table ------------------------------------------------------------------------------------------
+// The stored blocks of the block-rows [br0, br1) in mab order (block-row by block-row, jab order inside one), four words each: the element offset into the
+// range's slice of mab, n_in = h * (stored columns inside the matrix) -- a block is column-major h x w, so these are its FIRST n_in elements --, n_all = h * w,
+// and (block-row - br0) << 32 | block column.  Blocks of a block-row of height 0 are listed with n_in = n_all = 0: the numbering is jab's.  table == nullptr
+// only counts.  sparta_vbs_block_table_host hands this to the CPU suite; the device table of a handle is made from the same rows.
+int build_block_table(int64_t cols, int64_t w, int64_t br0, int64_t br1, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, int64_t jab_lo,
+                      int64_t* table, int64_t* n_blocks) {
+    const int64_t block_cols = (cols - 1) / w + 1;
+    int64_t q = 0, mo = 0;
+    for (int64_t ib = br0; ib < br1; ib++) {
+        const int64_t h = row_part[ib + 1] - row_part[ib];
+        for (int64_t b = 0; b < nzcount[ib]; b++, q++) {
+            if (!table) continue;
+            const int64_t jb = jab[jab_lo + q];
+            if (jb < 0 || jb >= block_cols) return sparta::fail(SPARTA_ERR_INVALID, "sparta_vbs_block_table_host: jab entry out of range");
+            int64_t* t = table + 4 * q;
+            t[0] = mo; t[1] = h * std::min(w, cols - jb * w); t[2] = h * w; t[3] = ((ib - br0) << 32) | jb;
+            mo += h * w;
+        }
+    }
+    *n_blocks = q;
+    return SPARTA_OK;
+}
+
 }  // namespace sparta_dev

@@ -408,6 +408,72 @@ class DeviceVBS(ValuesRecord):
         check(lib.sparta_vbs_step_info(self.h, out))
         return {"fused": int(out[0]), "launches": int(out[1])}
 
+    @property
+    def n_blocks(self):
+        """stored blocks of the handle (sparta_vbs_block_count), those of block-rows of height 0 included: the length of block_ssq's result and of keep"""
+        if getattr(self, "_n_blocks_cached", None) is None:
+            n = C.c_int64(0)
+            check(lib.sparta_vbs_block_count(self.h, C.byref(n)))
+            self._n_blocks_cached = int(n.value)
+        return self._n_blocks_cached
+
+    def _prune_operand(self, name, t):
+        import torch
+        if not (t.is_cuda and t.dtype == torch.float32 and t.device.index == self.device and t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float32 tensor on device %d" % (name, self.device))
+        if t.numel() != self._nztot():
+            raise ValueError("%s must hold nztot = %d elements" % (name, self._nztot()))
+        return C.cast(C.c_void_p(t.data_ptr() if t.numel() else None), _f32p)
+
+    def block_ssq(self, values, out=None, timed=False, stream=None):
+        """sparta_vbs_block_ssq, device tensors: per stored block (mab order: VBR.block_table) the float64 sum of the squares of those of its elements
+        of `values` that lie inside the matrix.  values: a contiguous float32 tensor of nztot elements on this device in the layout of VBR.mab (weights,
+        a gradient, ...).  out: a contiguous float64 tensor of n_blocks elements on this device, or None (allocated).  Stream-ordered on torch's
+        current stream; one kernel launch after the first call on the handle.  Returns out, or (out, kernel ms) if timed."""
+        import torch
+        W = self._prune_operand("values", values)
+        n = self.n_blocks
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=values.device)
+        elif not (out.is_cuda and out.dtype == torch.float64 and out.device.index == self.device and out.is_contiguous() and out.numel() == n):
+            raise ValueError("out must be a contiguous float64 tensor of n_blocks = %d elements on device %d" % (n, self.device))
+        st = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+        dt = C.c_float(0)
+        check(lib.sparta_vbs_block_ssq(self.h, W, C.cast(C.c_void_p(out.data_ptr() if n else None), C.POINTER(C.c_double)), C.c_void_p(st),
+                                       C.byref(dt) if timed else None))
+        return (out, dt.value) if timed else out
+
+    def mask_blocks(self, keep, *tensors, timed=False, stream=None):
+        """sparta_vbs_mask_blocks, device tensors: every block b with keep[b] == 0 stored as +0.0 -- all its elements, the positions past cols included
+        -- in each of `tensors` (contiguous float32 tensors of nztot elements on this device in the layout of VBR.mab, updated in place; they must not
+        overlap); the other blocks are not touched.  keep: a contiguous uint8 or bool tensor of n_blocks elements on this device.  One launch per
+        group of up to four tensors.  The handle's own images are NOT changed and the handle does not learn which tensor holds its values: follow
+        with set_values (or a step) to make it multiply with the masked values.  The version counters of the tensors are bumped.  Stream-ordered on
+        torch's current stream.  Returns kernel ms if timed else None."""
+        import torch
+        if not tensors:
+            raise ValueError("mask_blocks needs at least one tensor")
+        n = self.n_blocks
+        if not (keep.is_cuda and keep.dtype in (torch.uint8, torch.bool) and keep.device.index == self.device and keep.is_contiguous() and keep.numel() == n):
+            raise ValueError("keep must be a contiguous uint8 or bool tensor of n_blocks = %d elements on device %d" % (n, self.device))
+        ptrs = [self._prune_operand("tensor %d" % i, t) for i, t in enumerate(tensors)]
+        st = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+        kp = C.cast(C.c_void_p(keep.data_ptr() if n else None), C.POINTER(C.c_uint8))
+        total = 0.0
+        for g in range(0, len(ptrs), 4):
+            grp = ptrs[g:g + 4] + [None] * (4 - len(ptrs[g:g + 4]))
+            dt = C.c_float(0)
+            check(lib.sparta_vbs_mask_blocks(self.h, kp, *grp, C.c_void_p(st), C.byref(dt) if timed else None))
+            total += dt.value
+        bump = getattr(torch.autograd.graph, "increment_version", None)
+        for t in tensors:
+            if bump is not None:
+                bump(t)
+            else:
+                with torch.no_grad():
+                    t.add_(0)
+        return total if timed else None
+
     def set_values_host(self, mab):
         """set_values with a host array (numpy, fp32, nztot elements), staged through scratch of the handle.  Returns kernel ms."""
         mab = np.ascontiguousarray(mab, np.float32).reshape(-1)

@@ -338,6 +338,19 @@ class VBR:
         finally:
             lib.sparta_vbs_host_free(C.byref(h))
 
+    def block_table(self, block_row_range=None):
+        """sparta_vbs_block_table_host: the stored blocks of the block-rows block_row_range = (b0, b1) (default: all) in mab order, an (n_blocks, 4) int64
+        array: element offset into the range's slice of mab, n_in (the elements inside the matrix: the block's first n_in), n_all = h * w, and
+        (block-row - b0) << 32 | block column.  Block b is block b of DeviceVBS.block_ssq / mask_blocks on a handle of the same range."""
+        b0, b1 = (0, self.block_rows) if block_row_range is None else (int(block_row_range[0]), int(block_row_range[1]))
+        rp, nz, jab = (np.ascontiguousarray(a, np.int64) for a in (self.row_part, self.nzcount, self.jab))
+        args = (self.cols, self.block_rows, self.block_col_size, rp.ctypes.data_as(_i64p), nz.ctypes.data_as(_i64p), jab.ctypes.data_as(_i64p), b0, b1)
+        n = C.c_int64(0)
+        check(lib.sparta_vbs_block_table_host(*args, None, C.byref(n)))
+        table = np.zeros((n.value, 4), np.int64)
+        check(lib.sparta_vbs_block_table_host(*args, table.ctypes.data_as(_i64p), C.byref(n)))
+        return table
+
     def to_device(self, device=0, dtype=_lib.F32, block_row_range=None, updatable=False, transposable=False):
         from .device import DeviceVBS
         return DeviceVBS(self, device=device, dtype=dtype, block_row_range=block_row_range, updatable=updatable, transposable=transposable)

@@ -1,0 +1,135 @@
+"""Block pruning for block-sparse layers on VBS handles: a score per stored block (sparta_vbs_block_ssq), a selection rule in torch, and the chosen blocks
+written as zeros -- and kept zero through training -- in the weights, the optimizer state and the gradients (sparta_vbs_mask_blocks).  The block pattern
+of a handle stays as creation made it: a pruned block is a stored block of zeros, which the fp32 forward product already skips (the k-compaction of
+set_values follows the zero pattern of the new values).  torch is imported when first used, as in optim.py."""
+import math
+
+
+def select(scores, keep, sparsity, scope="global"):
+    """The selection rule: which blocks are to be zero at `sparsity`.  Pure torch, any device, no synchronisation.
+
+    scores, keep: lists with one tensor per layer -- a floating-point score per block (low = prune first) and the current mask (uint8 or bool, 0 = pruned).
+    Over all blocks (scope "global") or per layer ("layer"): k = floor(sparsity * n_blocks) blocks are to be zero in total.  The blocks already pruned count
+    first (they stay pruned: the rule is monotone); then come the live blocks in ascending score order, ties going to the lower (layer, block) index (a
+    stable sort).  A non-finite score counts as +Inf: such a block is chosen only when no block with a finite score is left.  With k not above the number
+    already pruned nothing changes.  Returns the new masks, a list of uint8 tensors."""
+    import torch
+    if scope not in ("global", "layer"):
+        raise ValueError("scope must be 'global' or 'layer'")
+    if not 0.0 <= sparsity <= 1.0:
+        raise ValueError("sparsity must lie in [0, 1]")
+    if len(scores) != len(keep) or any(s.numel() != k.numel() for s, k in zip(scores, keep)):
+        raise ValueError("scores and keep must hold one tensor per layer, of the same lengths")
+
+    def one(s, live):
+        n = s.numel()
+        k = int(math.floor(sparsity * n))
+        s = s.reshape(-1).to(torch.float64)
+        inf = torch.full_like(s, float("inf"))
+        key = torch.where(live, torch.where(torch.isfinite(s), s, inf), -inf)          # the pruned first, in index order; the non-finite last
+        order = torch.sort(key, stable=True).indices
+        rank = torch.empty_like(order)
+        rank[order] = torch.arange(n, device=order.device)
+        return (live & (rank >= k)).to(torch.uint8)
+
+    lives = [k.reshape(-1) != 0 for k in keep]
+    if scope == "layer" or len(scores) <= 1:
+        return [one(s, l) for s, l in zip(scores, lives)]
+    new = one(torch.cat([s.reshape(-1).to(torch.float64) for s in scores]), torch.cat(lives))
+    return list(torch.split(new, [k.numel() for k in keep]))
+
+
+class BlockPruner:
+    """Magnitude pruning of the stored blocks of block-sparse layers, on the device.
+
+        pruner = sa.BlockPruner(opt)              # a VbsSGD / VbsAdamW, or a list of (handle, values) pairs
+        ...
+        loss.backward(); pruner.mask_grads(); ctl.collect(opt); opt.step(ctl=ctl)          # every step: the gradient of the pruned blocks is zero
+        pruner.prune(0.5)                         # now and then: the lowest-scoring blocks of all layers become zero
+
+    The score of a block is the sum of the squares of its values inside the matrix, divided (normalize=True) by their number: block-rows of different heights
+    compare, and a ragged last block column is not pruned for being narrow.  scope: "global" ranks the blocks of all pairs together, "layer" each pair alone.
+    A pruned block is +0.0 in values, in the optimizer's state and (after mask_grads) in the gradient, and the optimizers' arithmetic keeps it there (W = M =
+    V = +0 and g = +-0 give W = +0, with momentum and with either weight decay).  prune, mask_grads and scores are launches and torch device operations only, on
+    torch's current stream; mask_grads can be captured into a graph after its first call (the masks are updated in place)."""
+
+    def __init__(self, optimizer_or_pairs, scope="global", normalize=True):
+        import torch
+        if scope not in ("global", "layer"):
+            raise ValueError("scope must be 'global' or 'layer'")
+        self.optimizer = optimizer_or_pairs if hasattr(optimizer_or_pairs, "pairs") else None
+        self.pairs = [(h, v) for h, v in (self.optimizer.pairs if self.optimizer is not None else optimizer_or_pairs)]
+        self.scope, self.normalize = scope, bool(normalize)
+        self._keep, self._n_in = [], []
+        for handle, values in self.pairs:
+            self._keep.append(torch.ones(handle.n_blocks, dtype=torch.uint8, device=values.device))
+            self._n_in.append(handle.block_ssq(torch.ones_like(values, requires_grad=False)))          # 1 + 1 + ...: the elements inside the matrix, exactly
+
+    def scores(self):
+        """per pair: block_ssq(values), divided by the block's elements inside the matrix when normalize (a block without any scores +Inf)"""
+        import torch
+        out = []
+        for (handle, values), n_in in zip(self.pairs, self._n_in):
+            s = handle.block_ssq(values.detach())
+            if self.normalize:
+                s = torch.where(n_in > 0, s / n_in, torch.full_like(s, float("inf")))
+            out.append(s)
+        return out
+
+    def _state_tensors(self, i):
+        opt = self.optimizer
+        if opt is None:
+            return []
+        if hasattr(opt, "_bufs"):
+            return [opt._bufs[i]] if opt._bufs[i] is not None else []
+        s = opt._state[i] if hasattr(opt, "_state") else None
+        return [] if s is None else [s["exp_avg"], s["exp_avg_sq"]]
+
+    def _apply(self, i):
+        handle, values = self.pairs[i]
+        tensors = [values.detach()] + ([values.grad] if values.grad is not None else []) + self._state_tensors(i)
+        handle.mask_blocks(self._keep[i], *tensors)
+        handle.set_values(values.detach())
+
+    def prune(self, sparsity):
+        """select() on scores(), then per pair the pruned blocks zeroed in values, values.grad (if present) and the optimizer's state (where allocated), and
+        the handle given the new values"""
+        new = select(self.scores(), self._keep, sparsity, self.scope)
+        for i, k in enumerate(new):
+            self._keep[i].copy_(k)
+            self._apply(i)
+
+    def mask_grads(self):
+        """the gradient of every pruned block made zero: call it after backward and before GradCtl.collect / step, so that the clipped norm is that of the
+        live blocks and the step leaves the pruned ones at zero"""
+        for (handle, values), keep in zip(self.pairs, self._keep):
+            if values.grad is not None:
+                handle.mask_blocks(keep, values.grad)
+
+    def keep_masks(self):
+        """per pair the mask, a uint8 device tensor of n_blocks elements (0 = pruned); updated in place by prune"""
+        return list(self._keep)
+
+    def sparsity(self):
+        """pruned blocks / blocks over all pairs (synchronises)"""
+        total = sum(k.numel() for k in self._keep)
+        pruned = sum(int((k == 0).sum().item()) for k in self._keep)
+        return pruned / total if total else 0.0
+
+    def state_dict(self):
+        """{"keep": [per pair the mask as a uint8 CPU tensor], "scope", "normalize"} (synchronises)"""
+        return {"keep": [k.detach().cpu().clone() for k in self._keep], "scope": self.scope, "normalize": self.normalize}
+
+    def load_state_dict(self, sd):
+        """takes the masks over and applies them as prune does: values, gradient and optimizer state of the pruned blocks become zero, the handles get the
+        new values"""
+        import torch
+        if len(sd["keep"]) != len(self.pairs):
+            raise ValueError("the state dict holds %d pairs, the pruner %d" % (len(sd["keep"]), len(self.pairs)))
+        for i, src in enumerate(sd["keep"]):
+            if src.numel() != self._keep[i].numel():
+                raise ValueError("pair %d: the mask holds %d blocks, expected %d" % (i, src.numel(), self._keep[i].numel()))
+        self.scope, self.normalize = sd.get("scope", self.scope), bool(sd.get("normalize", self.normalize))
+        for i, src in enumerate(sd["keep"]):
+            self._keep[i].copy_((src != 0).to(torch.uint8))
+            self._apply(i)
