@@ -337,7 +337,17 @@ int sparta_vbs_plan_stats(int64_t rows, int64_t cols, const int64_t* rowptr, con
  *   of the block-row, row jb * w + q of Y), and with accumulate = 1 on their own previous value.
  *   sparta_vbs_set_values: a non-finite value in a stored block reaches only rows of C of that block's block-row (and, through spmm_t, rows of Ct of its
  *   block column); the next set_values replaces it completely.
- *   Overwriting calls (accumulate = 0) do not depend on the previous content of the output, NaN included. */
+ *   Overwriting calls (accumulate = 0) do not depend on the previous content of the output, NaN included.
+ *   WITH A LIVE-BLOCK SET INSTALLED (sparta_vbs_set_live_blocks; a block is dead when its byte of the snapshot is 0):
+ *   sparta_vbs_sddmm: the elements of G in a live block have the same bits as the same call without a live set.  A dead block depends on nothing: neither
+ *   X's rows of its block-row nor Y's rows of its block column are read on its behalf.  accumulate = 0: all n_all elements of a dead block are +0.0f, the
+ *   positions past `cols` included.  accumulate = 1: its elements are neither read nor written -- a -0.0f, a NaN or any other bits there stay.
+ *   sparta_vbs_spmm_t: Ct[c, j] is the sum over the LIVE blocks of c's block column only, in block-row order: still one wave, one fixed order, no atomics.
+ *   accumulate = 0 still writes all cols x n_cols elements, zeros where no live block covers a column.  Rows of X that reach a block column only through
+ *   dead blocks are not read for it.  Dropping a block removes whole MFMA passes (a pass covers rows of one block only): with finite X the result equals,
+ *   up to the sign of a zero, the product without a live set on values whose dead blocks are zero.
+ *   Everything else ignores the live set: the forward products, sparta_vbs_set_values, the steps, sparta_vbs_block_ssq, sparta_vbs_mask_blocks.  Keeping
+ *   the VALUES of dead blocks at zero stays the caller's job. */
 int sparta_vbs_spmm(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int32_t n_cols,
                     void* C, int64_t ldc, int32_t c_layout, int32_t accumulate,
                     int32_t ptr_space, void* stream, int32_t algo, float* dt_ms);
@@ -584,6 +594,40 @@ int sparta_vbs_block_table_host(int64_t cols, int64_t block_rows, int64_t block_
 int sparta_vbs_block_count(const sparta_vbs_t* A, int64_t* n_blocks_out);
 int sparta_vbs_block_ssq(sparta_vbs_t* A, const float* W, double* ssq_out, void* stream, float* dt_ms);
 int sparta_vbs_mask_blocks(sparta_vbs_t* A, const uint8_t* keep, float* T0, float* T1, float* T2, float* T3, void* stream, float* dt_ms);
+
+/* The live-block set of a handle: which of its stored blocks the two backward products (sparta_vbs_sddmm, sparta_vbs_spmm_t) still compute.  The pattern, the
+ * images and every other entry stay as they are (the contract: "WITH A LIVE-BLOCK SET INSTALLED" above).
+ *
+ * sparta_vbs_set_live_blocks: keep = n_blocks device bytes in the numbering of sparta_vbs_mask_blocks (mab order, blocks of block-rows of height 0 included,
+ * a range handle: the numbering of its range); keep[b] == 0: block b is dead.  The handle takes a snapshot in stream order: later writes to the caller's keep
+ * have no effect until the next call.  keep == NULL removes the live set (host state only, nothing launched): from then on the handle launches the kernels
+ * and lists it launched before one was installed.  Takes every handle sparta_vbs_mask_blocks takes (others: SPARTA_ERR_UNSUPPORTED); without
+ * SPARTA_CREATE_TRANSPOSE only the SDDMM half is built.  The FIRST call with keep != NULL builds and uploads pattern-only helper arrays (the block table, the
+ * map from positions of the block-column index to block numbers, about 40 bytes per block) and returns SPARTA_ERR_UNSUPPORTED while the stream is being
+ * captured; every later call is two kernel launches (one without SPARTA_CREATE_TRANSPOSE), no allocation, no synchronisation, capturable -- a replay reads
+ * keep again.  WHETHER a live set is installed is host state, decided when sparta_vbs_sddmm / _spmm_t is called (or captured); its CONTENT is device state in
+ * stream order, as the values after sparta_vbs_set_values are.  With a live set sparta_vbs_sddmm with accumulate = 0 is two launches (the zeros of the dead
+ * blocks, then the product).  sparta_vbs_destroy frees everything.
+ *
+ * The lists (written by stable compaction -- ballot and prefix count, one wave per block-row / block column, no atomics: a function of keep alone):
+ *   sd_groups[SDDMM groups], sd_count[block_rows]: group g of a block-row is its stored columns 32 g .. 32 g + 31 (mab order, nb * w of them; a block-row of
+ *     height 0 has no groups); it is live iff one of the blocks it overlaps is.  Block-row ib owns the slice of sd_groups that starts at the sum of the group
+ *     counts of the block-rows before it: its live group numbers in ascending order, sd_count[ib] of them, then -1.  Work item (block-row, tile of rows, g0)
+ *     of sparta_vbs_sddmm takes positions g0 .. g0 + 15 of the slice.
+ *   t_blocks[spmm_t list entries], t_count[block columns]: the list of block column jb is its blocks of height > 0 in block-row order; its slice starts at
+ *     the sum of the list lengths of the block columns before it and holds the block numbers of its live blocks in that order, t_count[jb] of them, then -1.
+ * sparta_vbs_live_info: info_out[8] = {installed, n_blocks, live blocks, SDDMM groups, live SDDMM groups, spmm_t list entries, live spmm_t list entries, 0},
+ * the live counts read back from the device (words 2..6 are 0 when no live set is installed, words 5, 6 without SPARTA_CREATE_TRANSPOSE).
+ * sparta_vbs_live_lists_get: the lists the kernels walk, downloaded (host pointers; any of the four may be NULL); SPARTA_ERR_INVALID without a live set.  Both
+ * synchronise the stream and are refused under capture; they are for tests and records.
+ * sparta_vbs_live_lists_host: the same rule as host code (no GPU) on VBS arrays and a host keep, arguments as sparta_vbs_block_table_host; any of the four
+ * outputs may be NULL (info_out[3] and [5] give the sizes). */
+int sparta_vbs_set_live_blocks(sparta_vbs_t* A, const uint8_t* keep, void* stream);
+int sparta_vbs_live_info(sparta_vbs_t* A, int64_t* info_out /* [8] */, void* stream);
+int sparta_vbs_live_lists_get(sparta_vbs_t* A, int32_t* sd_groups, int32_t* sd_count, int32_t* t_blocks, int32_t* t_count, void* stream);
+int sparta_vbs_live_lists_host(int64_t cols, int64_t block_rows, int64_t block_col_size, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab,
+                               int64_t block_row_begin, int64_t block_row_end, const uint8_t* keep, int32_t* sd_groups, int32_t* sd_count, int32_t* t_blocks,
+                               int32_t* t_count, int64_t* info_out /* [8] */);
 
 /* Ct (+)= A^T * X on the stored blocks of A: the gradient of the dense operand of C = A * B (X = dC, Ct = dB), on the handle itself, so that
  * it follows sparta_vbs_set_values in stream order.  Only handles made with SPARTA_CREATE_TRANSPOSE take the call; every other handle

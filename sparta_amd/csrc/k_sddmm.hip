@@ -16,6 +16,13 @@
 // 16-bit: v_mfma_f32_32x32x16_{f16,bf16} wants 8 consecutive k per lane, which column-major X and Y have strided.  Both are staged as
 //       [k][32 entities] images (coalesced row loads; X once per workgroup, Y per wave and group) and read back with ds_read_b64_tr_b16.
 //       EXEC is all ones at every transposed read (the group loops are wave-uniform), the LDS image is one 16-byte aligned static object.
+//
+// Live-block set (sparta_vbs_set_live_blocks, k_live.hip): the LIVE forms of the two kernels (vbs_sdlive_*_kernel; the bodies are templates, LIVE = false
+// is the kernel as it always was).  An item takes positions g0 .. g0 + 15 of its block-row's COMPACTED list of live groups; a workgroup whose item has none
+// returns before its first barrier; inside a live group a lane whose stored column belongs to a dead block loads nothing and its column is stored as +0.0f
+// (accumulate = 0) or skipped, neither read nor written (accumulate = 1).  The groups without a live block are not visited: their zeros under accumulate = 0
+// come from a launch of the mask kernel of k_prune.hip on G and the snapshot, in front (vbs_capi.cpp).  (Storing them inside this kernel was built and
+// measured: 2 to 6 us faster at the median, inside the arms' ranges -- profiles/live/README.md -- and not kept.)
 #include "vbs_kernel_common.hpp"
 
 namespace sparta_dev {
@@ -33,22 +40,63 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
-// the stored column of lane (lane & 31) in group gi of the item: its column of Y, or -1 (past the block-row's stored columns, or ragged)
-__device__ __forceinline__ int64_t sd_column(const SddmmParams& p, const BlockRowDesc& br, int64_t nq, int64_t q) {
-    if (q >= nq) return -1;
-    const int64_t b = q / p.w, c = q - b * p.w;
-    const int64_t col = (int64_t)p.jab[br.jab_off + b] * p.w + c;
-    return col < p.cols ? col : -1;
+// the stored column of lane (lane & 31) in group gi of the item: its column of Y, or -1 (past the block-row's stored columns, or ragged); LIVE: -2 if
+// its block is dead (keep = the snapshot, one byte per block).  The LIVE form is branch-free -- a lane past the block-row's stored columns looks up block 0,
+// which exists: a workgroup gets here only with a group to compute -- so that the loads of the wave's groups (jab and keep of each) are issued together: written
+// with the early return of the plain form, every load waits for the one before it, and the eight extra round trips cost the kernel 15 us of its 140
+// (profiles/live/README.md)
+// ... for NQ stored columns at once, in three phases -- the divisions (a 64-bit division is a routine with a branch of its own), then every load, then the
+// classification: the loads of all NQ are in flight together
+template <int NQ>
+__device__ __forceinline__ void sd_columns_live(const SddmmParams& p, const BlockRowDesc& br, int64_t nq, const int64_t (&q)[NQ], const uint8_t* keep, int64_t (&col)[NQ]) {
+    int64_t b[NQ], c[NQ];
+    int32_t jb[NQ];
+    uint8_t k[NQ];
+#pragma unroll
+    for (int t = 0; t < NQ; t++) {
+        const int64_t qc = q[t] < nq ? q[t] : 0;
+        b[t] = qc / p.w;
+        c[t] = qc - b[t] * p.w;
+    }
+#pragma unroll
+    for (int t = 0; t < NQ; t++) {
+        jb[t] = p.jab[br.jab_off + b[t]];
+        k[t] = keep[br.jab_off + b[t]];
+    }
+#pragma unroll
+    for (int t = 0; t < NQ; t++) {
+        const int64_t cc = (int64_t)jb[t] * p.w + c[t];
+        col[t] = q[t] >= nq ? -1 : k[t] == 0 ? -2 : cc < p.cols ? cc : -1;
+    }
+}
+
+template <bool LIVE>
+__device__ __forceinline__ int64_t sd_column(const SddmmParams& p, const BlockRowDesc& br, int64_t nq, int64_t q, const uint8_t* keep) {
+    if constexpr (LIVE) {
+        const int64_t qs[1] = {q};
+        int64_t col[1];
+        sd_columns_live<1>(p, br, nq, qs, keep, col);
+        return col[0];
+    } else {
+        if (q >= nq) return -1;
+        const int64_t b = q / p.w, c = q - b * p.w;
+        const int64_t col = (int64_t)p.jab[br.jab_off + b] * p.w + c;
+        return col < p.cols ? col : -1;
+    }
 }
 
 // the 32 x 32 accumulator -> G: lane (i = lane & 31, g = lane >> 5), register r: stored column q0 + (r & 3) + 8 (r >> 2) + 4 g, row i.  A stored position past
 // cols (ragged last block column) gets 0 whatever X holds: its accumulator is X times the zeros that stand in for a row of Y that does not exist, and
-// Inf x 0 is NaN (include/sparta_amd.h: such a position depends on nothing)
+// Inf x 0 is NaN (include/sparta_amd.h: such a position depends on nothing).  LIVE: a second mask, the positions of dead blocks -- +0.0f under
+// accumulate = 0, neither read nor written under accumulate = 1; a ragged position of a live block still gets its 0
+template <bool LIVE>
 __device__ __forceinline__ void sd_store(const SddmmParams& p, const BlockRowDesc& br, const f32x16& acc, float* G, int64_t base, int64_t q0, int64_t nq, int h, int mt,
-                                         int lane, int accumulate) {
+                                         int lane, int accumulate, const uint8_t* keep) {
     const int i = lane & 31;
     // bit j: stored position q0 + j is a column of the matrix -- looked up once per group of 32 positions (lane j), not once per stored element
-    const unsigned long long live = __ballot(sd_column(p, br, nq, q0 + i) >= 0);
+    const int64_t cq = sd_column<LIVE>(p, br, nq, q0 + i, keep);
+    const unsigned long long live = __ballot(cq >= 0);
+    const unsigned long long dead = LIVE ? __ballot(cq == -2) : 0ull;
     if (i >= mt) return;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
@@ -56,27 +104,67 @@ __device__ __forceinline__ void sd_store(const SddmmParams& p, const BlockRowDes
         const int64_t q = q0 + j;
         if (q >= nq) continue;
         float* dst = G + base + q * h + i;
+        if constexpr (LIVE)
+            if ((dead >> j) & 1) {
+                if (!accumulate) *dst = 0.0f;
+                continue;
+            }
         const float v = (live >> j) & 1 ? acc[r] : 0.0f;
         *dst = accumulate ? *dst + v : v;
     }
 }
 
-__global__ __launch_bounds__(kThreads) void vbs_sddmm_f32_kernel(const SddmmParams p) {
+// the groups of an item.  LIVE: positions g0 .. g0 + 15 of the block-row's compacted list (ng = 0: the item has nothing to do); else g0 .. g0 + ng - 1
+template <bool LIVE>
+struct SdGroups {
+    const int32_t* list;
+    int g0, ng;
+    __device__ __forceinline__ SdGroups(const SddmmItem& it, const SddmmLive& lv) : list(nullptr), g0(it.g0), ng(it.ng) {
+        if constexpr (LIVE) {
+            list = lv.groups + lv.goff[it.brow] + it.g0;
+            ng = min(max(lv.count[it.brow] - it.g0, 0), kSdGroups);
+        }
+    }
+    // group number of slot s (wave-uniform); LIVE: of slot min(s, ng - 1), ng >= 1 -- an unconditional load, so that a wave's four are issued together
+    __device__ __forceinline__ int at(int s) const {
+        if constexpr (LIVE) return list[min(s, ng - 1)];
+        else return g0 + s;
+    }
+};
+
+template <bool LIVE>
+__device__ __forceinline__ void sddmm_f32_body(const SddmmParams& p, const SddmmLive& lv) {
     __shared__ float xs[kKC32][32];
     const SddmmItem it = p.items[blockIdx.x];
+    const SdGroups<LIVE> grp(it, lv);
     const BlockRowDesc br = p.brows[it.brow];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int mt = min(32, br.h - it.r0);
     const int64_t nq = (int64_t)br.nb * p.w;
+    if constexpr (LIVE)
+        if (grp.ng == 0) return;                                        // (the whole workgroup, before the first barrier)
     const float* X = (const float*)p.X + (int64_t)br.c_row + it.r0;
     const float* Y = (const float*)p.Y;
     const float* yp[kSdGpw];
     bool ok[kSdGpw];
+    int gq[kSdGpw];
+#pragma unroll
+    for (int t = 0; t < kSdGpw; t++) gq[t] = grp.at(wv + kSdWaves * t);
+    int64_t colv[kSdGpw];
+    if constexpr (LIVE) {
+        int64_t qs[kSdGpw];
+#pragma unroll
+        for (int t = 0; t < kSdGpw; t++) {
+            gq[t] = __builtin_amdgcn_readfirstlane(gq[t]);
+            qs[t] = (int64_t)gq[t] * 32 + (lane & 31);
+        }
+        sd_columns_live<kSdGpw>(p, br, nq, qs, lv.keep, colv);
+    }
 #pragma unroll
     for (int t = 0; t < kSdGpw; t++) {
-        const int64_t col = sd_column(p, br, nq, (int64_t)(it.g0 + wv + kSdWaves * t) * 32 + (lane & 31));
-        ok[t] = col >= 0 && wv + kSdWaves * t < it.ng;
+        const int64_t col = LIVE ? colv[t] : sd_column<false>(p, br, nq, (int64_t)gq[t] * 32 + (lane & 31), nullptr);
+        ok[t] = col >= 0 && wv + kSdWaves * t < grp.ng;
         yp[t] = Y + (ok[t] ? col : 0) + (int64_t)(lane >> 5) * p.ldy;
     }
     f32x16 acc[kSdGpw];
@@ -93,7 +181,7 @@ __global__ __launch_bounds__(kThreads) void vbs_sddmm_f32_kernel(const SddmmPara
         __syncthreads();
 #pragma unroll
         for (int t = 0; t < kSdGpw; t++) {
-            if (wv + kSdWaves * t >= it.ng) break;                      // wave-uniform
+            if (wv + kSdWaves * t >= grp.ng) break;                     // wave-uniform
             float yv[kKC32 / 2];
 #pragma unroll
             for (int s = 0; s < kKC32 / 2; s++) {
@@ -109,10 +197,13 @@ __global__ __launch_bounds__(kThreads) void vbs_sddmm_f32_kernel(const SddmmPara
     const int64_t base = br.a_off + it.r0;
 #pragma unroll
     for (int t = 0; t < kSdGpw; t++) {
-        if (wv + kSdWaves * t >= it.ng) break;
-        sd_store(p, br, acc[t], p.G, base, (int64_t)(it.g0 + wv + kSdWaves * t) * 32, nq, br.h, mt, lane, p.accumulate);
+        if (wv + kSdWaves * t >= grp.ng) break;
+        sd_store<LIVE>(p, br, acc[t], p.G, base, (int64_t)gq[t] * 32, nq, br.h, mt, lane, p.accumulate, lv.keep);
     }
 }
+
+__global__ __launch_bounds__(kThreads) void vbs_sddmm_f32_kernel(const SddmmParams p) { sddmm_f32_body<false>(p, SddmmLive{}); }
+__global__ __launch_bounds__(kThreads) void vbs_sdlive_f32_kernel(const SddmmParams p, const SddmmLive lv) { sddmm_f32_body<true>(p, lv); }
 
 // 8 consecutive k (kb + 8 (lane >> 5) .. + 7) of entity lane & 31 from a [k][32] image of 16-bit values: two transposed reads.  Lane 4q + p of a
 // 16-lane group addresses row kb + 8 (lane >> 5) + 4 t + q, entities 16 ((lane >> 4) & 1) + 4 p .. + 3; lane i of the group receives entity i.
@@ -131,24 +222,40 @@ struct SdLds16 {
 
 // VEC (w, ldy multiples of 8, Y 16-byte aligned): a run of 8 stored columns is 8 consecutive columns of Y, 16 aligned bytes -- one load per lane
 // puts 8 columns of one k in the image (4 lanes a row of it); otherwise every lane gathers its own column, one 16-bit load per k
-template <bool BF16, bool VEC>
-__global__ __launch_bounds__(kThreads) void vbs_sddmm_h16_kernel(const SddmmParams p) {
+template <bool BF16, bool VEC, bool LIVE>
+__device__ __forceinline__ void sddmm_h16_body(const SddmmParams& p, const SddmmLive& lv) {
     __shared__ __attribute__((aligned(16))) SdLds16 lds;   // (the only LDS object: its base, and every row, is 16-byte aligned)
     const SddmmItem it = p.items[blockIdx.x];
+    const SdGroups<LIVE> grp(it, lv);
     const BlockRowDesc br = p.brows[it.brow];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int mt = min(32, br.h - it.r0);
     const int64_t nq = (int64_t)br.nb * p.w;
+    if constexpr (LIVE)
+        if (grp.ng == 0) return;                                        // (the whole workgroup, before the first barrier)
     const uint16_t* X = (const uint16_t*)p.X + (int64_t)br.c_row + it.r0;
     const uint16_t* Y = (const uint16_t*)p.Y;
     const uint16_t* yp[kSdGpw];
     bool ok[kSdGpw], full[kSdGpw];
+    int gq[kSdGpw];
+#pragma unroll
+    for (int t = 0; t < kSdGpw; t++) gq[t] = grp.at(wv + kSdWaves * t);
+    int64_t colv[kSdGpw];
+    if constexpr (LIVE) {
+        int64_t qs[kSdGpw];
+#pragma unroll
+        for (int t = 0; t < kSdGpw; t++) {
+            gq[t] = __builtin_amdgcn_readfirstlane(gq[t]);
+            qs[t] = (int64_t)gq[t] * 32 + (VEC ? 8 * (lane & 3) : lane & 31);
+        }
+        sd_columns_live<kSdGpw>(p, br, nq, qs, lv.keep, colv);
+    }
 #pragma unroll
     for (int t = 0; t < kSdGpw; t++) {
-        const int64_t q0 = (int64_t)(it.g0 + wv + kSdWaves * t) * 32;
-        const int64_t col = VEC ? sd_column(p, br, nq, q0 + 8 * (lane & 3)) : sd_column(p, br, nq, q0 + (lane & 31));
-        ok[t] = col >= 0 && wv + kSdWaves * t < it.ng;
+        const int64_t q0 = (int64_t)gq[t] * 32;
+        const int64_t col = LIVE ? colv[t] : sd_column<false>(p, br, nq, VEC ? q0 + 8 * (lane & 3) : q0 + (lane & 31), nullptr);     // (VEC: w % 8 == 0, the 8 columns lie in one block)
+        ok[t] = col >= 0 && wv + kSdWaves * t < grp.ng;
         yp[t] = Y + (ok[t] ? col : 0) + (int64_t)(VEC ? lane >> 2 : lane >> 5) * p.ldy;
         full[t] = ok[t] && col + 8 <= p.cols;
     }
@@ -165,7 +272,7 @@ __global__ __launch_bounds__(kThreads) void vbs_sddmm_h16_kernel(const SddmmPara
         }
 #pragma unroll
         for (int t = 0; t < kSdGpw; t++) {
-            if (wv + kSdWaves * t >= it.ng) break;
+            if (wv + kSdWaves * t >= grp.ng) break;
             if constexpr (VEC) {
 #pragma unroll
                 for (int s = 0; s < kKC16 / 16; s++) {
@@ -195,7 +302,7 @@ __global__ __launch_bounds__(kThreads) void vbs_sddmm_h16_kernel(const SddmmPara
             const s16x8 xf = sd_tr_frag(&lds.x[0][0], 16 * m, lane);
 #pragma unroll
             for (int t = 0; t < kSdGpw; t++) {
-                if (wv + kSdWaves * t >= it.ng) break;
+                if (wv + kSdWaves * t >= grp.ng) break;
                 const s16x8 yf = sd_tr_frag(&lds.y[wv][t][0][0], 16 * m, lane);
                 if constexpr (BF16) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, yf), __builtin_bit_cast(bf16x8, xf), acc[t], 0, 0, 0);
                 else acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, yf), __builtin_bit_cast(f16x8, xf), acc[t], 0, 0, 0);
@@ -205,10 +312,15 @@ __global__ __launch_bounds__(kThreads) void vbs_sddmm_h16_kernel(const SddmmPara
     const int64_t base = br.a_off + it.r0;
 #pragma unroll
     for (int t = 0; t < kSdGpw; t++) {
-        if (wv + kSdWaves * t >= it.ng) break;
-        sd_store(p, br, acc[t], p.G, base, (int64_t)(it.g0 + wv + kSdWaves * t) * 32, nq, br.h, mt, lane, p.accumulate);
+        if (wv + kSdWaves * t >= grp.ng) break;
+        sd_store<LIVE>(p, br, acc[t], p.G, base, (int64_t)gq[t] * 32, nq, br.h, mt, lane, p.accumulate, lv.keep);
     }
 }
+
+template <bool BF16, bool VEC>
+__global__ __launch_bounds__(kThreads) void vbs_sddmm_h16_kernel(const SddmmParams p) { sddmm_h16_body<BF16, VEC, false>(p, SddmmLive{}); }
+template <bool BF16, bool VEC>
+__global__ __launch_bounds__(kThreads) void vbs_sdlive_h16_kernel(const SddmmParams p, const SddmmLive lv) { sddmm_h16_body<BF16, VEC, true>(p, lv); }
 
 }  // namespace
 
@@ -220,6 +332,16 @@ void launch_sddmm(int dtype, unsigned n_items, hipStream_t st, const SddmmParams
     else if (dtype == SPARTA_BF16) hipLaunchKernelGGL((vbs_sddmm_h16_kernel<true, false>), dim3(n_items), dim3(kThreads), 0, st, p);
     else if (vec) hipLaunchKernelGGL((vbs_sddmm_h16_kernel<false, true>), dim3(n_items), dim3(kThreads), 0, st, p);
     else hipLaunchKernelGGL((vbs_sddmm_h16_kernel<false, false>), dim3(n_items), dim3(kThreads), 0, st, p);
+}
+
+void launch_sddmm_live(int dtype, unsigned n_items, hipStream_t st, const SddmmParams& p, const SddmmLive& lv) {
+    if (n_items == 0) return;
+    const bool vec = p.w % 8 == 0 && p.ldy % 8 == 0 && (uintptr_t)p.Y % 16 == 0;
+    if (dtype == SPARTA_F32) hipLaunchKernelGGL(vbs_sdlive_f32_kernel, dim3(n_items), dim3(kThreads), 0, st, p, lv);
+    else if (dtype == SPARTA_BF16 && vec) hipLaunchKernelGGL((vbs_sdlive_h16_kernel<true, true>), dim3(n_items), dim3(kThreads), 0, st, p, lv);
+    else if (dtype == SPARTA_BF16) hipLaunchKernelGGL((vbs_sdlive_h16_kernel<true, false>), dim3(n_items), dim3(kThreads), 0, st, p, lv);
+    else if (vec) hipLaunchKernelGGL((vbs_sdlive_h16_kernel<false, true>), dim3(n_items), dim3(kThreads), 0, st, p, lv);
+    else hipLaunchKernelGGL((vbs_sdlive_h16_kernel<false, false>), dim3(n_items), dim3(kThreads), 0, st, p, lv);
 }
 
 }  // namespace sparta_dev

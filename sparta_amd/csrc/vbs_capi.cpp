@@ -127,6 +127,15 @@ void destroy_impl(sparta_vbs* v) {
     if (v->d_upd_hub) (void)hipFree(v->d_upd_hub);
     if (v->d_upd_ws) (void)hipFree(v->d_upd_ws);
     if (v->d_prune) (void)hipFree(v->d_prune);
+    if (v->d_live_keep) (void)hipFree(v->d_live_keep);
+    if (v->d_live_goff) (void)hipFree(v->d_live_goff);
+    if (v->d_live_groups) (void)hipFree(v->d_live_groups);
+    if (v->d_live_gcount) (void)hipFree(v->d_live_gcount);
+    if (v->d_live_tmap) (void)hipFree(v->d_live_tmap);
+    if (v->d_live_tids) (void)hipFree(v->d_live_tids);
+    if (v->d_live_tcount) (void)hipFree(v->d_live_tcount);
+    if (v->d_live_t_blocks) (void)hipFree(v->d_live_t_blocks);
+    if (v->d_live_t_items) (void)hipFree(v->d_live_t_items);
     if (v->d_t_items) (void)hipFree(v->d_t_items);
     if (v->d_t_blocks) (void)hipFree(v->d_t_blocks);
     if (v->d_t_A) (void)hipFree(v->d_t_A);
@@ -1031,6 +1040,7 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
         SpmmTIndexHost T;
         if (int rc = build_spmm_t_index(cols, w, br0, br1, row_part, nzcount, jab, jab_lo, h16, T)) return rc;
         v->n_t_items = (int64_t)T.items.size();
+        v->n_t_blocks = (int64_t)T.blocks.size();
         CREATE_TRY(hipMalloc((void**)&v->d_t_items, T.items.size() * sizeof(SpmmTItem)));
         CREATE_TRY(hipMemcpy(v->d_t_items, T.items.data(), T.items.size() * sizeof(SpmmTItem), hipMemcpyHostToDevice));
         if (!T.blocks.empty()) {
@@ -2353,7 +2363,14 @@ int sddmm_impl(sparta_vbs_t* A, const void* X, int64_t ldx, const void* Y, int64
     p.ldx = kx; p.ldy = ky; p.cols = A->cols;
     p.k = k; p.w = (int32_t)A->w; p.accumulate = accumulate != 0; p.pad = 0;
     if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
-    launch_sddmm(A->dtype, (unsigned)A->n_sd_items, st, p);
+    if (A->live_on) {
+        // a live set is installed: the dead blocks get their zeros (accumulate = 0) from the mask kernel and the snapshot, in front; the live kernel walks the
+        // compacted group lists over the same grid (an item past its block-row's live groups returns at once), so nothing here depends on a count read back
+        if (!p.accumulate && A->n_prune > 0 && A->nztot > 0) launch_mask_blocks(st, A->d_prune, A->n_prune, A->d_live_keep, dG, nullptr, nullptr, nullptr);
+        launch_sddmm_live(A->dtype, (unsigned)A->n_sd_items, st, p, SddmmLive{A->d_live_groups, A->d_live_goff, A->d_live_gcount, A->d_live_keep});
+    } else {
+        launch_sddmm(A->dtype, (unsigned)A->n_sd_items, st, p);
+    }
     HIP_TRY(hipGetLastError());
     if (dt_ms) {
         HIP_TRY(hipEventRecord(A->ev1, st));
@@ -2783,6 +2800,174 @@ extern "C" int sparta_vbs_mask_blocks(sparta_vbs_t* A, const uint8_t* keep, floa
     SPARTA_GUARD_END("sparta_vbs_mask_blocks")
 }
 
+// ---- the live-block set: sparta_vbs_set_live_blocks, _live_info, _live_lists_get, _live_lists_host (k_live.hip) ----------------------------------
+namespace {
+
+// the pattern-only helper arrays, made at the first sparta_vbs_set_live_blocks from what the handle keeps (heights, counts, jab; the block table for the zeros
+// of sddmm), and the arrays the launches of every call fill
+int ensure_live_arrays(sparta_vbs_t* A, const char* entry) {
+    using sparta::fail;
+    if (A->live_built) return SPARTA_OK;
+    if (g_capturing) return capture_refusal("build and upload the helper arrays of the live set", entry);
+    if (int rc = ensure_prune_table(A, entry)) return rc;
+    const int64_t nb = A->nblocks;
+    std::vector<int32_t> jab32((size_t)nb);
+    if (nb > 0) HIP_TRY(hipMemcpy(jab32.data(), A->d_jab, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const std::vector<int64_t> jab(jab32.begin(), jab32.end());
+    LiveMapsHost M;
+    if (int rc = build_live_maps(A->cols, A->w, 0, A->block_rows, A->h_row_part.data(), A->h_nzcount.data(), jab.data(), 0, M)) return rc;
+    std::vector<int32_t> goff;
+    for (int64_t ib = 0; ib < A->block_rows; ib++)
+        if (A->h_row_part[(size_t)ib + 1] > A->h_row_part[(size_t)ib]) goff.push_back((int32_t)M.goff[(size_t)ib]);
+    if ((int64_t)goff.size() != A->n_brows || M.first_block.back() != nb) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": the live-set maps disagree with the handle's block-rows");
+    auto alloc = [](void** ptr, size_t bytes) {
+        if (*ptr) { (void)hipFree(*ptr); *ptr = nullptr; }
+        return hipMalloc(ptr, std::max<size_t>(bytes, 16));
+    };
+    A->live_n_groups = M.goff.back();
+    HIP_TRY(alloc((void**)&A->d_live_keep, (size_t)nb));
+    HIP_TRY(alloc((void**)&A->d_live_goff, goff.size() * sizeof(int32_t)));
+    HIP_TRY(alloc((void**)&A->d_live_groups, (size_t)A->live_n_groups * sizeof(int32_t)));
+    HIP_TRY(alloc((void**)&A->d_live_gcount, goff.size() * sizeof(int32_t)));
+    if (!goff.empty()) HIP_TRY(hipMemcpy(A->d_live_goff, goff.data(), goff.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    A->live_n_tlist = 0;
+    A->live_block_cols = (int64_t)M.tptr.size() - 1;
+    if (A->create_flags & SPARTA_CREATE_TRANSPOSE) {
+        const int64_t panels = (A->w + 31) / 32;
+        if (A->live_block_cols * panels != A->n_t_items || (int64_t)M.tmap.size() != A->n_t_blocks)
+            return fail(SPARTA_ERR_INVALID, std::string(entry) + ": the live-set maps disagree with the handle's block-column index");
+        A->live_n_tlist = (int64_t)M.tmap.size();
+        HIP_TRY(alloc((void**)&A->d_live_tmap, M.tmap.size() * sizeof(int32_t)));
+        HIP_TRY(alloc((void**)&A->d_live_tids, M.tmap.size() * sizeof(int32_t)));
+        HIP_TRY(alloc((void**)&A->d_live_t_blocks, M.tmap.size() * sizeof(SpmmTBlock)));
+        HIP_TRY(alloc((void**)&A->d_live_tcount, (size_t)A->live_block_cols * sizeof(int32_t)));
+        HIP_TRY(alloc((void**)&A->d_live_t_items, (size_t)A->n_t_items * sizeof(SpmmTItem)));
+        if (!M.tmap.empty()) HIP_TRY(hipMemcpy(A->d_live_tmap, M.tmap.data(), M.tmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    A->live_built = true;
+    return SPARTA_OK;
+}
+
+}  // namespace
+
+extern "C" int sparta_vbs_set_live_blocks(sparta_vbs_t* A, const uint8_t* keep, void* stream) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* entry = "sparta_vbs_set_live_blocks";
+    if (int rc = prune_handle_check(A, entry)) return rc;
+    if (!keep) {                                 // host state only: the products launch what they launched before a live set was installed
+        A->live_on = false;
+        return SPARTA_OK;
+    }
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, true);
+    if (int rc = ensure_live_arrays(A, entry)) return rc;
+    launch_live_sddmm(st, A->d_brows, A->n_brows, (int)A->w, keep, A->nblocks, A->d_live_keep, A->d_live_goff, A->d_live_groups, A->d_live_gcount);
+    if (A->create_flags & SPARTA_CREATE_TRANSPOSE)
+        launch_live_spmm_t(st, A->d_t_items, A->d_t_blocks, A->d_live_tmap, A->live_block_cols, (int)((A->w + 31) / 32), keep, A->d_live_t_items, A->d_live_t_blocks,
+                           A->d_live_tids, A->d_live_tcount);
+    HIP_TRY(hipGetLastError());
+    A->live_on = true;
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_vbs_set_live_blocks")
+}
+
+namespace {
+
+// the device state of an installed live set on the host (synchronises `st`)
+struct LiveDownload { std::vector<uint8_t> keep; std::vector<int32_t> groups, gcount, tids, tcount; };
+int live_download(sparta_vbs_t* A, const char* entry, hipStream_t st, LiveDownload& D) {
+    using sparta::fail;
+    const CaptureScope capture(st, true);
+    if (g_capturing) return capture_refusal("read the live set back (synchronises)", entry);
+    HIP_TRY(hipStreamSynchronize(st));
+    auto get = [](auto& vec, const void* src, int64_t n) {
+        vec.resize((size_t)n);
+        return n > 0 ? hipMemcpy(vec.data(), src, (size_t)n * sizeof(vec[0]), hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    HIP_TRY(get(D.keep, A->d_live_keep, A->nblocks));
+    HIP_TRY(get(D.groups, A->d_live_groups, A->live_n_groups));
+    HIP_TRY(get(D.gcount, A->d_live_gcount, A->n_brows));
+    HIP_TRY(get(D.tids, A->d_live_tids, A->live_n_tlist));
+    HIP_TRY(get(D.tcount, A->d_live_tcount, (A->create_flags & SPARTA_CREATE_TRANSPOSE) ? A->live_block_cols : 0));
+    return SPARTA_OK;
+}
+
+}  // namespace
+
+extern "C" int sparta_vbs_live_info(sparta_vbs_t* A, int64_t* info_out, void* stream) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* entry = "sparta_vbs_live_info";
+    if (int rc = prune_handle_check(A, entry)) return rc;
+    if (!info_out) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": NULL argument");
+    std::memset(info_out, 0, 8 * sizeof(int64_t));
+    info_out[1] = A->nblocks;
+    if (!A->live_on) return SPARTA_OK;
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
+    LiveDownload D;
+    if (int rc = live_download(A, entry, (hipStream_t)stream, D)) return rc;
+    info_out[0] = 1;
+    for (uint8_t k : D.keep) info_out[2] += k != 0;
+    info_out[3] = A->live_n_groups;
+    for (int32_t n : D.gcount) info_out[4] += n;
+    info_out[5] = A->live_n_tlist;
+    for (int32_t n : D.tcount) info_out[6] += n;
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_vbs_live_info")
+}
+
+extern "C" int sparta_vbs_live_lists_get(sparta_vbs_t* A, int32_t* sd_groups, int32_t* sd_count, int32_t* t_blocks, int32_t* t_count, void* stream) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* entry = "sparta_vbs_live_lists_get";
+    if (int rc = prune_handle_check(A, entry)) return rc;
+    if (!A->live_on) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": no live set is installed");
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
+    LiveDownload D;
+    if (int rc = live_download(A, entry, (hipStream_t)stream, D)) return rc;
+    if (sd_groups && !D.groups.empty()) std::memcpy(sd_groups, D.groups.data(), D.groups.size() * sizeof(int32_t));
+    if (sd_count) {                              // per block-row of the handle; the device keeps the block-rows of height > 0 only
+        size_t at = 0;
+        for (int64_t ib = 0; ib < A->block_rows; ib++) sd_count[ib] = A->h_row_part[(size_t)ib + 1] > A->h_row_part[(size_t)ib] ? D.gcount[at++] : 0;
+    }
+    if (t_blocks && !D.tids.empty()) std::memcpy(t_blocks, D.tids.data(), D.tids.size() * sizeof(int32_t));
+    if (t_count && !D.tcount.empty()) std::memcpy(t_count, D.tcount.data(), D.tcount.size() * sizeof(int32_t));
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_vbs_live_lists_get")
+}
+
+extern "C" int sparta_vbs_live_lists_host(int64_t cols, int64_t block_rows, int64_t w, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, int64_t br0,
+                                          int64_t br1, const uint8_t* keep, int32_t* sd_groups, int32_t* sd_count, int32_t* t_blocks, int32_t* t_count, int64_t* info_out) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* entry = "sparta_vbs_live_lists_host";
+    if (cols <= 0 || block_rows <= 0 || w <= 0 || !row_part || !nzcount || !info_out) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": bad dimensions or NULL argument");
+    if (br0 < 0 || br1 > block_rows || br0 > br1) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": bad block-row range");
+    const int64_t block_cols = (cols - 1) / w + 1;
+    int64_t jab_lo = 0, nblocks = 0;
+    for (int64_t ib = 0; ib < br1; ib++) {
+        if (row_part[ib + 1] < row_part[ib] || nzcount[ib] < 0 || nzcount[ib] > block_cols) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": invalid row_part / nzcount");
+        if (ib < br0) jab_lo += nzcount[ib];
+        else nblocks += nzcount[ib];
+    }
+    if (nblocks > 0 && (!jab || !keep)) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": jab or keep is NULL");
+    LiveMapsHost M;
+    if (int rc = build_live_maps(cols, w, br0, br1, row_part, nzcount, jab, jab_lo, M)) return rc;
+    std::vector<int32_t> g((size_t)M.goff.back()), gc((size_t)(br1 - br0)), t((size_t)M.tptr.back()), tc((size_t)block_cols);
+    live_lists_host(M, keep, g.data(), gc.data(), t.data(), tc.data(), info_out);
+    if (sd_groups && !g.empty()) std::memcpy(sd_groups, g.data(), g.size() * sizeof(int32_t));
+    if (sd_count && !gc.empty()) std::memcpy(sd_count, gc.data(), gc.size() * sizeof(int32_t));
+    if (t_blocks && !t.empty()) std::memcpy(t_blocks, t.data(), t.size() * sizeof(int32_t));
+    if (t_count) std::memcpy(t_count, tc.data(), tc.size() * sizeof(int32_t));
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_vbs_live_lists_host")
+}
+
 // ---- sparta_vbs_spmm_t (k_spmm_t.hip) ---------------------------------------------------------------------------------------------------
 namespace {
 
@@ -2827,6 +3012,7 @@ int spmm_t_impl(sparta_vbs_t* A, const void* X, int64_t ldx, int32_t n_cols, flo
     }
     SpmmTParams p;
     p.items = A->d_t_items; p.blocks = A->d_t_blocks;
+    if (A->live_on) { p.items = A->d_live_t_items; p.blocks = A->d_live_t_blocks; }      // the same kernels on the compacted lists (an empty list writes the zeros)
     p.A = h16 ? (const void*)A->d_t_A : (const void*)A->d_A;
     p.X = dX; p.Ct = dC;
     p.ldx = kx; p.ldo = ldo; p.cols = A->cols;

@@ -8,6 +8,7 @@
 //   k_spmm_t.hip      the transposed product on a handle's own stored blocks (sparta_vbs_spmm_t)
 //   k_update.hip      new values for the images of an updatable handle (sparta_vbs_set_values)
 //   k_prune.hip       block pruning: per-block sums of squares, zero fill of chosen blocks (sparta_vbs_block_ssq, sparta_vbs_mask_blocks)
+//   k_live.hip        the live-block set of a handle: stable compaction of the lists sddmm and spmm_t walk (sparta_vbs_set_live_blocks)
 //   vbs_plan.cpp      host: stream plans (step lists, worker ranges, split tiles)
 //   vbs_capi.cpp      host: device image (sparta_vbs), sparta_vbs_create* / sparta_vbs_spmm* (include/sparta_amd.h)
 // Every kernel TU exports plain launch functions (namespace sparta_dev); the host TUs never see a __global__ symbol.
@@ -263,6 +264,16 @@ struct SddmmParams {
     int32_t k, w, accumulate, pad;
 };
 
+// the live-block set of a handle (sparta_vbs_set_live_blocks; k_live.hip writes these arrays, the live kernels of k_sddmm.hip read them): per block-row of
+// d_brows the numbers of its live groups, in ascending order, at groups[goff[brow] ..], count[brow] of them (-1 behind them); keep = the snapshot, one byte
+// per stored block (0 / 1), block b of block-row `brow` at keep[brows[brow].jab_off + b].  An item (brow, r0, g0, ng) takes positions g0 .. g0 + 15 of the list.
+struct SddmmLive {
+    const int32_t* groups;
+    const int32_t* goff;
+    const int32_t* count;
+    const uint8_t* keep;
+};
+
 // sparta_vbs_set_values (k_update.hip): where one 16-bit slice of an updatable handle comes from.  Row rr of the slice, column kk of its k range, is
 // mab[off_lo + kk * h_lo + rr] for rr < rows_lo, else mab[off_hi + kk * h_hi + (rr - 32)] for 32 <= rr < 32 + rows_hi, else zero.  An ordinary tile has
 // rows_lo = its rows (<= 64) and rows_hi = 0; a pair tile has rows_lo = 32 or 0 (upper block-row present or not) and rows_hi = the lower block-row's
@@ -483,7 +494,7 @@ struct sparta_vbs {
     // sparta_vbs_spmm_t (SPARTA_CREATE_TRANSPOSE handles only): the block-column index, the 16-bit image, the sources of its blocks; host-pointer calls stage X, Ct
     sparta_dev::SpmmTItem* d_t_items = nullptr;
     sparta_dev::SpmmTBlock* d_t_blocks = nullptr;
-    int64_t n_t_items = 0;
+    int64_t n_t_items = 0, n_t_blocks = 0;
     uint16_t* d_t_A = nullptr;                                 // 16-bit handles: [ceil(h / 8)][w][8] per block, blocks in mab order
     sparta_dev::SpmmTSrc* d_t_src = nullptr;                   // 16-bit handles with both flags: one record per block (set_values)
     int64_t n_t_src = 0;
@@ -497,6 +508,20 @@ struct sparta_vbs {
     std::vector<int64_t> h_row_part, h_nzcount;                // [block_rows + 1] (from 0), [block_rows]
     sparta_dev::PruneBlock* d_prune = nullptr;
     int64_t n_prune = -1;                                      // -1: not built yet
+    // the live-block set (sparta_vbs_set_live_blocks): whether one is installed is host state; the helper arrays (pattern only) are built at the first call,
+    // the snapshot and the compacted lists are written by the launches of every call (k_live.hip)
+    bool live_on = false, live_built = false;
+    uint8_t* d_live_keep = nullptr;                            // [nblocks] the snapshot (0 / 1)
+    int32_t* d_live_goff = nullptr;                            // [n_brows] first position of the block-row's slice of d_live_groups
+    int32_t* d_live_groups = nullptr;                          // [live_n_groups]
+    int32_t* d_live_gcount = nullptr;                          // [n_brows]
+    int64_t live_n_groups = 0;
+    int32_t* d_live_tmap = nullptr;                            // [live_n_tlist] list position of d_t_blocks -> block number
+    int32_t* d_live_tids = nullptr;                            // [live_n_tlist] the live block numbers of every block column, compacted (-1 behind them)
+    int32_t* d_live_tcount = nullptr;                          // [block columns]
+    sparta_dev::SpmmTBlock* d_live_t_blocks = nullptr;         // d_t_blocks, every block column's live records first
+    sparta_dev::SpmmTItem* d_live_t_items = nullptr;           // d_t_items with l1 = l0 + live count
+    int64_t live_n_tlist = 0, live_block_cols = 0;
 };
 
 namespace sparta_dev {
@@ -542,6 +567,9 @@ void launch_union_f32(unsigned n_slabs, hipStream_t st, const UnionParams& p);
 void launch_union_h16(bool bf16, unsigned n_slabs, hipStream_t st, const UnionParams& p);   // 16-bit handles: p.B = the row-major 16-bit B, side.A = 16-bit slices
 // k_sddmm.hip: one workgroup per work item (n_items <= 2^31 - 1); dtype = SPARTA_F32 / F16 / BF16
 void launch_sddmm(int dtype, unsigned n_items, hipStream_t st, const SddmmParams& p);
+// ... with a live set: an item's groups come from lv's compacted list, stored columns of dead blocks are not loaded (accumulate = 0: stored as +0.0f; 1: skipped);
+// the groups that are not on the list are not written: under accumulate = 0 the caller zeroes the dead blocks first (launch_mask_blocks with the snapshot)
+void launch_sddmm_live(int dtype, unsigned n_items, hipStream_t st, const SddmmParams& p, const SddmmLive& lv);
 // k_update.hip (sparta_vbs_set_values): new values, nztot floats in the mab layout, into the images of an updatable handle
 void launch_update_copy(hipStream_t st, const float* mab, int64_t n, float* A);        // the reference-layout image (fp32 handles)
 // the fragment image of the fp32 one-tile plan, k-compaction redone per step (position table, fragments, STEP_KPAIRS of steps[q].mt_flags);
@@ -576,6 +604,11 @@ void launch_grad_ctl_finish(hipStream_t st, void* R, float max_norm, float growt
 // keep[b] == 0 stored as +0.0f (all n_all elements) in each non-NULL T[0..3]
 void launch_block_ssq(hipStream_t st, const PruneBlock* blocks, int64_t n_blocks, const float* W, double* ssq);
 void launch_mask_blocks(hipStream_t st, const PruneBlock* blocks, int64_t n_blocks, const uint8_t* keep, float* T0, float* T1, float* T2, float* T3);
+// k_live.hip: the snapshot of keep and the compacted lists, one wave per block-row / per block column, stable, no atomics, no LDS
+void launch_live_sddmm(hipStream_t st, const BlockRowDesc* brows, int64_t n_brows, int w, const uint8_t* keep, int64_t n_blocks, uint8_t* snap, const int32_t* goff,
+                       int32_t* groups, int32_t* count);
+void launch_live_spmm_t(hipStream_t st, const SpmmTItem* items, const SpmmTBlock* blocks, const int32_t* tmap, int64_t block_cols, int panels, const uint8_t* keep,
+                        SpmmTItem* live_items, SpmmTBlock* live_blocks, int32_t* live_ids, int32_t* live_count);
 
 // vbs_plan.cpp
 struct StreamPlanIn {
@@ -656,6 +689,16 @@ int build_spmm_t_index(int64_t cols, int64_t w, int64_t br0, int64_t br1, const 
 // the block table of block pruning: [n_blocks][4] = {offset, n_in, n_all, (block-row - br0) << 32 | block column}; table == nullptr only counts
 int build_block_table(int64_t cols, int64_t w, int64_t br0, int64_t br1, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, int64_t jab_lo,
                       int64_t* table, int64_t* n_blocks);
+// the pattern-only maps of the live-block set for the block-rows [br0, br1): goff[block_rows + 1] = first position of every block-row's slice of the SDDMM group
+// list (a block-row of height 0 has no groups), tptr[block columns + 1] = every block column's slice of the spmm_t list (the ptr of build_spmm_t_index), tmap =
+// list position -> block number (mab order, as build_block_table numbers them); and the rule itself on the host (what k_live.hip computes)
+struct LiveMapsHost {
+    std::vector<int64_t> goff, tptr, first_block;             // first_block[block_rows + 1]: block number of every block-row's first block
+    std::vector<int32_t> tmap;
+    int64_t w = 0;
+};
+int build_live_maps(int64_t cols, int64_t w, int64_t br0, int64_t br1, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, int64_t jab_lo, LiveMapsHost& M);
+void live_lists_host(const LiveMapsHost& M, const uint8_t* keep, int32_t* sd_groups, int32_t* sd_count, int32_t* t_blocks, int32_t* t_count, int64_t* info);
 // one block of the 16-bit image from its column-major h x w source
 void pack_spmm_t_block(const float* blk, int64_t h, int64_t w, bool bf16, uint16_t* dst);
 uint16_t to_h16(float v, bool bf16);   // fp32 -> fp16 / bf16 bits, round to nearest even (what the device conversion kernel does too)

@@ -1159,4 +1159,68 @@ int build_block_table(int64_t cols, int64_t w, int64_t br0, int64_t br1, const i
     return SPARTA_OK;
 }
 
+// ---- the live-block set (k_live.hip): the pattern-only maps and the rule on the host ----------------------------------------------------------
+// The spmm_t list is the one of build_spmm_t_index (counting sort by block column, block-row order inside a column, blocks of height 0 left out), with the
+// block number of every entry next to it.
+int build_live_maps(int64_t cols, int64_t w, int64_t br0, int64_t br1, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, int64_t jab_lo, LiveMapsHost& M) {
+    const int64_t block_cols = (cols - 1) / w + 1, n_br = br1 - br0;
+    M.w = w;
+    M.goff.assign((size_t)n_br + 1, 0);
+    M.first_block.assign((size_t)n_br + 1, 0);
+    M.tptr.assign((size_t)block_cols + 1, 0);
+    int64_t q = 0;
+    for (int64_t ib = br0; ib < br1; ib++) {
+        const int64_t h = row_part[ib + 1] - row_part[ib];
+        M.goff[(size_t)(ib - br0) + 1] = M.goff[(size_t)(ib - br0)] + (h > 0 ? (nzcount[ib] * w + 31) / 32 : 0);
+        for (int64_t b = 0; b < nzcount[ib]; b++, q++) {
+            const int64_t jb = jab[jab_lo + q];
+            if (jb < 0 || jb >= block_cols) return sparta::fail(SPARTA_ERR_INVALID, "sparta_vbs_live_lists_host: jab entry out of range");
+            if (h > 0) M.tptr[(size_t)jb + 1]++;
+        }
+        M.first_block[(size_t)(ib - br0) + 1] = q;
+    }
+    if (q > INT32_MAX || M.goff.back() > INT32_MAX) return sparta::fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_set_live_blocks: more than 2^31 - 1 blocks or groups");
+    for (int64_t j = 0; j < block_cols; j++) M.tptr[(size_t)j + 1] += M.tptr[(size_t)j];
+    M.tmap.assign((size_t)M.tptr.back(), 0);
+    std::vector<int64_t> at(M.tptr.begin(), M.tptr.end() - 1);
+    q = 0;
+    for (int64_t ib = br0; ib < br1; ib++) {
+        const int64_t h = row_part[ib + 1] - row_part[ib];
+        for (int64_t b = 0; b < nzcount[ib]; b++, q++)
+            if (h > 0) M.tmap[(size_t)at[(size_t)jab[jab_lo + q]]++] = (int32_t)q;
+    }
+    return SPARTA_OK;
+}
+
+// Group g of a block-row (stored columns 32 g .. 32 g + 31 of its nb * w) is live iff one of the blocks it overlaps is; the live group numbers go to the front
+// of the block-row's slice in ascending order, -1 behind them.  A block column's live block numbers go to the front of its slice in list order, -1 behind them.
+void live_lists_host(const LiveMapsHost& M, const uint8_t* keep, int32_t* sd_groups, int32_t* sd_count, int32_t* t_blocks, int32_t* t_count, int64_t* info) {
+    const int64_t n_br = (int64_t)M.goff.size() - 1, block_cols = (int64_t)M.tptr.size() - 1, w = M.w;
+    int64_t live_groups = 0, live_entries = 0, live_blocks = 0;
+    for (int64_t b = 0; b < M.first_block.back(); b++) live_blocks += keep[b] != 0;
+    for (int64_t ib = 0; ib < n_br; ib++) {
+        const int64_t g_lo = M.goff[(size_t)ib], ng = M.goff[(size_t)ib + 1] - g_lo, b0 = M.first_block[(size_t)ib], nq = (M.first_block[(size_t)ib + 1] - b0) * w;
+        int64_t n = 0;
+        for (int64_t g = 0; g < ng; g++) {
+            bool live = false;
+            for (int64_t b = 32 * g / w; b <= (std::min(32 * g + 31, nq - 1)) / w; b++) live = live || keep[b0 + b] != 0;
+            if (live) sd_groups[g_lo + n++] = (int32_t)g;
+        }
+        for (int64_t g = n; g < ng; g++) sd_groups[g_lo + g] = -1;
+        sd_count[ib] = (int32_t)n;
+        live_groups += n;
+    }
+    for (int64_t j = 0; j < block_cols; j++) {
+        const int64_t l0 = M.tptr[(size_t)j], l1 = M.tptr[(size_t)j + 1];
+        int64_t n = 0;
+        for (int64_t l = l0; l < l1; l++)
+            if (keep[M.tmap[(size_t)l]] != 0) t_blocks[l0 + n++] = M.tmap[(size_t)l];
+        for (int64_t l = l0 + n; l < l1; l++) t_blocks[l] = -1;
+        t_count[j] = (int32_t)n;
+        live_entries += n;
+    }
+    info[0] = 1; info[1] = M.first_block.back(); info[2] = live_blocks; info[3] = M.goff.back(); info[4] = live_groups; info[5] = M.tptr.back(); info[6] = live_entries;
+    info[7] = 0;
+}
+
 }  // namespace sparta_dev

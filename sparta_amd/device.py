@@ -474,6 +474,50 @@ class DeviceVBS(ValuesRecord):
                     t.add_(0)
         return total if timed else None
 
+    def set_live_blocks(self, keep, stream=None):
+        """sparta_vbs_set_live_blocks: from now on sddmm and spmm_t of this handle skip every block b with keep[b] == 0 -- its gradient is +0.0 (accumulate=
+        False) or left as it is (True), and it adds nothing to spmm_t; the operands are not read on its behalf.  keep: a contiguous uint8 or bool tensor of
+        n_blocks elements on this device, numbered as for mask_blocks; the handle takes a snapshot in stream order (torch's current stream).  keep=None
+        removes the live set.  Nothing else changes: the forward products, set_values and the steps ignore it, so the values of the dead blocks must be
+        zero for forward and backward to agree (BlockPruner does that).  Launches only after the first call on the handle (capturable from then on)."""
+        if keep is None:
+            check(lib.sparta_vbs_set_live_blocks(self.h, None, None))
+            return
+        import torch
+        n = self.n_blocks
+        if not (keep.is_cuda and keep.dtype in (torch.uint8, torch.bool) and keep.device.index == self.device and keep.is_contiguous() and keep.numel() == n):
+            raise ValueError("keep must be a contiguous uint8 or bool tensor of n_blocks = %d elements on device %d" % (n, self.device))
+        st = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+        if n == 0:                                             # (no byte to point at: an all-live set of no blocks is no live set)
+            check(lib.sparta_vbs_set_live_blocks(self.h, None, None))
+            return
+        check(lib.sparta_vbs_set_live_blocks(self.h, C.cast(C.c_void_p(keep.data_ptr()), C.POINTER(C.c_uint8)), C.c_void_p(st)))
+
+    def _live_stream(self, stream):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream)
+
+    def live_info(self, stream=None):
+        """sparta_vbs_live_info (synchronises): {"installed", "n_blocks", "live_blocks", "sd_groups", "live_sd_groups", "t_entries", "live_t_entries"}"""
+        a = np.zeros(8, np.int64)
+        check(lib.sparta_vbs_live_info(self.h, a.ctypes.data_as(_i64p), self._live_stream(stream)))
+        keys = ["installed", "n_blocks", "live_blocks", "sd_groups", "live_sd_groups", "t_entries", "live_t_entries"]
+        return {k: int(a[i]) for i, k in enumerate(keys)}
+
+    def live_lists(self, stream=None):
+        """sparta_vbs_live_lists_get (synchronises; for tests): the compacted lists the kernels walk, as VBR.live_lists returns them for the same keep --
+        {"sd_groups", "sd_count", "t_blocks", "t_count"}, int32 arrays; the last two are empty on a handle made without transposable=True"""
+        li, info = self.live_info(stream), self.info()
+        if not li["installed"]:
+            raise ValueError("no live set is installed")
+        i32p = C.POINTER(C.c_int32)
+        block_cols = (info["cols"] - 1) // info["block_col_size"] + 1
+        out = {"sd_groups": np.zeros(li["sd_groups"], np.int32), "sd_count": np.zeros(info["block_rows"], np.int32),
+               "t_blocks": np.zeros(li["t_entries"], np.int32), "t_count": np.zeros(block_cols if self.transposable else 0, np.int32)}
+        check(lib.sparta_vbs_live_lists_get(self.h, *(out[k].ctypes.data_as(i32p) if out[k].size else None for k in ("sd_groups", "sd_count", "t_blocks", "t_count")),
+                                            self._live_stream(stream)))
+        return out
+
     def set_values_host(self, mab):
         """set_values with a host array (numpy, fp32, nztot elements), staged through scratch of the handle.  Returns kernel ms."""
         mab = np.ascontiguousarray(mab, np.float32).reshape(-1)

@@ -351,6 +351,29 @@ class VBR:
         check(lib.sparta_vbs_block_table_host(*args, table.ctypes.data_as(_i64p), C.byref(n)))
         return table
 
+    def live_lists(self, keep, block_row_range=None):
+        """sparta_vbs_live_lists_host: the lists a handle of the block-rows block_row_range = (b0, b1) (default: all) walks after set_live_blocks(keep), by
+        the host form of the rule (no GPU).  keep: n_blocks bytes in the numbering of block_table (0 = dead).  Returns {"sd_groups", "sd_count", "t_blocks",
+        "t_count"} (int32 arrays, formats in include/sparta_amd.h) and "info": {installed, n_blocks, live blocks, SDDMM groups, live SDDMM groups, spmm_t
+        list entries, live spmm_t list entries, 0}."""
+        b0, b1 = (0, self.block_rows) if block_row_range is None else (int(block_row_range[0]), int(block_row_range[1]))
+        rp, nz, jab = (np.ascontiguousarray(a, np.int64) for a in (self.row_part, self.nzcount, self.jab))
+        keep = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8).reshape(-1)
+        n_blocks = int(nz[b0:b1].sum())
+        if keep.size != n_blocks:
+            raise ValueError("keep must hold n_blocks = %d elements" % n_blocks)
+        args = (self.cols, self.block_rows, self.block_col_size, rp.ctypes.data_as(_i64p), nz.ctypes.data_as(_i64p), jab.ctypes.data_as(_i64p), b0, b1,
+                keep.ctypes.data_as(C.POINTER(C.c_uint8)))
+        info = np.zeros(8, np.int64)
+        check(lib.sparta_vbs_live_lists_host(*args, None, None, None, None, info.ctypes.data_as(_i64p)))
+        block_cols = (int(self.cols) - 1) // int(self.block_col_size) + 1
+        out = {"sd_groups": np.zeros(int(info[3]), np.int32), "sd_count": np.zeros(b1 - b0, np.int32), "t_blocks": np.zeros(int(info[5]), np.int32),
+               "t_count": np.zeros(block_cols, np.int32)}
+        check(lib.sparta_vbs_live_lists_host(*args, *(out[k].ctypes.data_as(_i32p) for k in ("sd_groups", "sd_count", "t_blocks", "t_count")),
+                                             info.ctypes.data_as(_i64p)))
+        out["info"] = info
+        return out
+
     def to_device(self, device=0, dtype=_lib.F32, block_row_range=None, updatable=False, transposable=False):
         from .device import DeviceVBS
         return DeviceVBS(self, device=device, dtype=dtype, block_row_range=block_row_range, updatable=updatable, transposable=transposable)

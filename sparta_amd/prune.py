@@ -51,15 +51,20 @@ class BlockPruner:
     compare, and a ragged last block column is not pruned for being narrow.  scope: "global" ranks the blocks of all pairs together, "layer" each pair alone.
     A pruned block is +0.0 in values, in the optimizer's state and (after mask_grads) in the gradient, and the optimizers' arithmetic keeps it there (W = M =
     V = +0 and g = +-0 give W = +0, with momentum and with either weight decay).  prune, mask_grads and scores are launches and torch device operations only, on
-    torch's current stream; mask_grads can be captured into a graph after its first call (the masks are updated in place)."""
+    torch's current stream; mask_grads can be captured into a graph after its first call (the masks are updated in place).
 
-    def __init__(self, optimizer_or_pairs, scope="global", normalize=True):
+    skip_pruned=True: prune and load_state_dict also hand every handle its mask (DeviceVBS.set_live_blocks), so that the backward products skip the pruned
+    blocks instead of computing them: sddmm stores +0.0 for them and spmm_t leaves them out (their values are zero: the same sum).  A gradient that comes from
+    vbs_linear alone is then already +0 in the pruned blocks and mask_grads() can be dropped from the loop; it is still needed where anything else adds to
+    values.grad (a regulariser, a second use of the values outside vbs_linear)."""
+
+    def __init__(self, optimizer_or_pairs, scope="global", normalize=True, skip_pruned=False):
         import torch
         if scope not in ("global", "layer"):
             raise ValueError("scope must be 'global' or 'layer'")
         self.optimizer = optimizer_or_pairs if hasattr(optimizer_or_pairs, "pairs") else None
         self.pairs = [(h, v) for h, v in (self.optimizer.pairs if self.optimizer is not None else optimizer_or_pairs)]
-        self.scope, self.normalize = scope, bool(normalize)
+        self.scope, self.normalize, self.skip_pruned = scope, bool(normalize), bool(skip_pruned)
         self._keep, self._n_in = [], []
         for handle, values in self.pairs:
             self._keep.append(torch.ones(handle.n_blocks, dtype=torch.uint8, device=values.device))
@@ -90,6 +95,8 @@ class BlockPruner:
         tensors = [values.detach()] + ([values.grad] if values.grad is not None else []) + self._state_tensors(i)
         handle.mask_blocks(self._keep[i], *tensors)
         handle.set_values(values.detach())
+        if self.skip_pruned:
+            handle.set_live_blocks(self._keep[i])
 
     def prune(self, sparsity):
         """select() on scores(), then per pair the pruned blocks zeroed in values, values.grad (if present) and the optimizer's state (where allocated), and
