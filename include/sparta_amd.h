@@ -346,8 +346,19 @@ int sparta_vbs_plan_stats(int64_t rows, int64_t cols, const int64_t* rowptr, con
  *   accumulate = 0 still writes all cols x n_cols elements, zeros where no live block covers a column.  Rows of X that reach a block column only through
  *   dead blocks are not read for it.  Dropping a block removes whole MFMA passes (a pass covers rows of one block only): with finite X the result equals,
  *   up to the sign of a zero, the product without a live set on values whose dead blocks are zero.
- *   Everything else ignores the live set: the forward products, sparta_vbs_set_values, the steps, sparta_vbs_block_ssq, sparta_vbs_mask_blocks.  Keeping
- *   the VALUES of dead blocks at zero stays the caller's job. */
+ *   Everything else ignores the live set: the forward products, sparta_vbs_set_values, the steps (unless live steps are on, below), sparta_vbs_block_ssq,
+ *   sparta_vbs_mask_blocks.  Keeping the VALUES of dead blocks at zero stays the caller's job.
+ *   WITH A LIVE-BLOCK SET INSTALLED AND LIVE STEPS ON (sparta_vbs_set_live_steps), for sparta_vbs_sgd_step, sparta_vbs_adam_step and both _ctl forms, in the
+ *   fused and in the two-pass form:
+ *   Live blocks: every element gets the pinned arithmetic of the plain step and the same bits.
+ *   Dead blocks: G, M and V are neither read nor written -- all n_all elements, the positions past `cols` included -- and W is not written.  Every image the
+ *   step's own kernel writes holds +0.0 for them.  PRECONDITION: W holds +0.0 there, as sparta_vbs_mask_blocks leaves it; the images written by the set_values
+ *   launches that follow the step's kernel (the two-pass form; the image of sparta_vbs_spmm_t of a 16-bit handle) come from W as it stands.  If the
+ *   precondition is broken W, M and V are still untouched, and those images hold whatever W held, rounded.
+ *   The Adam step state: the tick and S are unchanged; a skipped step (R[skip]) behaves as without live steps (W, M, V, S keep their bits; the fused kernel
+ *   still writes +0.0 for dead blocks into its image).
+ *   Equivalence: on tensors whose dead blocks are +0 in W, M, V and G a live step leaves W, M, V, S and every product of the handle bit-identical to the
+ *   plain step (which computes +0 for them: "A zero block stays zero", below). */
 int sparta_vbs_spmm(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int32_t n_cols,
                     void* C, int64_t ldc, int32_t c_layout, int32_t accumulate,
                     int32_t ptr_space, void* stream, int32_t algo, float* dt_ms);
@@ -487,7 +498,8 @@ typedef struct sparta_adam_cfg { float lr, beta1, beta2, eps, weight_decay, grad
 int sparta_vbs_adam_step(sparta_vbs_t* A, float* W, const float* G, float* M, float* V, void* S,
                          const sparta_adam_cfg* cfg, void* stream, float* dt_ms);
 /* info_out[4] = {1 if the last sparta_vbs_sgd_step / sparta_vbs_adam_step on the handle did the arithmetic inside an image kernel, 0 if it took
- * the two-pass form, -1 if no step has run yet; kernel launches of that step (an Adam step counts its tick); 0; 0}. */
+ * the two-pass form, -1 if no step has run yet; kernel launches of that step (an Adam step counts its tick); 1 if that step skipped dead blocks
+ * (sparta_vbs_set_live_steps), else 0; 0}. */
 int sparta_vbs_step_info(const sparta_vbs_t* A, int64_t* info_out);
 
 /* Global-norm gradient clipping and loss scaling with skip-on-overflow, decided on the device: between backward and step nothing comes back to the
@@ -616,13 +628,25 @@ int sparta_vbs_mask_blocks(sparta_vbs_t* A, const uint8_t* keep, float* T0, floa
  *     of sparta_vbs_sddmm takes positions g0 .. g0 + 15 of the slice.
  *   t_blocks[spmm_t list entries], t_count[block columns]: the list of block column jb is its blocks of height > 0 in block-row order; its slice starts at
  *     the sum of the list lengths of the block columns before it and holds the block numbers of its live blocks in that order, t_count[jb] of them, then -1.
- * sparta_vbs_live_info: info_out[8] = {installed, n_blocks, live blocks, SDDMM groups, live SDDMM groups, spmm_t list entries, live spmm_t list entries, 0},
- * the live counts read back from the device (words 2..6 are 0 when no live set is installed, words 5, 6 without SPARTA_CREATE_TRANSPOSE).
+ * sparta_vbs_live_info: info_out[8] = {installed, n_blocks, live blocks, SDDMM groups, live SDDMM groups, spmm_t list entries, live spmm_t list entries, the
+ * live-steps switch}, the live counts read back from the device (words 2..6 are 0 when no live set is installed, words 5, 6 without SPARTA_CREATE_TRANSPOSE).
  * sparta_vbs_live_lists_get: the lists the kernels walk, downloaded (host pointers; any of the four may be NULL); SPARTA_ERR_INVALID without a live set.  Both
  * synchronise the stream and are refused under capture; they are for tests and records.
  * sparta_vbs_live_lists_host: the same rule as host code (no GPU) on VBS arrays and a host keep, arguments as sparta_vbs_block_table_host; any of the four
  * outputs may be NULL (info_out[3] and [5] give the sizes). */
 int sparta_vbs_set_live_blocks(sparta_vbs_t* A, const uint8_t* keep, void* stream);
+/* Live steps: with enable != 0 and a live set installed, sparta_vbs_sgd_step / _adam_step and their _ctl forms skip the dead blocks (the contract: "WITH A
+ * LIVE-BLOCK SET INSTALLED AND LIVE STEPS ON" above).  Opt-in, off at creation.  The switch is host state, read when a step is called (or captured); it has an
+ * effect only while a live set is installed: sparta_vbs_set_live_blocks(A, NULL, ...) puts the steps back on the plain kernels without clearing it, and the
+ * next live set switches them over again.  sparta_vbs_step_info word 2 says what the last step did, sparta_vbs_live_info word 7 is the switch.
+ * On a set that prunes nothing a live step moves the bytes of the plain one: it measured the same, there is nothing to gain.
+ * The FIRST enabling call builds and uploads pattern-only helper arrays (the arrays of the live set if no set was ever installed; on a handle with a fused
+ * image one 32-bit map entry and one 32-bit word per step of the fp32 one-tile plan / two per 16-bit slice) and returns SPARTA_ERR_UNSUPPORTED while the
+ * stream is being captured.  If a set is installed the call launches, on `stream`, the kernel that derives the image kernel's words from the snapshot; from then
+ * on every sparta_vbs_set_live_blocks adds that one launch (none on a handle without a fused image: the two-pass form walks the block table with the snapshot
+ * itself).  No allocation, no synchronisation, capturable after the first call; a replay of set_live_blocks re-reads keep.  enable == 0: host state only.
+ * SPARTA_ERR_UNSUPPORTED on a handle made without SPARTA_CREATE_UPDATABLE and on every handle sparta_vbs_set_live_blocks refuses; SPARTA_ERR_INVALID on NULL. */
+int sparta_vbs_set_live_steps(sparta_vbs_t* A, int32_t enable, void* stream);
 int sparta_vbs_live_info(sparta_vbs_t* A, int64_t* info_out /* [8] */, void* stream);
 int sparta_vbs_live_lists_get(sparta_vbs_t* A, int32_t* sd_groups, int32_t* sd_count, int32_t* t_blocks, int32_t* t_count, void* stream);
 int sparta_vbs_live_lists_host(int64_t cols, int64_t block_rows, int64_t block_col_size, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab,

@@ -82,9 +82,30 @@ __global__ __launch_bounds__(kThreads) void vbs_live_columns_kernel(const SpmmTI
     if (lane == 0) live_count[jb] = n;
 }
 
+// The live words of the image kernels of the steps (sparta_vbs_set_live_steps; k_update_image.inc reads them): word i belongs to one step of the fp32 one-tile
+// plan / to rows 0..31 / rows 32..63 of one 16-bit slice, and wmap[i] is the number of the block that step / half lies in (pattern only, built next to
+// build_live_maps; -1: a half the slice does not have).  A step is 32 columns of ONE block and a slice half kp columns of one block (the planner cuts blocks,
+// whose width is a multiple of 32 wherever an image kernel exists), so all 32 column bits of a word are equal: all ones if the block is live in the snapshot,
+// else zero.  One thread per word, a grid-stride loop, plain 4-byte vector stores, every word written on every call; no atomics, no LDS.  (The name avoids
+// "vbs_live_": the tests count the two compaction kernels by it.)
+__global__ __launch_bounds__(kThreads) void vbs_lvstep_words_kernel(const int32_t* __restrict__ wmap, int64_t n_words, const uint8_t* __restrict__ snap,
+                                                                  uint32_t* __restrict__ words) {
+    const int64_t stride = (int64_t)gridDim.x * kThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n_words; i += stride) {
+        const int32_t b = wmap[i];
+        words[i] = (b >= 0 && snap[b] != 0) ? 0xffffffffu : 0u;
+    }
+}
+
 unsigned live_grid(int64_t waves) { return (unsigned)((waves + kLiveWaves - 1) / kLiveWaves); }
 
 }  // namespace
+
+void launch_live_step_words(hipStream_t st, const int32_t* wmap, int64_t n_words, const uint8_t* snap, uint32_t* words) {
+    if (n_words <= 0) return;
+    const int64_t groups = (n_words + kThreads - 1) / kThreads;
+    hipLaunchKernelGGL(vbs_lvstep_words_kernel, dim3((unsigned)std::min<int64_t>(groups, 65536)), dim3(kThreads), 0, st, wmap, n_words, snap, words);
+}
 
 void launch_live_sddmm(hipStream_t st, const BlockRowDesc* brows, int64_t n_brows, int w, const uint8_t* keep, int64_t n_blocks, uint8_t* snap, const int32_t* goff,
                        int32_t* groups, int32_t* count) {

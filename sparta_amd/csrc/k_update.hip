@@ -13,6 +13,11 @@
 // elementwise vbs_adam_step_kernel, behind the one-wave vbs_adam_tick_kernel that advances S once per step.
 // sparta_vbs_sgd_step_ctl / sparta_vbs_adam_step_ctl reach the same kernels with a control record (k_gradctl.hip) in the value source: its coef multiplies g, its
 // skip flag turns the step into sparta_vbs_set_values(A, W) -- W, M, V, S keep their bits, every image is written from W.
+// LIVE STEPS (sparta_vbs_set_live_steps with a live-block set installed): k_update_image.inc is compiled once more per stepping source (vbs_sgdlive_* /
+// vbs_adamlive_*) with a test in front of the value source -- a lane whose elements lie in a dead block does not call it: no load, no store, +0.0f handed on;
+// the test reads one word per step / per slice half that k_live.hip derives from the snapshot.  The two-pass form walks the block
+// table of k_prune.hip instead of the flat array (vbs_sgdlive_blocks_kernel / vbs_adamlive_blocks_kernel: one wave per block, a dead block costs one byte read).
+// The names avoid "vbs_sgd_" / "vbs_adam_" on purpose: the tests count the plain kernels by those, as "vbs_sdlive_" avoids "sddmm" in k_sddmm.hip.
 // Every kernel writes exactly the elements creation wrote (the slices behind the end of an image keep what creation left there) and reads mab
 // only where the plan says a stored element is: nothing is read past mab + nztot.  Offsets are 64-bit throughout.
 #include "vbs_kernel_common.hpp"
@@ -174,6 +179,69 @@ __global__ __launch_bounds__(kThreads) void vbs_adam_step_kernel(int64_t n, Adam
     for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) { float x[1]; s.step<1>(i, 1, x); }
 }
 
+// ---- the two-pass form of the live steps --------------------------------------------------------------------------------------------------------
+// The block table of k_prune.hip (PruneBlock: first element, n_all elements, mab order) walked as vbs_prune_mask_kernel walks it: one WAVE per block, kPruneWaves
+// to a workgroup, a block never split.  A wave whose block is dead in the snapshot returns after one byte read: nothing of W, G, M, V is read or written, the
+// positions past `cols` included (n_all covers them).  A live block: the elements up to the first 16-byte boundary of W one per lane, the body 16 bytes per
+// lane and access (G, M, V at the same offsets: tensors of one allocator share W's alignment modulo 16; the accesses are right on any 4-byte boundary), the
+// last (n - head) % 4 one per lane.  The arithmetic is sgd_element / adam_element per element: the bits of the flat kernels.
+__device__ __forceinline__ int upd_head(const float* p, int n) {
+    const int to_boundary = (int)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2);
+    return n < to_boundary ? n : to_boundary;
+}
+
+__global__ __launch_bounds__(kThreads) void vbs_sgdlive_blocks_kernel(const PruneBlock* __restrict__ blocks, int64_t n_blocks, const uint8_t* __restrict__ keep, SgdStep s) {
+    const int64_t b = (int64_t)blockIdx.x * kPruneWaves + (threadIdx.x >> 6);
+    if (b >= n_blocks || keep[b] == 0 || s.skip()) return;      // (the whole wave)
+    const int lane = threadIdx.x & 63;
+    const PruneBlock blk = blocks[b];
+    const int n = blk.n_all, head = upd_head(s.W + blk.off, n), n4 = (n - head) >> 2;
+    const int64_t body = blk.off + head;
+    const bool mom = s.c.momentum != 0.0f, ctl = s.R != nullptr;
+    const float cf = s.coef();
+    for (int i = lane; i < n4; i += 64) {
+        f32x4 w = *reinterpret_cast<const f32x4u*>(s.W + body + 4 * i);
+        const f32x4 g = *reinterpret_cast<const f32x4u*>(s.G + body + 4 * i);
+        f32x4 m = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (mom) m = *reinterpret_cast<const f32x4u*>(s.M + body + 4 * i);
+#pragma unroll
+        for (int e = 0; e < 4; e++) { float me = m[e]; w[e] = sgd_element(s.c, ctl, cf, w[e], g[e], me); m[e] = me; }
+        if (mom) *reinterpret_cast<f32x4u*>(s.M + body + 4 * i) = m;
+        *reinterpret_cast<f32x4u*>(s.W + body + 4 * i) = w;
+    }
+    float x[1];
+    if (lane < head) s.step<1>(blk.off + lane, 1, x);
+    const int t = head + 4 * n4 + lane;
+    if (t < n) s.step<1>(blk.off + t, 1, x);
+}
+
+__global__ __launch_bounds__(kThreads) void vbs_adamlive_blocks_kernel(const PruneBlock* __restrict__ blocks, int64_t n_blocks, const uint8_t* __restrict__ keep, AdamStep s) {
+    const int64_t b = (int64_t)blockIdx.x * kPruneWaves + (threadIdx.x >> 6);
+    if (b >= n_blocks || keep[b] == 0 || s.skip()) return;      // (the whole wave)
+    const int lane = threadIdx.x & 63;
+    const PruneBlock blk = blocks[b];
+    const int n = blk.n_all, head = upd_head(s.W + blk.off, n), n4 = (n - head) >> 2;
+    const int64_t body = blk.off + head;
+    const bool ctl = s.R != nullptr;
+    const float cf = s.coef();
+    const float step_size = s.S[3], d = s.S[4];
+    for (int i = lane; i < n4; i += 64) {
+        f32x4 w = *reinterpret_cast<const f32x4u*>(s.W + body + 4 * i);
+        const f32x4 g = *reinterpret_cast<const f32x4u*>(s.G + body + 4 * i);
+        f32x4 m = *reinterpret_cast<const f32x4u*>(s.M + body + 4 * i);
+        f32x4 v = *reinterpret_cast<const f32x4u*>(s.V + body + 4 * i);
+#pragma unroll
+        for (int e = 0; e < 4; e++) { float me = m[e], ve = v[e]; w[e] = adam_element(s.c, ctl, cf, step_size, d, w[e], g[e], me, ve); m[e] = me; v[e] = ve; }
+        *reinterpret_cast<f32x4u*>(s.M + body + 4 * i) = m;
+        *reinterpret_cast<f32x4u*>(s.V + body + 4 * i) = v;
+        *reinterpret_cast<f32x4u*>(s.W + body + 4 * i) = w;
+    }
+    float x[1];
+    if (lane < head) s.step<1>(blk.off + lane, 1, x);
+    const int t = head + 4 * n4 + lane;
+    if (t < n) s.step<1>(blk.off + t, 1, x);
+}
+
 __global__ __launch_bounds__(kThreads) void vbs_update_copy_kernel(const float* __restrict__ mab, int64_t n, float* __restrict__ A) {
     const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * kThreads;
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += stride)      // (the caller's array may start on any 4-byte boundary)
@@ -202,6 +270,15 @@ __device__ __forceinline__ uint32_t upd_h16(float v) {
 #include "k_update_image.inc"
 #undef UPD_SOURCE
 #define UPD_SOURCE 2
+#include "k_update_image.inc"
+#undef UPD_SOURCE
+// ... and the live form of the two stepping sources
+#define UPD_SOURCE 1
+#define UPD_LIVE 1
+#include "k_update_image.inc"
+#undef UPD_SOURCE
+#define UPD_SOURCE 2
+#define UPD_LIVE 1
 #include "k_update_image.inc"
 #undef UPD_SOURCE
 
@@ -258,7 +335,26 @@ void launch_adam_h16_t(int tms, int kp, hipStream_t st, const UpdSlice* map, int
     else hipLaunchKernelGGL((vbs_adam_h16_kernel<BF16, 64, 64>), dim3(upd_grid(n_slices * 2)), block, 0, st, map, n_slices, vs, dst);
 }
 
+template <bool BF16>
+void launch_sgd_h16_live_t(int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, const SgdStep& vs, uint16_t* dst, const uint32_t* words) {   // the grids of launch_update_h16_t
+    const dim3 block(kThreads);
+    if (tms == 32 && kp == 32) hipLaunchKernelGGL((vbs_sgdlive_h16_kernel<BF16, 32, 32>), dim3(upd_grid((n_slices + 1) / 2)), block, 0, st, map, n_slices, vs, dst, words);
+    else if (tms == 64 && kp == 32) hipLaunchKernelGGL((vbs_sgdlive_h16_kernel<BF16, 64, 32>), dim3(upd_grid(n_slices)), block, 0, st, map, n_slices, vs, dst, words);
+    else if (tms == 32 && kp == 64) hipLaunchKernelGGL((vbs_sgdlive_h16_kernel<BF16, 32, 64>), dim3(upd_grid(n_slices)), block, 0, st, map, n_slices, vs, dst, words);
+    else hipLaunchKernelGGL((vbs_sgdlive_h16_kernel<BF16, 64, 64>), dim3(upd_grid(n_slices * 2)), block, 0, st, map, n_slices, vs, dst, words);
+}
+
+template <bool BF16>
+void launch_adam_h16_live_t(int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, const AdamStep& vs, uint16_t* dst, const uint32_t* words) {
+    const dim3 block(kThreads);
+    if (tms == 32 && kp == 32) hipLaunchKernelGGL((vbs_adamlive_h16_kernel<BF16, 32, 32>), dim3(upd_grid((n_slices + 1) / 2)), block, 0, st, map, n_slices, vs, dst, words);
+    else if (tms == 64 && kp == 32) hipLaunchKernelGGL((vbs_adamlive_h16_kernel<BF16, 64, 32>), dim3(upd_grid(n_slices)), block, 0, st, map, n_slices, vs, dst, words);
+    else if (tms == 32 && kp == 64) hipLaunchKernelGGL((vbs_adamlive_h16_kernel<BF16, 32, 64>), dim3(upd_grid(n_slices)), block, 0, st, map, n_slices, vs, dst, words);
+    else hipLaunchKernelGGL((vbs_adamlive_h16_kernel<BF16, 64, 64>), dim3(upd_grid(n_slices * 2)), block, 0, st, map, n_slices, vs, dst, words);
+}
+
 SgdStep sgd_source(float* W, const float* G, float* M, const SgdCfg& cfg, const uint32_t* R) { return SgdStep{W, G, cfg.momentum != 0.0f ? M : nullptr, cfg, R}; }
+unsigned blocks_grid(int64_t n_blocks) { return (unsigned)((n_blocks + kPruneWaves - 1) / kPruneWaves); }
 
 }  // namespace
 
@@ -326,6 +422,46 @@ void launch_adam_h16(bool bf16, int tms, int kp, hipStream_t st, const UpdSlice*
     const AdamStep vs{a.W, a.G, a.M, a.V, a.S, a.c, a.R};
     if (bf16) launch_adam_h16_t<true>(tms, kp, st, map, n_slices, vs, dst);
     else launch_adam_h16_t<false>(tms, kp, st, map, n_slices, vs, dst);
+}
+
+
+// ---- the live forms (sparta_vbs_set_live_steps) -------------------------------------------------------------------------------------------
+void launch_sgd_blocks_live(hipStream_t st, const PruneBlock* blocks, int64_t n_blocks, const uint8_t* keep, float* W, const float* G, float* M, const SgdCfg& cfg,
+                            const uint32_t* R) {
+    if (n_blocks <= 0) return;
+    hipLaunchKernelGGL(vbs_sgdlive_blocks_kernel, dim3(blocks_grid(n_blocks)), dim3(kThreads), 0, st, blocks, n_blocks, keep, sgd_source(W, G, M, cfg, R));
+}
+
+void launch_sgd_f32_frag_live(hipStream_t st, StepRec* steps, int64_t n_steps, float* W, const float* G, float* M, const SgdCfg& cfg, const uint32_t* R, float* a_frag,
+                              float* A_out, const uint32_t* words) {
+    if (n_steps <= 0) return;
+    hipLaunchKernelGGL(vbs_sgdlive_f32_frag_kernel, dim3(upd_grid((n_steps + kThreads / 64 - 1) / (kThreads / 64))), dim3(kThreads), 0, st, steps, n_steps,
+                       sgd_source(W, G, M, cfg, R), a_frag, A_out, words);
+}
+
+void launch_sgd_h16_live(bool bf16, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, float* W, const float* G, float* M, const SgdCfg& cfg,
+                         const uint32_t* R, uint16_t* dst, const uint32_t* words) {
+    if (n_slices <= 0) return;
+    if (bf16) launch_sgd_h16_live_t<true>(tms, kp, st, map, n_slices, sgd_source(W, G, M, cfg, R), dst, words);
+    else launch_sgd_h16_live_t<false>(tms, kp, st, map, n_slices, sgd_source(W, G, M, cfg, R), dst, words);
+}
+
+void launch_adam_blocks_live(hipStream_t st, const PruneBlock* blocks, int64_t n_blocks, const uint8_t* keep, const AdamArgs& a) {
+    if (n_blocks <= 0) return;
+    hipLaunchKernelGGL(vbs_adamlive_blocks_kernel, dim3(blocks_grid(n_blocks)), dim3(kThreads), 0, st, blocks, n_blocks, keep, AdamStep{a.W, a.G, a.M, a.V, a.S, a.c, a.R});
+}
+
+void launch_adam_f32_frag_live(hipStream_t st, StepRec* steps, int64_t n_steps, const AdamArgs& a, float* a_frag, float* A_out, const uint32_t* words) {
+    if (n_steps <= 0) return;
+    hipLaunchKernelGGL(vbs_adamlive_f32_frag_kernel, dim3(upd_grid((n_steps + kThreads / 64 - 1) / (kThreads / 64))), dim3(kThreads), 0, st, steps, n_steps,
+                       AdamStep{a.W, a.G, a.M, a.V, a.S, a.c, a.R}, a_frag, A_out, words);
+}
+
+void launch_adam_h16_live(bool bf16, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, const AdamArgs& a, uint16_t* dst, const uint32_t* words) {
+    if (n_slices <= 0) return;
+    const AdamStep vs{a.W, a.G, a.M, a.V, a.S, a.c, a.R};
+    if (bf16) launch_adam_h16_live_t<true>(tms, kp, st, map, n_slices, vs, dst, words);
+    else launch_adam_h16_live_t<false>(tms, kp, st, map, n_slices, vs, dst, words);
 }
 
 }  // namespace sparta_dev

@@ -4,14 +4,37 @@
 //                  registers, W (and M) stored, the new weights returned (sparta_vbs_sgd_step, where the kernel's image holds every stored element exactly once)
 //   UPD_SOURCE 2   vbs_adam_f32_frag_kernel / vbs_adam_h16_kernel: the same with AdamStep::step -- W, G, M, V loaded, W, M, V stored (sparta_vbs_adam_step)
 // Everything behind the loads -- ballot, k-compaction, rounding, placement -- is the same text.
-#if UPD_SOURCE == 1
+// UPD_LIVE (defined to 1 around an inclusion with UPD_SOURCE 1 or 2): the live form of the two stepping kernels, vbs_sgdlive_* / vbs_adamlive_*.  One more
+// argument, live_words (k_live.hip writes it from the snapshot of the live set): one 32-bit word per step (fp32) / two per slice, its rows 0..31 and its rows
+// 32..63 (16-bit: the two block-rows of a pair tile; twice the same block for an ordinary 64-row tile); bit k & 31 says "column k of the step / of those rows
+// of the slice lies in a live block".  Wherever an image kernel exists the block width is a multiple of 32: a step is 32 columns of ONE block and a 16-byte chunk 8 columns of one block, so the 16 (8) elements of a lane share one bit (the host refuses to build
+// the words otherwise) and the lane tests the bit of its first column: dead, it does not call the value source at all -- nothing loaded, nothing stored, its
+// values stay the +0.0f they were initialised to -- and the ballot, the k-compaction and the rounding see zero columns.  Live, it runs the unchanged
+// loads-first / arithmetic / stores text of step<N>.  (A test per element inside step<16> was tried first: 328 registers against 248 in the Adam kernel.)
+#ifndef UPD_LIVE
+#define UPD_LIVE 0
+#endif
+#if UPD_SOURCE == 1 && !UPD_LIVE
 #define UPD_STEP SgdStep
 #define UPD_FRAG_KERNEL vbs_sgd_f32_frag_kernel
 #define UPD_H16_KERNEL vbs_sgd_h16_kernel
-#elif UPD_SOURCE == 2
+#elif UPD_SOURCE == 2 && !UPD_LIVE
 #define UPD_STEP AdamStep
 #define UPD_FRAG_KERNEL vbs_adam_f32_frag_kernel
 #define UPD_H16_KERNEL vbs_adam_h16_kernel
+#elif UPD_SOURCE == 1
+#define UPD_STEP SgdStep
+#define UPD_FRAG_KERNEL vbs_sgdlive_f32_frag_kernel
+#define UPD_H16_KERNEL vbs_sgdlive_h16_kernel
+#elif UPD_SOURCE == 2
+#define UPD_STEP AdamStep
+#define UPD_FRAG_KERNEL vbs_adamlive_f32_frag_kernel
+#define UPD_H16_KERNEL vbs_adamlive_h16_kernel
+#endif
+#if UPD_LIVE
+#define UPD_LIVE_ARG , const uint32_t* __restrict__ live_words
+#else
+#define UPD_LIVE_ARG
 #endif
 
 // The forward of vbs_f32_legacy_from_frag_kernel.  One wave per step q of the one-tile plan (four steps per workgroup and pass): lane = (row m = lane & 31,
@@ -25,7 +48,7 @@
 __global__ __launch_bounds__(kThreads) void vbs_update_f32_frag_kernel(StepRec* steps, int64_t n_steps, const float* __restrict__ mab, float* __restrict__ a_frag,
                                                                        float* __restrict__ A_out) {
 #else
-__global__ __launch_bounds__(kThreads) void UPD_FRAG_KERNEL(StepRec* steps, int64_t n_steps, UPD_STEP vs, float* __restrict__ a_frag, float* __restrict__ A_out) {
+__global__ __launch_bounds__(kThreads) void UPD_FRAG_KERNEL(StepRec* steps, int64_t n_steps, UPD_STEP vs, float* __restrict__ a_frag, float* __restrict__ A_out UPD_LIVE_ARG) {
 #endif
     __shared__ float img[kThreads / 64][32 * 32];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, m = lane & 31, g = lane >> 5;
@@ -49,7 +72,11 @@ __global__ __launch_bounds__(kThreads) void UPD_FRAG_KERNEL(StepRec* steps, int6
 #else
 #pragma unroll
         for (int i = 0; i < 16; i++) v[i] = 0.0f;
+#if UPD_LIVE
+        if (m < mt && ((live_words[q] >> g) & 1u) != 0u) vs.step<16>(a_off + (int64_t)g * h + m, 2 * h, v);     // (m < mt implies active; bit g: the lane's first column)
+#else
         if (m < mt) vs.step<16>(a_off + (int64_t)g * h + m, 2 * h, v);         // element (m, k = 2 i + g), i = 0..15
+#endif
 #pragma unroll
         for (int i = 0; i < 16; i++) {
             const unsigned long long b = __ballot(v[i] != 0.0f);
@@ -94,7 +121,7 @@ template <bool BF16, bool HUB, int TMS, int KP>
 __global__ __launch_bounds__(kThreads) void vbs_update_h16_kernel(const UpdSlice* __restrict__ map, int64_t n_slices, const float* __restrict__ mab, uint16_t* __restrict__ dst) {
 #else
 template <bool BF16, int TMS, int KP>
-__global__ __launch_bounds__(kThreads) void UPD_H16_KERNEL(const UpdSlice* __restrict__ map, int64_t n_slices, UPD_STEP vs, uint16_t* __restrict__ dst) {
+__global__ __launch_bounds__(kThreads) void UPD_H16_KERNEL(const UpdSlice* __restrict__ map, int64_t n_slices, UPD_STEP vs, uint16_t* __restrict__ dst UPD_LIVE_ARG) {
     constexpr bool HUB = false;
 #endif
     constexpr int kChunks = TMS * KP / 8;
@@ -102,6 +129,20 @@ __global__ __launch_bounds__(kThreads) void UPD_H16_KERNEL(const UpdSlice* __res
     for (int64_t id = (int64_t)blockIdx.x * kThreads + threadIdx.x; id < total; id += stride) {
         const int64_t s = id / kChunks;
         const int c = (int)(id % kChunks), kc = c / TMS, rr = c % TMS;
+#if UPD_LIVE
+        // a chunk of a dead block is zeros, as a row the map does not cover: stored at once, in front of everything the live path holds in registers (rr >> 5: rows
+        // 0..31 or 32..63 of the slice; stepping sources have no hub form, so the chunk's place is c * 8)
+        uint32_t lw;
+        if constexpr (kChunks % kThreads == 0) {                // 64-row slices: the kThreads chunks of a workgroup's pass lie in ONE slice, s is uniform and its
+            const uint32_t su = __builtin_amdgcn_readfirstlane((uint32_t)(2 * s));      // two words come through the scalar cache (a plan has fewer than 2^31 slices)
+            const uint32_t w0 = live_words[su], w1 = live_words[su + 1u];
+            lw = rr >= 32 ? w1 : w0;
+        } else lw = live_words[(uint32_t)(2 * s) + (uint32_t)(rr >> 5)];
+        if (((lw >> ((kc * 8) & 31)) & 1u) == 0u) {
+            *reinterpret_cast<u32x4*>(dst + s * (int64_t)(TMS * KP) + c * 8) = u32x4{0u, 0u, 0u, 0u};
+            continue;
+        }
+#endif
         const UpdSlice u = map[s];
 #if UPD_SOURCE == 0
         const float* src = nullptr;
@@ -135,3 +176,5 @@ __global__ __launch_bounds__(kThreads) void UPD_H16_KERNEL(const UpdSlice* __res
 #undef UPD_FRAG_KERNEL
 #undef UPD_H16_KERNEL
 #endif
+#undef UPD_LIVE_ARG
+#undef UPD_LIVE

@@ -136,6 +136,8 @@ void destroy_impl(sparta_vbs* v) {
     if (v->d_live_tcount) (void)hipFree(v->d_live_tcount);
     if (v->d_live_t_blocks) (void)hipFree(v->d_live_t_blocks);
     if (v->d_live_t_items) (void)hipFree(v->d_live_t_items);
+    if (v->d_live_wmap) (void)hipFree(v->d_live_wmap);
+    if (v->d_live_words) (void)hipFree(v->d_live_words);
     if (v->d_t_items) (void)hipFree(v->d_t_items);
     if (v->d_t_blocks) (void)hipFree(v->d_t_blocks);
     if (v->d_t_A) (void)hipFree(v->d_t_A);
@@ -2482,6 +2484,10 @@ int sgd_fused_image(const sparta_vbs_t* A) {
 // image kernel measured faster than the elementwise kernel + the set_values launches, and than the same update as torch ops + set_values, with and without
 // momentum, fp32 and f16.  SPARTA_SGD_FUSE=0 asks for the two-pass form on every step, 1 is the default spelled out.  Read at every
 // call (no plan depends on it): scripts/sgd_step_record.py and the tests drive both forms of one handle in one process.
+// Live steps (sparta_vbs_set_live_steps): the switch counts only while a live set is installed; read when a step is called or captured.  The image kernels'
+// words exist then: the enabling call built them, and every set_live_blocks since rewrote them behind the snapshot.
+bool live_steps_active(const sparta_vbs_t* A) { return A->live_on && A->live_steps && A->live_steps_built; }
+
 bool sgd_fuse_wanted() {
     const char* e = std::getenv("SPARTA_SGD_FUSE");
     return !e || atoi(e) != 0;
@@ -2505,24 +2511,31 @@ int sgd_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G, 
     if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
     int launches = 0;
     int fused = -1;
+    bool live = false;
     if (A->nztot > 0) {
         const SgdCfg c{cfg->lr, cfg->momentum, cfg->weight_decay, cfg->grad_scale};
         const uint32_t* ctl = (const uint32_t*)R;
         if (sgd_fuse_wanted()) fused = sgd_fused_image(A);
+        live = live_steps_active(A);
         if (fused >= 0 && A->dtype == SPARTA_F32) {
-            launch_sgd_f32_frag(st, A->d_steps[0], A->n_steps[0], W, G, M, c, ctl, A->d_a_frag, A->d_A);
+            if (live) launch_sgd_f32_frag_live(st, A->d_steps[0], A->n_steps[0], W, G, M, c, ctl, A->d_a_frag, A->d_A, A->d_live_words);
+            else launch_sgd_f32_frag(st, A->d_steps[0], A->n_steps[0], W, G, M, c, ctl, A->d_a_frag, A->d_A);
             launches = 1;
         } else if (fused >= 0) {
             const bool bf16 = A->dtype == SPARTA_BF16;
-            launch_sgd_h16(bf16, fused ? 64 : 32, A->kp16, st, A->d_upd_map[fused], A->n_steps[fused], W, G, M, c, ctl, (uint16_t*)A->d_A + A->upd_base[fused]);
+            uint16_t* dst = (uint16_t*)A->d_A + A->upd_base[fused];
+            if (live) launch_sgd_h16_live(bf16, fused ? 64 : 32, A->kp16, st, A->d_upd_map[fused], A->n_steps[fused], W, G, M, c, ctl, dst, A->d_live_words);
+            else launch_sgd_h16(bf16, fused ? 64 : 32, A->kp16, st, A->d_upd_map[fused], A->n_steps[fused], W, G, M, c, ctl, dst);
             launches = 1;
             if (A->n_t_src > 0) { launch_update_h16_t(bf16, st, A->d_t_src, A->n_t_src, (int)A->w, W, A->d_t_A); launches++; }   // reads the W written above
         } else {
-            launch_sgd_step(st, A->nztot, W, G, M, c, ctl);
+            if (live) launch_sgd_blocks_live(st, A->d_prune, A->n_prune, A->d_live_keep, W, G, M, c, ctl);
+            else launch_sgd_step(st, A->nztot, W, G, M, c, ctl);
             launches = 1 + launch_images_from(A, st, W);
         }
         HIP_TRY(hipGetLastError());
     }
+    A->step_last_live = live ? 1 : 0;
     A->step_last_fused = fused >= 0 ? 1 : 0;
     A->step_last_launches = launches;
     if (dt_ms) {
@@ -2582,6 +2595,7 @@ int adam_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G,
     if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
     int launches = 0;
     int fused = -1;
+    bool live = false;
     if (A->nztot > 0) {
         // the three derived constants, each operation rounded once to fp32 (volatile: no contraction, no wider intermediate)
         volatile float omb1 = 1.0f - cfg->beta1, omb2 = 1.0f - cfg->beta2, lr_wd = cfg->lr * cfg->weight_decay;
@@ -2589,22 +2603,28 @@ int adam_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G,
         const AdamArgs a{W, G, M, V, (float*)S,
                          AdamCfg{cfg->lr, cfg->beta1, cfg->beta2, cfg->eps, cfg->weight_decay, cfg->grad_scale, omb1, omb2, dk, cfg->decoupled != 0 ? 1 : 0}, (const uint32_t*)R};
         if (adam_fuse_wanted()) fused = sgd_fused_image(A);
+        live = live_steps_active(A);
         launch_adam_tick(st, a);
         launches = 1;
         if (fused >= 0 && A->dtype == SPARTA_F32) {
-            launch_adam_f32_frag(st, A->d_steps[0], A->n_steps[0], a, A->d_a_frag, A->d_A);
+            if (live) launch_adam_f32_frag_live(st, A->d_steps[0], A->n_steps[0], a, A->d_a_frag, A->d_A, A->d_live_words);
+            else launch_adam_f32_frag(st, A->d_steps[0], A->n_steps[0], a, A->d_a_frag, A->d_A);
             launches++;
         } else if (fused >= 0) {
             const bool bf16 = A->dtype == SPARTA_BF16;
-            launch_adam_h16(bf16, fused ? 64 : 32, A->kp16, st, A->d_upd_map[fused], A->n_steps[fused], a, (uint16_t*)A->d_A + A->upd_base[fused]);
+            uint16_t* dst = (uint16_t*)A->d_A + A->upd_base[fused];
+            if (live) launch_adam_h16_live(bf16, fused ? 64 : 32, A->kp16, st, A->d_upd_map[fused], A->n_steps[fused], a, dst, A->d_live_words);
+            else launch_adam_h16(bf16, fused ? 64 : 32, A->kp16, st, A->d_upd_map[fused], A->n_steps[fused], a, dst);
             launches++;
             if (A->n_t_src > 0) { launch_update_h16_t(bf16, st, A->d_t_src, A->n_t_src, (int)A->w, W, A->d_t_A); launches++; }   // reads the W written above
         } else {
-            launch_adam_step(st, A->nztot, a);
+            if (live) launch_adam_blocks_live(st, A->d_prune, A->n_prune, A->d_live_keep, a);
+            else launch_adam_step(st, A->nztot, a);
             launches += 1 + launch_images_from(A, st, W);
         }
         HIP_TRY(hipGetLastError());
     }
+    A->step_last_live = live ? 1 : 0;
     A->step_last_fused = fused >= 0 ? 1 : 0;
     A->step_last_launches = launches;
     if (dt_ms) {
@@ -2684,7 +2704,7 @@ extern "C" int sparta_grad_ctl_finish(void* R, const sparta_grad_ctl_cfg* cfg, v
 
 extern "C" int sparta_vbs_step_info(const sparta_vbs_t* A, int64_t* info_out) {
     if (!A || !info_out) return sparta::fail(SPARTA_ERR_INVALID, "sparta_vbs_step_info: NULL argument");
-    info_out[0] = A->step_last_fused; info_out[1] = A->step_last_launches; info_out[2] = 0; info_out[3] = 0;
+    info_out[0] = A->step_last_fused; info_out[1] = A->step_last_launches; info_out[2] = A->step_last_live; info_out[3] = 0;
     return SPARTA_OK;
 }
 
@@ -2848,7 +2868,73 @@ int ensure_live_arrays(sparta_vbs_t* A, const char* entry) {
     return SPARTA_OK;
 }
 
+// the pattern-only map of the live words (handles with a fused image only): word -> block number, from the block table and the plan's own records of where
+// a step / a slice half starts in mab.  Built once, at the first enabling sparta_vbs_set_live_steps.
+int ensure_live_step_arrays(sparta_vbs_t* A, const char* entry) {
+    using sparta::fail;
+    if (A->live_steps_built) return SPARTA_OK;
+    if (g_capturing) return capture_refusal("build and upload the helper arrays of the live steps", entry);
+    if (int rc = ensure_live_arrays(A, entry)) return rc;
+    const int ty = sgd_fused_image(A);
+    if (ty >= 0 && A->nztot > 0) {
+        const int64_t nb = A->n_prune;
+        std::vector<PruneBlock> tab((size_t)nb);
+        if (nb > 0) HIP_TRY(hipMemcpy(tab.data(), A->d_prune, (size_t)nb * sizeof(PruneBlock), hipMemcpyDeviceToHost));
+        std::vector<int64_t> off((size_t)nb);
+        for (int64_t b = 0; b < nb; b++) off[(size_t)b] = tab[(size_t)b].off;
+        std::vector<int64_t> first;
+        std::vector<int32_t> ld;
+        int64_t span = SK_KP;
+        if (A->dtype == SPARTA_F32) {                       // one word per step: its 32 columns start at a_off, h apart
+            for (int64_t q = 0; q < A->n_steps[0]; q++) { first.push_back(A->h_steps[0][(size_t)q].a_off); ld.push_back(A->h_steps[0][(size_t)q].h); }
+        } else {                                            // two words per slice: the kp columns of its rows 0..31 and of its rows 32..63 -- the upper and the
+                                                            // lower block-row of a pair tile (rows_lo = 32 or 0), the one block of an ordinary tile (rows_hi = 0)
+            std::vector<UpdSlice> map((size_t)A->n_steps[ty]);
+            HIP_TRY(hipMemcpy(map.data(), A->d_upd_map[ty], map.size() * sizeof(UpdSlice), hipMemcpyDeviceToHost));
+            span = A->kp16;
+            for (const UpdSlice& u : map) {
+                first.push_back(u.rows_lo > 0 ? u.off_lo : -1); ld.push_back(u.h_lo);
+                if (u.rows_hi > 0) { first.push_back(u.off_hi); ld.push_back(u.h_hi); }
+                else { first.push_back(u.rows_lo > 32 ? u.off_lo : -1); ld.push_back(u.h_lo); }
+            }
+        }
+        std::vector<int32_t> wmap(first.size());
+        if (int rc = build_live_word_map(off.data(), nb, A->nztot, first.data(), ld.data(), (int64_t)first.size(), span, wmap.data())) return rc;
+        A->live_n_words = (int64_t)wmap.size();
+        HIP_TRY(hipMalloc((void**)&A->d_live_wmap, std::max<size_t>(wmap.size() * sizeof(int32_t), 16)));
+        HIP_TRY(hipMalloc((void**)&A->d_live_words, std::max<size_t>(wmap.size() * sizeof(uint32_t), 16)));
+        if (!wmap.empty()) HIP_TRY(hipMemcpy(A->d_live_wmap, wmap.data(), wmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    A->live_steps_built = true;
+    return SPARTA_OK;
+}
+
 }  // namespace
+
+extern "C" int sparta_vbs_set_live_steps(sparta_vbs_t* A, int32_t enable, void* stream) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* entry = "sparta_vbs_set_live_steps";
+    if (int rc = prune_handle_check(A, entry)) return rc;
+    if (!(A->create_flags & SPARTA_CREATE_UPDATABLE))
+        return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the handle was not made with SPARTA_CREATE_UPDATABLE (it takes no steps)");
+    if (!enable) {                               // host state only
+        A->live_steps = false;
+        return SPARTA_OK;
+    }
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, true);
+    if (int rc = ensure_live_step_arrays(A, entry)) return rc;
+    if (A->live_on && A->live_n_words > 0) {     // a set is installed already: the words follow from its snapshot
+        launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
+        HIP_TRY(hipGetLastError());
+    }
+    A->live_steps = true;
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_vbs_set_live_steps")
+}
 
 extern "C" int sparta_vbs_set_live_blocks(sparta_vbs_t* A, const uint8_t* keep, void* stream) {
     SPARTA_GUARD_BEGIN
@@ -2868,6 +2954,8 @@ extern "C" int sparta_vbs_set_live_blocks(sparta_vbs_t* A, const uint8_t* keep, 
     if (A->create_flags & SPARTA_CREATE_TRANSPOSE)
         launch_live_spmm_t(st, A->d_t_items, A->d_t_blocks, A->d_live_tmap, A->live_block_cols, (int)((A->w + 31) / 32), keep, A->d_live_t_items, A->d_live_t_blocks,
                            A->d_live_tids, A->d_live_tcount);
+    // live steps: the words of the image kernel behind the snapshot, in stream order (written whether or not the switch is on right now, once they exist)
+    if (A->live_steps_built && A->live_n_words > 0) launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
     HIP_TRY(hipGetLastError());
     A->live_on = true;
     return SPARTA_OK;
@@ -2905,6 +2993,7 @@ extern "C" int sparta_vbs_live_info(sparta_vbs_t* A, int64_t* info_out, void* st
     if (!info_out) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": NULL argument");
     std::memset(info_out, 0, 8 * sizeof(int64_t));
     info_out[1] = A->nblocks;
+    info_out[7] = A->live_steps ? 1 : 0;
     if (!A->live_on) return SPARTA_OK;
     DeviceGuard guard(A->device);
     if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");

@@ -522,6 +522,14 @@ struct sparta_vbs {
     sparta_dev::SpmmTBlock* d_live_t_blocks = nullptr;         // d_t_blocks, every block column's live records first
     sparta_dev::SpmmTItem* d_live_t_items = nullptr;           // d_t_items with l1 = l0 + live count
     int64_t live_n_tlist = 0, live_block_cols = 0;
+    // live steps (sparta_vbs_set_live_steps): the switch is host state and acts only while a live set is installed.  Handles with a fused image hold one
+    // word per step (fp32) / two per slice (16-bit) for its kernel: the map word -> block number is pattern only (built at the first enabling call), the words
+    // are written from the snapshot by one launch of k_live.hip.  The two-pass form needs nothing of its own: it walks d_prune with d_live_keep.
+    bool live_steps = false, live_steps_built = false;
+    int32_t* d_live_wmap = nullptr;                            // [live_n_words]
+    uint32_t* d_live_words = nullptr;                          // [live_n_words]
+    int64_t live_n_words = 0;
+    int32_t step_last_live = 0;                                // the last step skipped dead blocks (sparta_vbs_step_info word 2)
 };
 
 namespace sparta_dev {
@@ -591,6 +599,18 @@ void launch_adam_tick(hipStream_t st, const AdamArgs& a);
 void launch_adam_step(hipStream_t st, int64_t n, const AdamArgs& a);
 void launch_adam_f32_frag(hipStream_t st, StepRec* steps, int64_t n_steps, const AdamArgs& a, float* a_frag, float* A_out);
 void launch_adam_h16(bool bf16, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, const AdamArgs& a, uint16_t* dst);
+// the live forms (sparta_vbs_set_live_steps with a live set installed).  Image kernels: `words` = the live words of launch_live_step_words, one per step / two per
+// slice; a step or chunk of a dead block is neither loaded nor stored and its part of the image is +0.0.  Two-pass: the block table and the snapshot, one wave
+// per block, dead blocks untouched; the set_values launches follow as behind launch_sgd_step / launch_adam_step
+void launch_sgd_blocks_live(hipStream_t st, const PruneBlock* blocks, int64_t n_blocks, const uint8_t* keep, float* W, const float* G, float* M, const SgdCfg& cfg,
+                            const uint32_t* R);
+void launch_sgd_f32_frag_live(hipStream_t st, StepRec* steps, int64_t n_steps, float* W, const float* G, float* M, const SgdCfg& cfg, const uint32_t* R, float* a_frag,
+                              float* A_out, const uint32_t* words);
+void launch_sgd_h16_live(bool bf16, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, float* W, const float* G, float* M, const SgdCfg& cfg,
+                         const uint32_t* R, uint16_t* dst, const uint32_t* words);
+void launch_adam_blocks_live(hipStream_t st, const PruneBlock* blocks, int64_t n_blocks, const uint8_t* keep, const AdamArgs& a);
+void launch_adam_f32_frag_live(hipStream_t st, StepRec* steps, int64_t n_steps, const AdamArgs& a, float* a_frag, float* A_out, const uint32_t* words);
+void launch_adam_h16_live(bool bf16, int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, const AdamArgs& a, uint16_t* dst, const uint32_t* words);
 // k_spmm_t.hip: grid = n_items x slabs of kSpmmTSlab columns; dtype = SPARTA_F32 / F16 / BF16
 void launch_spmm_t(int dtype, unsigned n_items, hipStream_t st, const SpmmTParams& p);
 // k_colres.hip
@@ -609,6 +629,8 @@ void launch_live_sddmm(hipStream_t st, const BlockRowDesc* brows, int64_t n_brow
                        int32_t* groups, int32_t* count);
 void launch_live_spmm_t(hipStream_t st, const SpmmTItem* items, const SpmmTBlock* blocks, const int32_t* tmap, int64_t block_cols, int panels, const uint8_t* keep,
                         SpmmTItem* live_items, SpmmTBlock* live_blocks, int32_t* live_ids, int32_t* live_count);
+// ... and the live words of the steps' image kernels: words[i] = all ones if block wmap[i] is live in the snapshot, else 0 (wmap[i] < 0: 0)
+void launch_live_step_words(hipStream_t st, const int32_t* wmap, int64_t n_words, const uint8_t* snap, uint32_t* words);
 
 // vbs_plan.cpp
 struct StreamPlanIn {
@@ -699,6 +721,11 @@ struct LiveMapsHost {
 };
 int build_live_maps(int64_t cols, int64_t w, int64_t br0, int64_t br1, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, int64_t jab_lo, LiveMapsHost& M);
 void live_lists_host(const LiveMapsHost& M, const uint8_t* keep, int32_t* sd_groups, int32_t* sd_count, int32_t* t_blocks, int32_t* t_count, int64_t* info);
+// the pattern-only map of the live words of the steps' image kernels: word i covers the `span` stored columns (leading dimension ld[i]) that start at element
+// first[i] of the range's mab (first[i] < 0: a slice half that is not there, wmap[i] = -1); wmap[i] = the number of the block they lie in, by the block table's
+// offsets (block_off[n_blocks], ascending, mab order).  SPARTA_ERR_INVALID if a word's first and last column lie in different blocks: the image kernels test one
+// bit per lane, which is right only where a step / slice half never leaves its block (block widths that are multiples of 32: every plan with an image kernel)
+int build_live_word_map(const int64_t* block_off, int64_t n_blocks, int64_t nztot, const int64_t* first, const int32_t* ld, int64_t n_words, int64_t span, int32_t* wmap);
 // one block of the 16-bit image from its column-major h x w source
 void pack_spmm_t_block(const float* blk, int64_t h, int64_t w, bool bf16, uint16_t* dst);
 uint16_t to_h16(float v, bool bf16);   // fp32 -> fp16 / bf16 bits, round to nearest even (what the device conversion kernel does too)

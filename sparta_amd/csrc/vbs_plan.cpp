@@ -1192,6 +1192,21 @@ int build_live_maps(int64_t cols, int64_t w, int64_t br0, int64_t br1, const int
     return SPARTA_OK;
 }
 
+// The block of an element: the last block of the table that starts at or before it (blocks without elements share their successor's offset and are passed over).
+int build_live_word_map(const int64_t* block_off, int64_t n_blocks, int64_t nztot, const int64_t* first, const int32_t* ld, int64_t n_words, int64_t span, int32_t* wmap) {
+    using sparta::fail;
+    auto block_of = [&](int64_t e) { return (int64_t)(std::upper_bound(block_off, block_off + n_blocks, e) - block_off) - 1; };
+    for (int64_t i = 0; i < n_words; i++) {
+        if (first[i] < 0) { wmap[i] = -1; continue; }
+        const int64_t last = first[i] + (span - 1) * (int64_t)ld[i];
+        if (last >= nztot) return fail(SPARTA_ERR_INVALID, "live steps: a step of the plan reaches past the stored elements");
+        const int64_t b = block_of(first[i]);
+        if (b < 0 || b != block_of(last)) return fail(SPARTA_ERR_INVALID, "live steps: a step of the plan spans more than one block");
+        wmap[i] = (int32_t)b;
+    }
+    return SPARTA_OK;
+}
+
 // Group g of a block-row (stored columns 32 g .. 32 g + 31 of its nb * w) is live iff one of the blocks it overlaps is; the live group numbers go to the front
 // of the block-row's slice in ascending order, -1 behind them.  A block column's live block numbers go to the front of its slice in list order, -1 behind them.
 void live_lists_host(const LiveMapsHost& M, const uint8_t* keep, int32_t* sd_groups, int32_t* sd_count, int32_t* t_blocks, int32_t* t_count, int64_t* info) {

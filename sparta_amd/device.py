@@ -23,6 +23,24 @@ def device_count():
     return int(lib.sparta_device_count())
 
 
+class _Info(dict):
+    """An info dict that grew: the words an entry point reported from the start are its items -- equality, iteration and len() see those alone, as code that
+    compares whole dicts expects -- and the words added later answer to subscript and get()."""
+
+    def __init__(self, items, later):
+        super().__init__(items)
+        self.later = dict(later)
+
+    def __missing__(self, key):
+        return self.later[key]
+
+    def get(self, key, default=None):
+        return self[key] if key in self or key in self.later else default
+
+    def __repr__(self):
+        return "%s + %r" % (dict.__repr__(self), self.later)
+
+
 class ValuesRecord:
     """vbs_linear's record, kept on a handle, of which tensor (at which version) the handle's values were last taken from (autograd.py).  Whatever
     gives the handle other values, or none, calls _values_replaced(); a handle class of its own that vbs_linear is to drive derives from this."""
@@ -403,10 +421,11 @@ class DeviceVBS(ValuesRecord):
 
     def step_info(self):
         """sparta_vbs_step_info: {"fused": 1 the last sgd_step / adam_step did its arithmetic inside an image kernel / 0 it ran the elementwise kernel and then
-        the set_values launches / -1 no step yet, "launches": kernel launches of that step (an Adam step counts its tick)}"""
+        the set_values launches / -1 no step yet, "launches": kernel launches of that step (an Adam step counts its tick)}; ["live"]: 1 if that step
+        skipped dead blocks (set_live_steps), else 0 -- a later word, see _Info"""
         out = (C.c_int64 * 4)()
         check(lib.sparta_vbs_step_info(self.h, out))
-        return {"fused": int(out[0]), "launches": int(out[1])}
+        return _Info({"fused": int(out[0]), "launches": int(out[1])}, {"live": int(out[2])})
 
     @property
     def n_blocks(self):
@@ -493,16 +512,28 @@ class DeviceVBS(ValuesRecord):
             return
         check(lib.sparta_vbs_set_live_blocks(self.h, C.cast(C.c_void_p(keep.data_ptr()), C.POINTER(C.c_uint8)), C.c_void_p(st)))
 
+    def set_live_steps(self, on, stream=None):
+        """sparta_vbs_set_live_steps: with on=True and a live set installed (set_live_blocks) sgd_step / adam_step, plain and under a GradCtl, skip the dead
+        blocks: their G, M, V are neither read nor written, W is not written (it must hold +0.0 there, as mask_blocks leaves it) and the images get +0.0.
+        Live blocks get the bits of the plain step.  Off by default; without a live set the switch does nothing.  The first enabling call builds helper
+        arrays and cannot be captured; later calls, and set_live_blocks with the switch on, are launches only (torch's current stream).  Nothing to gain
+        on an unpruned set.  step_info()["live"] says what the last step did."""
+        if not on:
+            check(lib.sparta_vbs_set_live_steps(self.h, 0, None))
+            return
+        check(lib.sparta_vbs_set_live_steps(self.h, 1, self._live_stream(stream)))
+
     def _live_stream(self, stream):
         import torch
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream)
 
     def live_info(self, stream=None):
-        """sparta_vbs_live_info (synchronises): {"installed", "n_blocks", "live_blocks", "sd_groups", "live_sd_groups", "t_entries", "live_t_entries"}"""
+        """sparta_vbs_live_info (synchronises): {"installed", "n_blocks", "live_blocks", "sd_groups", "live_sd_groups", "t_entries", "live_t_entries"};
+        ["live_steps"]: the switch of set_live_steps -- a later word, see _Info"""
         a = np.zeros(8, np.int64)
         check(lib.sparta_vbs_live_info(self.h, a.ctypes.data_as(_i64p), self._live_stream(stream)))
         keys = ["installed", "n_blocks", "live_blocks", "sd_groups", "live_sd_groups", "t_entries", "live_t_entries"]
-        return {k: int(a[i]) for i, k in enumerate(keys)}
+        return _Info({k: int(a[i]) for i, k in enumerate(keys)}, {"live_steps": int(a[7])})
 
     def live_lists(self, stream=None):
         """sparta_vbs_live_lists_get (synchronises; for tests): the compacted lists the kernels walk, as VBR.live_lists returns them for the same keep --

@@ -56,15 +56,21 @@ class BlockPruner:
     skip_pruned=True: prune and load_state_dict also hand every handle its mask (DeviceVBS.set_live_blocks), so that the backward products skip the pruned
     blocks instead of computing them: sddmm stores +0.0 for them and spmm_t leaves them out (their values are zero: the same sum).  A gradient that comes from
     vbs_linear alone is then already +0 in the pruned blocks and mask_grads() can be dropped from the loop; it is still needed where anything else adds to
-    values.grad (a regulariser, a second use of the values outside vbs_linear)."""
+    values.grad (a regulariser, a second use of the values outside vbs_linear).
 
-    def __init__(self, optimizer_or_pairs, scope="global", normalize=True, skip_pruned=False):
+    live_steps=True (needs skip_pruned=True): the handles are also switched to live steps (DeviceVBS.set_live_steps) once they have their mask, so that the
+    optimizer's step skips the pruned blocks too -- it reads and writes the weights, the gradient and the state of the live blocks only, with the bits of the
+    plain step.  The pruned blocks of values must stay +0.0, which prune guarantees; their gradient and state are not looked at any more."""
+
+    def __init__(self, optimizer_or_pairs, scope="global", normalize=True, skip_pruned=False, live_steps=False):
         import torch
         if scope not in ("global", "layer"):
             raise ValueError("scope must be 'global' or 'layer'")
+        if live_steps and not skip_pruned:
+            raise ValueError("live_steps=True needs skip_pruned=True (the steps skip the blocks of the live set the handles are given)")
         self.optimizer = optimizer_or_pairs if hasattr(optimizer_or_pairs, "pairs") else None
         self.pairs = [(h, v) for h, v in (self.optimizer.pairs if self.optimizer is not None else optimizer_or_pairs)]
-        self.scope, self.normalize, self.skip_pruned = scope, bool(normalize), bool(skip_pruned)
+        self.scope, self.normalize, self.skip_pruned, self.live_steps = scope, bool(normalize), bool(skip_pruned), bool(live_steps)
         self._keep, self._n_in = [], []
         for handle, values in self.pairs:
             self._keep.append(torch.ones(handle.n_blocks, dtype=torch.uint8, device=values.device))
@@ -97,6 +103,8 @@ class BlockPruner:
         handle.set_values(values.detach())
         if self.skip_pruned:
             handle.set_live_blocks(self._keep[i])
+            if self.live_steps:
+                handle.set_live_steps(True)
 
     def prune(self, sparsity):
         """select() on scores(), then per pair the pruned blocks zeroed in values, values.grad (if present) and the optimizer's state (where allocated), and
