@@ -569,6 +569,54 @@ int sparta_vbs_sgd_step_ctl(sparta_vbs_t* A, float* W, const float* G, float* M,
 int sparta_vbs_adam_step_ctl(sparta_vbs_t* A, float* W, const float* G, float* M, float* V, void* S,
                              const sparta_adam_cfg* cfg, const void* R, void* stream, float* dt_ms);
 
+/* The epilogue of a block-sparse linear layer: bias, activation and the output type in ONE pass behind the forward product (sparta_epilogue_fwd), and in ONE
+ * pass in front of the two backward products (sparta_epilogue_bwd), which writes their operand dZ in the handle's type and the bias gradient.  Handle-free,
+ * as sparta_grad_stats: device pointers only, on the current device.  Every operand is a column-major rows x n_cols matrix with a leading dimension
+ * (element (i, j) at j * ld + i) -- the layout of C of sparta_vbs_spmm and of X of sparta_vbs_spmm_t / sparta_vbs_sddmm; Z is fp32, y_dtype / dy_dtype /
+ * dz_dtype are SPARTA_F32, SPARTA_F16 or SPARTA_BF16; bias (rows floats, may be NULL) is indexed by the row.  Bases and leading dimensions are arbitrary
+ * (aligned to the element size, ld >= rows); offsets are 64-bit.  Where every operand is 16-byte aligned at the same row of every column (the bases agree
+ * modulo four elements and every ld is a multiple of 4) a lane takes four consecutive rows per access, the rows in front and behind one by one; otherwise all
+ * rows go one by one.  The results do not depend on which.
+ *
+ * THE ARITHMETIC, per element, every fp32 operation rounded once in the order written, nothing contracted into an FMA; 16-bit inputs are widened exactly and
+ * 16-bit outputs rounded to nearest even (a bf16 NaN keeps its sign and gets the quiet bit):
+ *     u = Z[i,j] + bias[i]                      (u = Z[i,j] when bias == NULL: no addition)
+ *     SPARTA_ACT_NONE   y = u                                            dz = dy
+ *     SPARTA_ACT_RELU   y = (u <= 0) ? +0.0f : u   (a NaN passes)        dz = (u <= 0) ? +0.0f : dy     (a select: a NaN in dy under a masked position is dropped)
+ *     SPARTA_ACT_GELU   e = erff(u * 0.70710678f)                        (the erf form, torch's default)
+ *                       y = (0.5f * u) * (1.0f + e)
+ *                       dz = dy * (0.5f * (1.0f + e) + (u * expf((-0.5f * u) * u)) * 0.39894228f)
+ * erff and expf are the device library's; everything else can be restated in numpy float32 bit for bit (tests/_epilogue.py).
+ * THE BIAS GRADIENT: dbias[i] = the sum over j of the fp32 dz[i,j] BEFORE its rounding to dz_dtype, each widened to fp64.  The order is fixed: the columns go
+ * in consecutive runs of SPARTA_EPILOGUE_RUN; inside a run the sum is sequential in fp64, j ascending, starting from 0.0; the run sums are added
+ * sequentially in ascending run order; the result is rounded once to fp32.  No floating-point atomic, no shuffle tree: dbias is a function of (rows, n_cols,
+ * data) alone -- not of the grid, the device, the alignment of the operands, eager or replayed.  With more than one run the run sums pass through `scratch`
+ * (sparta_epilogue_scratch_bytes(rows, n_cols) bytes of caller-owned device memory on an 8-byte boundary, content unspecified before and after; 0 bytes when
+ * one run covers n_cols) and a second, fixed-order launch adds them.  dbias == NULL skips the sums, and scratch is then unused.
+ *
+ * WHAT AN OUTPUT ELEMENT DEPENDS ON (Inf and NaN are ordinary data):
+ *   Y[i,j] depends on Z[i,j] and bias[i] only.
+ *   dZ[i,j] depends on dY[i,j], Z[i,j] and bias[i] only (with SPARTA_ACT_NONE on dY[i,j] only: Z may be NULL then, and neither Z nor bias is read).
+ *   dbias[i] depends on row i of dY, Z and on bias[i] only; nothing accumulates into the previous content of dbias or scratch.
+ *   The elements [rows, ld) of a column of any operand are neither read into a result nor written.
+ * IN PLACE: Y == Z is allowed with y_dtype == SPARTA_F32 and ldy == ldz; dZ == dY with dz_dtype == dy_dtype and lddz == lddy.  Any other overlap of an
+ * output with an operand is undefined.
+ * The entries launch kernels only -- no allocation, no synchronisation -- and can be captured into a hipGraph from the first call.  *dt_ms (may be NULL)
+ * covers the kernels and synchronises (SPARTA_ERR_UNSUPPORTED while the stream is being captured).  rows == 0 or n_cols == 0 returns SPARTA_OK; with
+ * n_cols == 0 and dbias != NULL, dbias gets rows times +0.0f.  SPARTA_ERR_INVALID, with nothing launched and a message that names the entry, for a negative
+ * size, an unknown act or dtype, ld < rows, a NULL Z (unless SPARTA_ACT_NONE in backward), Y, dY or dZ with rows and n_cols > 0, a pointer not aligned to
+ * its element size, a NULL (or not 8-byte aligned) scratch when sparta_epilogue_scratch_bytes > 0 and dbias != NULL. */
+#define SPARTA_ACT_NONE 0
+#define SPARTA_ACT_RELU 1
+#define SPARTA_ACT_GELU 2
+#define SPARTA_EPILOGUE_RUN 32
+int sparta_epilogue_fwd(const float* Z, int64_t ldz, const float* bias, int32_t act,
+                        void* Y, int64_t ldy, int32_t y_dtype, int64_t rows, int64_t n_cols, void* stream, float* dt_ms);
+int sparta_epilogue_scratch_bytes(int64_t rows, int64_t n_cols, int64_t* bytes_out);   /* may be 0 */
+int sparta_epilogue_bwd(const void* dY, int64_t lddy, int32_t dy_dtype, const float* Z, int64_t ldz, const float* bias, int32_t act,
+                        void* dZ, int64_t lddz, int32_t dz_dtype, float* dbias, void* scratch,
+                        int64_t rows, int64_t n_cols, void* stream, float* dt_ms);
+
 /* Block pruning: a score per stored block, and chosen blocks made zero -- and kept zero -- in the weights, the optimizer state and the gradient.
  * The stored blocks of the block-rows [block_row_begin, block_row_end) are numbered in mab order: block-row by block-row, inside a block-row in jab order.
  * sparta_vbs_block_table_host (pure host code, no GPU) writes four words per block:

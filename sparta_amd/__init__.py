@@ -20,10 +20,11 @@ from .host import (CSR, BlockingEngine, VBR, get_permutation, get_partition, get
                    row_distance, merge_rows, BLOCKING_ALGOS, save_grouping, read_grouping_file, blocking_csv_row,
                    save_blocking_data, CSV_COLUMNS)
 from .device import DeviceVBS, vbs_multiply, device_count  # noqa: F401
-from . import gen, dist, autograd, optim, gradctl, prune  # noqa: F401
+from . import gen, dist, autograd, optim, gradctl, prune, epilogue  # noqa: F401
 from .optim import VbsSGD, VbsAdamW  # noqa: F401
 from .gradctl import GradCtl  # noqa: F401
 from .prune import BlockPruner  # noqa: F401
+from .epilogue import epilogue_fwd, epilogue_bwd  # noqa: F401
 
 # revision tag of the device kernels: PMC-derived numbers kept under profiles/ (HBM traffic per launch) carry it, and bench.py
 # only quotes them for the revision they were measured on

@@ -28,6 +28,9 @@ CREATE_TRANSPOSE = 2
 # the control record of sparta_grad_stats / sparta_grad_ctl_finish: its size in bytes, and the launch rule of the reduction (one workgroup per
 # GRAD_STATS_CHUNK elements, at most GRAD_STATS_MAX_GRID)
 GRAD_CTL_BYTES, GRAD_STATS_CHUNK, GRAD_STATS_MAX_GRID = 16448, 4096, 1024
+# sparta_epilogue_fwd / sparta_epilogue_bwd: the activations, and the run of columns of the bias gradient's fixed order
+ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
+EPILOGUE_RUN = 32
 FMT_EL, FMT_MTX = 0, 1
 IO_COMPAT, IO_STRICT = 0, 1
 
@@ -51,6 +54,7 @@ SYMBOLS = [
     "sparta_f32_pack_blocks", "sparta_vbs_packed_info",
     "sparta_vbs_block_table_host", "sparta_vbs_block_count", "sparta_vbs_block_ssq", "sparta_vbs_mask_blocks",
     "sparta_vbs_set_live_blocks", "sparta_vbs_live_info", "sparta_vbs_live_lists_get", "sparta_vbs_live_lists_host", "sparta_vbs_set_live_steps",
+    "sparta_epilogue_fwd", "sparta_epilogue_scratch_bytes", "sparta_epilogue_bwd",
 ]
 
 
@@ -152,6 +156,9 @@ def _load():
     L.sparta_vbs_step_info.argtypes = [vp, i64p]
     L.sparta_grad_stats.argtypes = [f32p, C.c_int64, vp, C.c_int32, vp, f32p]
     L.sparta_grad_ctl_finish.argtypes = [vp, C.POINTER(GradCtlCfg), vp]
+    L.sparta_epilogue_fwd.argtypes = [f32p, C.c_int64, f32p, C.c_int32, vp, C.c_int64, C.c_int32, C.c_int64, C.c_int64, vp, f32p]
+    L.sparta_epilogue_scratch_bytes.argtypes = [C.c_int64, C.c_int64, i64p]
+    L.sparta_epilogue_bwd.argtypes = [vp, C.c_int64, C.c_int32, f32p, C.c_int64, f32p, C.c_int32, vp, C.c_int64, C.c_int32, f32p, vp, C.c_int64, C.c_int64, vp, f32p]
     L.sparta_vbs_sgd_step_ctl.argtypes = [vp, f32p, f32p, f32p, C.POINTER(SgdCfg), vp, vp, f32p]
     L.sparta_vbs_adam_step_ctl.argtypes = [vp, f32p, f32p, f32p, f32p, vp, C.POINTER(AdamCfg), vp, vp, f32p]
     L.sparta_vbs_flags.argtypes = [vp, i32p]

@@ -249,19 +249,7 @@ __global__ __launch_bounds__(kThreads) void vbs_update_copy_kernel(const float* 
     for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) A[i] = mab[i];
 }
 
-// fp32 -> fp16 / bf16 bits exactly as to_h16 (vbs_plan.cpp) rounds at creation: round to nearest even; bf16 keeps a NaN a NaN (quiet bit set), Inf stays Inf
-template <bool BF16>
-__device__ __forceinline__ uint32_t upd_h16(float v) {
-    if constexpr (BF16) {
-        const uint32_t u = __float_as_uint(v);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return ((u >> 16) | 0x40u) & 0xffffu;
-        return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-    } else {
-        const _Float16 hh = (_Float16)v;
-        return (uint32_t)__builtin_bit_cast(uint16_t, hh);
-    }
-}
-
+// (upd_h16, the fp32 -> fp16 / bf16 rounding of every image, lives in vbs_kernel_common.hpp: k_epilogue.hip rounds with it too)
 // the fragment kernel and the slice kernel, once per value source
 #define UPD_SOURCE 0
 #include "k_update_image.inc"

@@ -8,6 +8,7 @@
 //   k_spmm_t.hip      the transposed product on a handle's own stored blocks (sparta_vbs_spmm_t)
 //   k_update.hip      new values for the images of an updatable handle (sparta_vbs_set_values)
 //   k_prune.hip       block pruning: per-block sums of squares, zero fill of chosen blocks (sparta_vbs_block_ssq, sparta_vbs_mask_blocks)
+//   k_epilogue.hip    the epilogue of a linear layer: bias, activation, output type, bias gradient (sparta_epilogue_fwd, sparta_epilogue_bwd)
 //   k_live.hip        the live-block set of a handle: stable compaction of the lists sddmm and spmm_t walk (sparta_vbs_set_live_blocks)
 //   vbs_plan.cpp      host: stream plans (step lists, worker ranges, split tiles)
 //   vbs_capi.cpp      host: device image (sparta_vbs), sparta_vbs_create* / sparta_vbs_spmm* (include/sparta_amd.h)
@@ -324,6 +325,22 @@ struct PruneBlock { int64_t off; int32_t n_in, n_all; };
 static_assert(sizeof(PruneBlock) == 16, "PruneBlock must stay 16 bytes");
 constexpr int kPruneWaves = kThreads / 64;    // blocks per workgroup: one wave each
 
+// the epilogue of a linear layer (k_epilogue.hip): column-major rows x n_cols operands.  A work item = a tile of kThreads rows x a run of kEpRun columns.
+// Rows [head, head + 4 n4) are the body (vec_tiles tiles, a lane owns four rows: every operand is aligned there in every column), the others the edge
+// (edge_tiles tiles, one element per access); ep_plan (vbs_capi.cpp) fills the four.  dY / Out: the types are the kernels' template arguments.
+constexpr int kEpRun = 32, kEpNone = 0, kEpRelu = 1, kEpGelu = 2;
+struct EpilogueParams {
+    const void* dY;                 // backward only
+    const float* Z;                 // forward: the input; backward: NULL allowed when act == kEpNone
+    const float* bias;              // or nullptr
+    void* Out;                      // Y / dZ
+    float* dbias;                   // backward: nullptr = no sums
+    double* part;                   // backward, n_runs > 1: n_runs x rows partial sums (the caller's scratch)
+    int64_t lddy, ldz, ldo, rows, n_cols, n_runs;
+    int64_t head, n4, vec_tiles, edge_tiles;
+    int32_t act, pad;
+};
+
 #define HIP_TRY(expr)                                                                                   \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \
@@ -624,6 +641,9 @@ void launch_grad_ctl_finish(hipStream_t st, void* R, float max_norm, float growt
 // keep[b] == 0 stored as +0.0f (all n_all elements) in each non-NULL T[0..3]
 void launch_block_ssq(hipStream_t st, const PruneBlock* blocks, int64_t n_blocks, const float* W, double* ssq);
 void launch_mask_blocks(hipStream_t st, const PruneBlock* blocks, int64_t n_blocks, const uint8_t* keep, float* T0, float* T1, float* T2, float* T3);
+// k_epilogue.hip: Y = act(Z + bias); dZ = dY * act'(Z + bias), and with p.dbias the fixed-order fp64 row sums (a second launch folds the runs when n_runs != 1)
+void launch_epilogue_fwd(hipStream_t st, int y_dtype, const EpilogueParams& p);
+void launch_epilogue_bwd(hipStream_t st, int dy_dtype, int dz_dtype, const EpilogueParams& p);
 // k_live.hip: the snapshot of keep and the compacted lists, one wave per block-row / per block column, stable, no atomics, no LDS
 void launch_live_sddmm(hipStream_t st, const BlockRowDesc* brows, int64_t n_brows, int w, const uint8_t* keep, int64_t n_blocks, uint8_t* snap, const int32_t* goff,
                        int32_t* groups, int32_t* count);

@@ -92,6 +92,20 @@ __device__ __forceinline__ void clock_probe(long long* clk, int slot) {
     }
 }
 
+// fp32 -> fp16 / bf16 bits exactly as to_h16 (vbs_plan.cpp) rounds at creation: round to nearest even; bf16 keeps a NaN a NaN (quiet bit set), Inf stays Inf
+// (k_update.hip: the 16-bit images; k_epilogue.hip: 16-bit outputs)
+template <bool BF16>
+__device__ __forceinline__ uint32_t upd_h16(float v) {
+    if constexpr (BF16) {
+        const uint32_t u = __float_as_uint(v);
+        if ((u & 0x7fffffffu) > 0x7f800000u) return ((u >> 16) | 0x40u) & 0xffffu;
+        return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    } else {
+        const _Float16 hh = (_Float16)v;
+        return (uint32_t)__builtin_bit_cast(uint16_t, hh);
+    }
+}
+
 template <int MF>
 struct Acc;
 template <>
