@@ -10,6 +10,7 @@ from ._lib import lib, check
 _f32p = C.POINTER(C.c_float)
 ACTIVATIONS = {"none": _lib.ACT_NONE, "relu": _lib.ACT_RELU, "gelu": _lib.ACT_GELU}
 _SCRATCH = {}          # device index -> the float64 tensor the run sums of the bias gradient pass through (grown on demand, never under capture)
+_RETIRED = []          # every scratch tensor a larger one replaced: a graph captured earlier has its address in an epilogue_bwd node, so it is never freed
 _SCRATCH_BYTES = {}    # (rows, n_cols) -> sparta_epilogue_scratch_bytes: a function of the shape alone, asked once per shape
 _DTYPES = {}           # torch dtype -> SPARTA_* code, filled at the first call
 
@@ -97,6 +98,8 @@ def _scratch(device, nbytes):
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("epilogue_bwd: the scratch of the bias gradient would have to grow while the stream is being captured -- run the call once "
                                "outside the capture first")
+        if t is not None:
+            _RETIRED.append(t)                                  # (a few KB to MB each, and each larger than the one before)
         t = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
         _SCRATCH[device.index] = t
     return t

@@ -362,3 +362,42 @@ def test_torch_functions_match_the_entries():
         sa.epilogue_fwd(zt, bt[:-1], "relu")
     with pytest.raises(ValueError):
         sa.epilogue_bwd(zt, None, None, "relu", torch.float32, False)
+
+
+# ---- 9. the cached scratch of the bias gradient outlives the graph that captured it ------------------------------------------------------------------------
+def test_scratch_outlives_the_capture_that_took_its_address(monkeypatch):
+    """a graph that captured epilogue_bwd at (90, 33) has the scratch tensor's address in its node; an eager call at (200, 65) then needs a larger scratch.
+    The first tensor must stay alive: freed, its block goes back to torch's allocator and a replay writes fp64 partials into whatever lives there next.
+    The host-side assertion (a weakref taken before the growth) stands in front of the replay, so code that frees the tensor fails here without a write to
+    freed memory; then a sentinel of the old scratch's size is allocated and filled, and the replay gives the bits of dbias_of and leaves the sentinel alone."""
+    import weakref
+    monkeypatch.setattr(sa.epilogue, "_SCRATCH", {})                      # a cache of this test's own: what earlier tests grew it to does not matter
+    rows, n = 90, 33
+    sets = []
+    for seed in (31, 32):
+        Z, dY32, b = operands(rows, n, seed)
+        sets.append((np.nan_to_num(Z, nan=0.25, posinf=2.0, neginf=-2.0), np.clip(np.nan_to_num(dY32, nan=0.25, posinf=2.0, neginf=-2.0), -1000, 1000), b))
+    z, gy, bt = vec(sets[0][0].T), vec(sets[0][1].T), vec(sets[0][2])
+    big = torch.zeros((65, 200), device="cuda")
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        sa.epilogue_bwd(gy, z, bt, "relu", torch.float32, True)           # eager: the scratch is made here (a capture refuses to)
+        first = sa.epilogue._SCRATCH[gy.device.index]
+        nbytes = first.numel() * 8
+        assert nbytes == sa.epilogue.scratch_bytes(rows, n) > 0
+        alive = weakref.ref(first)
+        del first
+        gph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gph, stream=s):
+            dz, db = sa.epilogue_bwd(gy, z, bt, "relu", torch.float32, True)
+        sa.epilogue_bwd(big, big, None, "relu", torch.float32, True)      # eager, larger: the cache takes a new tensor
+        assert sa.epilogue._SCRATCH[gy.device.index].numel() * 8 >= sa.epilogue.scratch_bytes(200, 65) > nbytes
+        assert alive() is not None, "the scratch a captured epilogue_bwd writes to was freed when the cache grew"
+        sentinel = torch.full((nbytes // 8,), 7.25, dtype=torch.float64, device="cuda")
+        z.copy_(vec(sets[1][0].T)); gy.copy_(vec(sets[1][1].T)); bt.copy_(vec(sets[1][2]))
+        gph.replay()
+        torch.cuda.synchronize()
+    dz_ref, db_ref = E.bwd_ref(sets[1][1], sets[1][0], sets[1][2], RELU)
+    assert same(dz.cpu().numpy().T, dz_ref) and same(db.cpu().numpy(), db_ref)
+    assert bool((sentinel == 7.25).all())
