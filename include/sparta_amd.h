@@ -346,7 +346,7 @@ int sparta_vbs_plan_stats(int64_t rows, int64_t cols, const int64_t* rowptr, con
  *   accumulate = 0 still writes all cols x n_cols elements, zeros where no live block covers a column.  Rows of X that reach a block column only through
  *   dead blocks are not read for it.  Dropping a block removes whole MFMA passes (a pass covers rows of one block only): with finite X the result equals,
  *   up to the sign of a zero, the product without a live set on values whose dead blocks are zero.
- *   Everything else ignores the live set: the forward products, sparta_vbs_set_values, the steps (unless live steps are on, below), sparta_vbs_block_ssq,
+ *   Everything else ignores the live set: the forward products (unless live forward is on, below), sparta_vbs_set_values, the steps (unless live steps are on, below), sparta_vbs_block_ssq,
  *   sparta_vbs_mask_blocks.  Keeping the VALUES of dead blocks at zero stays the caller's job.
  *   WITH A LIVE-BLOCK SET INSTALLED AND LIVE STEPS ON (sparta_vbs_set_live_steps), for sparta_vbs_sgd_step, sparta_vbs_adam_step and both _ctl forms, in the
  *   fused and in the two-pass form:
@@ -358,7 +358,16 @@ int sparta_vbs_plan_stats(int64_t rows, int64_t cols, const int64_t* rowptr, con
  *   The Adam step state: the tick and S are unchanged; a skipped step (R[skip]) behaves as without live steps (W, M, V, S keep their bits; the fused kernel
  *   still writes +0.0 for dead blocks into its image).
  *   Equivalence: on tensors whose dead blocks are +0 in W, M, V and G a live step leaves W, M, V, S and every product of the handle bit-identical to the
- *   plain step (which computes +0 for them: "A zero block stays zero", below). */
+ *   plain step (which computes +0 for them: "A zero block stays zero", below).
+ *   WITH A LIVE-BLOCK SET INSTALLED AND LIVE FORWARD ON (sparta_vbs_set_live_forward), for sparta_vbs_spmm on a 16-bit handle that takes the live form
+ *   (sparta_vbs_live_forward_info word 1; every other handle and launch keeps the text above):
+ *   A dead block contributes nothing to C, whatever the image holds for it, NaN included.  Neither its slice of A nor, on its behalf, the rows of B is read:
+ *   its steps are not in a worker's live range, and what is kept of them (the dead half of a pair-tile step whose other half is live, the one step that
+ *   carries the epilogue of a tile piece without a live block) loads through descriptors of zero records and meets B fragments ANDed with 0.  (The load
+ *   pipeline still runs three records past the end of a live range, as it runs past the end of a plain one: those loads are issued and never used.)
+ *   Rows of C reached only through dead blocks are +0.0, or unchanged under accumulate = 1.
+ *   Equivalence: on values whose dead blocks are zero, C equals the plain product element for element, the sign of a zero aside -- whole steps of exact zero
+ *   products are dropped and the order of the rest is kept. */
 int sparta_vbs_spmm(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int32_t n_cols,
                     void* C, int64_t ldc, int32_t c_layout, int32_t accumulate,
                     int32_t ptr_space, void* stream, int32_t algo, float* dt_ms);
@@ -695,6 +704,41 @@ int sparta_vbs_set_live_blocks(sparta_vbs_t* A, const uint8_t* keep, void* strea
  * itself).  No allocation, no synchronisation, capturable after the first call; a replay of set_live_blocks re-reads keep.  enable == 0: host state only.
  * SPARTA_ERR_UNSUPPORTED on a handle made without SPARTA_CREATE_UPDATABLE and on every handle sparta_vbs_set_live_blocks refuses; SPARTA_ERR_INVALID on NULL. */
 int sparta_vbs_set_live_steps(sparta_vbs_t* A, int32_t enable, void* stream);
+/* Live forward: with enable != 0 and a live set installed, the 16-bit forward product walks only the steps of live blocks (the contract: "WITH A LIVE-BLOCK
+ * SET INSTALLED AND LIVE FORWARD ON" above).  Opt-in, off at creation; the plain kernels and the plain records are untouched.  The switch is host state, read
+ * when sparta_vbs_spmm is called (or captured), and acts only while a live set is installed.  Needs SPARTA_CREATE_UPDATABLE (the map from steps to blocks is
+ * the one of the live steps): SPARTA_ERR_UNSUPPORTED otherwise, and on every handle sparta_vbs_set_live_blocks refuses.
+ * Which handles take the live form: 16-bit handles with ONE stream image and no hub plan whose block width is a multiple of 32 (the handles with a fused step
+ * image).  fp32 handles (their forward product follows sparta_vbs_set_values by itself), handles with a hub plan or two stream images and other block widths
+ * accept the switch and keep the plain kernels; so do, on a handle that qualifies, a gathered B, SPARTA_H16_AHEAD=7 and SPARTA_H16_PATH=lds.  Word 1 and
+ * words 2, 3 of sparta_vbs_live_forward_info say so.
+ * The FIRST enabling call builds and uploads pattern-only helper arrays (those of the live set and the word map if they do not exist yet; a second copy of
+ * the stream image's step records, 32 bytes per step, a second range array and 4 bytes per step that say where its tile piece ends) and returns
+ * SPARTA_ERR_UNSUPPORTED while the stream is being captured.  If a set is installed the call launches, on `stream`, the word kernel and the compaction kernel;
+ * from then on every sparta_vbs_set_live_blocks adds those launches.  No allocation, no synchronisation, capturable after the first call.
+ * The rule (one wave per worker range, ballot and prefix count, no atomics: a function of the snapshot alone; sparta_live_forward_compact is the same rule
+ * as host code on arrays): a SEGMENT is the run of records of a range up to and including the next STEP_LAST record -- what one worker owns of a tile.  A
+ * step is live iff a present half of it (rows 0..31 / 32..63 of its slice) lies in a live block.  Per range, over the same positions: the kept steps first,
+ * in order -- every live step, and the first step of a segment without one -- then the dropped steps, unchanged and in order; the live range is (begin,
+ * begin + kept).  A kept record keeps its slice offset, its rows of B and its tail flag; the first kept step of a segment carries STEP_FIRST, the last one
+ * STEP_LAST and the segment's epilogue fields (split flag, slot, first row of C, tile rows); a dead half gets its absent flag, the kept step of a segment
+ * without a live step is marked dead as a whole (one-tile records: the lower absent flag, pair tiles: both) -- its epilogue still runs and writes zeros.
+ * Ranges stay as creation balanced them: the worker with the most kept steps bounds the kernel.
+ * sparta_vbs_live_forward_info: info_out[8] = {the switch, which stream image has the live form (0: none, 1: the <= 32-row tiles, 2: the 64-row / pair tiles), the form the last 16-bit product ran on the
+ * image of <= 32-row tiles and on the image of 64-row / pair tiles (0: none yet, 1: plain, 2: live), steps of the image with the live form, kept steps (read
+ * back; 0 without a live set or before the first enabling call), split tiles, ranges}.
+ * sparta_vbs_live_forward_lists_get: host pointers, any may be NULL -- the plain records [steps][32 bytes] and ranges [ranges][2], the two live bits of every
+ * step [steps][2], the compacted records and the live ranges.  SPARTA_ERR_INVALID without a live set, SPARTA_ERR_UNSUPPORTED on a handle without the lists.
+ * Both synchronise the stream and are refused under capture; they are for tests and records.
+ * sparta_live_forward_compact: `steps` = n_steps records of 32 bytes {int64 a_off; int32 b_row, h, c_row, mt_flags, slot, pad}, ranges = n_ranges disjoint
+ * (begin, end) pairs, pair_image != 0: the records are 64-row / pair tiles (two halves, absent flags 1 << 27 / 1 << 28), else one-tile records (live[2 q]
+ * alone counts); info_out[8] = {steps in ranges, kept, segments, segments without a live step, most kept steps of a range, fewest, 0, 0}. */
+int sparta_vbs_set_live_forward(sparta_vbs_t* A, int32_t enable, void* stream);
+int sparta_vbs_live_forward_info(sparta_vbs_t* A, int64_t* info_out /* [8] */, void* stream);
+int sparta_vbs_live_forward_lists_get(sparta_vbs_t* A, void* steps_plain, int32_t* ranges_plain, uint8_t* live_bits, void* steps_live, int32_t* ranges_live,
+                                      void* stream);
+int sparta_live_forward_compact(const void* steps, int64_t n_steps, const int32_t* ranges, int64_t n_ranges, int32_t pair_image, const uint8_t* live /* [n_steps][2] */,
+                                void* steps_out, int32_t* ranges_out, int64_t* info_out /* [8] */);
 int sparta_vbs_live_info(sparta_vbs_t* A, int64_t* info_out /* [8] */, void* stream);
 int sparta_vbs_live_lists_get(sparta_vbs_t* A, int32_t* sd_groups, int32_t* sd_count, int32_t* t_blocks, int32_t* t_count, void* stream);
 int sparta_vbs_live_lists_host(int64_t cols, int64_t block_rows, int64_t block_col_size, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab,

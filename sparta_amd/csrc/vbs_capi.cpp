@@ -138,6 +138,9 @@ void destroy_impl(sparta_vbs* v) {
     if (v->d_live_t_items) (void)hipFree(v->d_live_t_items);
     if (v->d_live_wmap) (void)hipFree(v->d_live_wmap);
     if (v->d_live_words) (void)hipFree(v->d_live_words);
+    if (v->d_fwd_steps) (void)hipFree(v->d_fwd_steps);
+    if (v->d_fwd_wrange) (void)hipFree(v->d_fwd_wrange);
+    if (v->d_fwd_seg_last) (void)hipFree(v->d_fwd_seg_last);
     if (v->d_t_items) (void)hipFree(v->d_t_items);
     if (v->d_t_blocks) (void)hipFree(v->d_t_blocks);
     if (v->d_t_A) (void)hipFree(v->d_t_A);
@@ -1755,6 +1758,9 @@ int spmm16_core(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
         }
         const dim3 grid((unsigned)A->n_workers, (unsigned)n_nt);
         const int probe_ty = A->n_steps[1] >= A->n_steps[0] ? 1 : 0;
+        // live forward (sparta_vbs_set_live_forward): with a live set installed and the switch on, the stream image that has compacted records is walked by
+        // the live kernels (k_h16_live.hip) on them; read here, when the product is called or captured.  Not for a gathered B.
+        const bool fwd_live = A->live_on && A->live_fwd && A->live_fwd_built && A->live_fwd_ty >= 0 && shard_rows == 0;
         for (int ty = 1; ty >= 0; ty--) {
             if (A->n_steps[ty] == 0) continue;
             sp.steps = shard_rows > 0 ? A->d_steps_g[ty] : A->d_steps[ty]; sp.worker_range = A->d_wrange[ty]; sp.c_nt = c_store_nt(A, ty, sp.C, sp.ldc, sp.c_row_major != 0);
@@ -1768,12 +1774,21 @@ int spmm16_core(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
             // N % 256 == 0, no split tile, not through the ring, the plain plan (on the plan with two sub-worker ranges per workgroup a workgroup walks its tiles in
             // two ascending passes and the gain is gone: 41.1 us; allowed there with SPARTA_H16_SLAB256=2).  SPARTA_H16_SLAB256=0: off.
             const bool slab256 = ty == 0 && A->kp16 == 32 && !gth && !c_stage && A->n_split == 0 && n_cols % 256 == 0 && h16_uses_direct_kernel(32, false) && ldb16 * 64 * 2 < ((int64_t)1 << 31) - 65536 &&
-                                 [&] { const char* e = std::getenv("SPARTA_H16_SLAB256"); const int m = e ? atoi(e) : 1; return m == 2 || (m == 1 && !A->wide16); }();
+                                 [&] { const char* e = std::getenv("SPARTA_H16_SLAB256"); const int m = e ? atoi(e) : 1; return m == 2 || (m == 1 && !A->wide16); }() &&
+                                 !(fwd_live && ty == A->live_fwd_ty && A->wide16);      // (live ranges of two sub-workers are not adjacent: the non-slab kernel there)
             // 64-row tiles of 64-wide blocks (the dense hub of a power-law matrix under the fixed 64 x 64 grid), N % 256 == 0: four accumulators per wave over
             // 256-column slabs -- A read once per 256 columns, every B fragment used twice (k_h16.hip, QUAD); split tiles allowed.  SPARTA_H16_QUAD=0: off.
             const bool quad = ty == 1 && n_cols % 256 == 0 && h16_uses_direct_kernel(A->kp16, true) && ldb16 * 64 * 2 < ((int64_t)1 << 31) - 65536 &&
                               [] { const char* e = std::getenv("SPARTA_H16_QUAD"); return !e || atoi(e) != 0; }();
-            if (quad) {
+            const bool wide = ty == 0 && A->wide16;
+            const bool live_form = fwd_live && ty == A->live_fwd_ty && (quad || slab256 || h16_live_form_available(A->kp16, ty != 0, c_stage && !wide, wide));
+            A->fwd_last_form[ty] = live_form ? 2 : 1;
+            if (live_form) {
+                sp.steps = A->d_fwd_steps; sp.worker_range = A->d_fwd_wrange; sp.sub_ranges = 0;
+                if (quad) launch_h16_live_quad(A->kp16, bf16, dim3((unsigned)A->n_workers, (unsigned)(n_cols / 256)), st, sp);
+                else if (slab256) launch_h16_live_slab256(bf16, dim3((unsigned)A->n_workers, (unsigned)(n_cols / 256)), st, sp);
+                else launch_h16_live_stream(A->kp16, ty != 0, bf16, c_stage, wide, grid, st, sp);
+            } else if (quad) {
                 sp.sub_ranges = 0;
                 launch_h16_quad(A->kp16, bf16, gth, dim3((unsigned)A->n_workers, (unsigned)(n_cols / 256)), st, sp);
             } else if (slab256) {
@@ -2999,11 +3014,11 @@ int ensure_live_arrays(sparta_vbs_t* A, const char* entry) {
 }
 
 // the pattern-only map of the live words (handles with a fused image only): word -> block number, from the block table and the plan's own records of where
-// a step / a slice half starts in mab.  Built once, at the first enabling sparta_vbs_set_live_steps.
-int ensure_live_step_arrays(sparta_vbs_t* A, const char* entry) {
+// a step / a slice half starts in mab.  Built once, at the first enabling sparta_vbs_set_live_steps or sparta_vbs_set_live_forward: both read the same words.
+int ensure_live_word_map(sparta_vbs_t* A, const char* entry) {
     using sparta::fail;
-    if (A->live_steps_built) return SPARTA_OK;
-    if (g_capturing) return capture_refusal("build and upload the helper arrays of the live steps", entry);
+    if (A->live_words_built) return SPARTA_OK;
+    if (g_capturing) return capture_refusal("build and upload the map of the live words", entry);
     if (int rc = ensure_live_arrays(A, entry)) return rc;
     const int ty = sgd_fused_image(A);
     if (ty >= 0 && A->nztot > 0) {
@@ -3035,8 +3050,62 @@ int ensure_live_step_arrays(sparta_vbs_t* A, const char* entry) {
         HIP_TRY(hipMalloc((void**)&A->d_live_words, std::max<size_t>(wmap.size() * sizeof(uint32_t), 16)));
         if (!wmap.empty()) HIP_TRY(hipMemcpy(A->d_live_wmap, wmap.data(), wmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
+    A->live_words_built = true;
+    return SPARTA_OK;
+}
+
+int ensure_live_step_arrays(sparta_vbs_t* A, const char* entry) {
+    if (A->live_steps_built) return SPARTA_OK;
+    if (g_capturing) return capture_refusal("build and upload the helper arrays of the live steps", entry);
+    if (int rc = ensure_live_word_map(A, entry)) return rc;
     A->live_steps_built = true;
     return SPARTA_OK;
+}
+
+// Live forward: which stream image of the handle has live sibling kernels -- a 16-bit handle whose one stream image holds every stored element (the handles
+// the word map covers two words per step: no hub plan, one image, block width a multiple of 32).  -1: the plain kernels run under the switch.
+int live_forward_image(const sparta_vbs_t* A) {
+    if (A->dtype == SPARTA_F32 || A->nztot <= 0 || !(A->create_flags & SPARTA_CREATE_UPDATABLE)) return -1;
+    return sgd_fused_image(A);
+}
+
+// the second record array (a copy of the plain one, padding included: what lies outside the ranges is never rewritten), the second range array and the
+// segment map of that image.  Built once, at the first enabling sparta_vbs_set_live_forward.
+int ensure_live_forward_arrays(sparta_vbs_t* A, const char* entry) {
+    using sparta::fail;
+    if (A->live_fwd_built) return SPARTA_OK;
+    if (g_capturing) return capture_refusal("build and upload the helper arrays of the live forward product", entry);
+    if (int rc = ensure_live_word_map(A, entry)) return rc;
+    const int ty = live_forward_image(A);
+    if (ty >= 0 && A->live_n_words == 2 * A->n_steps[ty]) {
+        const std::vector<StepRec>& hs = A->h_steps[ty];
+        const int64_t n = A->n_steps[ty], n_ranges = (int64_t)A->n_workers * ((ty == 0 && A->wide16) ? 2 : 1);
+        if ((int64_t)hs.size() < n) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": the handle keeps no host copy of its step records");
+        std::vector<int32_t> ranges((size_t)n_ranges * 2);
+        HIP_TRY(hipMemcpy(ranges.data(), A->d_wrange[ty], ranges.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int64_t r = 0; r < n_ranges; r++)
+            if (ranges[(size_t)(2 * r)] < 0 || ranges[(size_t)(2 * r + 1)] > n)
+                return fail(SPARTA_ERR_INVALID, std::string(entry) + ": a worker range of the plan lies outside its step records");
+        std::vector<int32_t> seg_last((size_t)n);
+        live_forward_segments(hs.data(), n, ranges.data(), n_ranges, seg_last.data());
+        HIP_TRY(hipMalloc((void**)&A->d_fwd_steps, hs.size() * sizeof(StepRec)));
+        HIP_TRY(hipMalloc((void**)&A->d_fwd_wrange, ranges.size() * sizeof(int32_t)));
+        HIP_TRY(hipMalloc((void**)&A->d_fwd_seg_last, std::max<size_t>(seg_last.size() * sizeof(int32_t), 16)));
+        HIP_TRY(hipMemcpy(A->d_fwd_steps, hs.data(), hs.size() * sizeof(StepRec), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(A->d_fwd_wrange, ranges.data(), ranges.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(A->d_fwd_seg_last, seg_last.data(), seg_last.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        A->fwd_n_ranges = n_ranges; A->fwd_n_alloc = (int64_t)hs.size();
+        A->live_fwd_ty = ty;
+    }
+    A->live_fwd_built = true;
+    return SPARTA_OK;
+}
+
+// the compacted records and live ranges behind the words of the current snapshot, in stream order
+void launch_live_forward_lists(sparta_vbs_t* A, hipStream_t st) {
+    const int ty = A->live_fwd_ty;
+    if (!A->live_fwd_built || ty < 0) return;
+    launch_live_forward_compact(st, A->d_steps[ty], A->d_fwd_seg_last, A->d_wrange[ty], A->fwd_n_ranges, A->d_live_words, ty == 1, A->d_fwd_steps, A->d_fwd_wrange);
 }
 
 }  // namespace
@@ -3085,11 +3154,115 @@ extern "C" int sparta_vbs_set_live_blocks(sparta_vbs_t* A, const uint8_t* keep, 
         launch_live_spmm_t(st, A->d_t_items, A->d_t_blocks, A->d_live_tmap, A->live_block_cols, (int)((A->w + 31) / 32), keep, A->d_live_t_items, A->d_live_t_blocks,
                            A->d_live_tids, A->d_live_tcount);
     // live steps: the words of the image kernel behind the snapshot, in stream order (written whether or not the switch is on right now, once they exist)
-    if (A->live_steps_built && A->live_n_words > 0) launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
+    if (A->live_words_built && A->live_n_words > 0) launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
+    // live forward: the compacted records of the stream image behind the words (likewise written once they exist, whatever the switch says right now)
+    launch_live_forward_lists(A, st);
     HIP_TRY(hipGetLastError());
     A->live_on = true;
     return SPARTA_OK;
     SPARTA_GUARD_END("sparta_vbs_set_live_blocks")
+}
+
+extern "C" int sparta_vbs_set_live_forward(sparta_vbs_t* A, int32_t enable, void* stream) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* entry = "sparta_vbs_set_live_forward";
+    if (int rc = prune_handle_check(A, entry)) return rc;
+    if (!(A->create_flags & SPARTA_CREATE_UPDATABLE))
+        return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the handle was not made with SPARTA_CREATE_UPDATABLE (it keeps no map from its steps to its blocks)");
+    if (!enable) {                               // host state only
+        A->live_fwd = false;
+        return SPARTA_OK;
+    }
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, true);
+    if (int rc = ensure_live_forward_arrays(A, entry)) return rc;
+    if (A->live_on && A->live_fwd_ty >= 0) {     // a set is installed already: words and lists follow from its snapshot
+        launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
+        launch_live_forward_lists(A, st);
+        HIP_TRY(hipGetLastError());
+    }
+    A->live_fwd = true;
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_vbs_set_live_forward")
+}
+
+extern "C" int sparta_vbs_live_forward_info(sparta_vbs_t* A, int64_t* info_out, void* stream) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* entry = "sparta_vbs_live_forward_info";
+    if (int rc = prune_handle_check(A, entry)) return rc;
+    if (!info_out) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": NULL argument");
+    std::memset(info_out, 0, 8 * sizeof(int64_t));
+    const int ty = A->live_fwd_built ? A->live_fwd_ty : live_forward_image(A);
+    info_out[0] = A->live_fwd ? 1 : 0;
+    info_out[1] = ty + 1;
+    info_out[2] = A->fwd_last_form[0];
+    info_out[3] = A->fwd_last_form[1];
+    info_out[4] = ty >= 0 ? A->n_steps[ty] : 0;
+    info_out[6] = A->n_split;
+    info_out[7] = A->live_fwd_built && ty >= 0 ? A->fwd_n_ranges : 0;
+    if (!A->live_on || !A->live_fwd_built || ty < 0) return SPARTA_OK;
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, true);
+    if (g_capturing) return capture_refusal("read the live ranges back (synchronises)", entry);
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<int32_t> ranges((size_t)A->fwd_n_ranges * 2);
+    if (!ranges.empty()) HIP_TRY(hipMemcpy(ranges.data(), A->d_fwd_wrange, ranges.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int64_t r = 0; r < A->fwd_n_ranges; r++) info_out[5] += std::max(0, ranges[(size_t)(2 * r + 1)] - ranges[(size_t)(2 * r)]);
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_vbs_live_forward_info")
+}
+
+extern "C" int sparta_vbs_live_forward_lists_get(sparta_vbs_t* A, void* steps_plain, int32_t* ranges_plain, uint8_t* live_bits, void* steps_live, int32_t* ranges_live,
+                                                 void* stream) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* entry = "sparta_vbs_live_forward_lists_get";
+    if (int rc = prune_handle_check(A, entry)) return rc;
+    if (!A->live_on) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": no live set is installed");
+    if (!A->live_fwd_built || A->live_fwd_ty < 0) return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the handle has no live forward lists");
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, true);
+    if (g_capturing) return capture_refusal("read the live forward lists back (synchronises)", entry);
+    HIP_TRY(hipStreamSynchronize(st));
+    const int ty = A->live_fwd_ty;
+    const size_t n = (size_t)A->n_steps[ty], nr = (size_t)A->fwd_n_ranges;
+    if (steps_plain && n > 0) HIP_TRY(hipMemcpy(steps_plain, A->d_steps[ty], n * sizeof(StepRec), hipMemcpyDeviceToHost));
+    if (steps_live && n > 0) HIP_TRY(hipMemcpy(steps_live, A->d_fwd_steps, n * sizeof(StepRec), hipMemcpyDeviceToHost));
+    if (ranges_plain && nr > 0) HIP_TRY(hipMemcpy(ranges_plain, A->d_wrange[ty], nr * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (ranges_live && nr > 0) HIP_TRY(hipMemcpy(ranges_live, A->d_fwd_wrange, nr * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (live_bits && n > 0) {
+        std::vector<uint32_t> words(2 * n);
+        HIP_TRY(hipMemcpy(words.data(), A->d_live_words, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < words.size(); i++) live_bits[i] = words[i] != 0u ? 1 : 0;
+    }
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_vbs_live_forward_lists_get")
+}
+
+extern "C" int sparta_live_forward_compact(const void* steps, int64_t n_steps, const int32_t* ranges, int64_t n_ranges, int32_t pair_image, const uint8_t* live,
+                                           void* steps_out, int32_t* ranges_out, int64_t* info_out) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* entry = "sparta_live_forward_compact";
+    if (n_steps < 0 || n_ranges < 0 || !info_out || (n_steps > 0 && (!steps || !live || !steps_out)) || (n_ranges > 0 && (!ranges || !ranges_out)))
+        return fail(SPARTA_ERR_INVALID, std::string(entry) + ": bad sizes or NULL argument");
+    if (n_steps > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": more than 2^31 - 1 steps");
+    for (int64_t r = 0; r < n_ranges; r++)
+        if (ranges[2 * r] < 0 || ranges[2 * r + 1] > n_steps)
+            return fail(SPARTA_ERR_INVALID, std::string(entry) + ": a range lies outside the records");
+    int64_t info[8];
+    live_forward_compact_host((const StepRec*)steps, n_steps, ranges, n_ranges, pair_image != 0, live, (StepRec*)steps_out, ranges_out, info);
+    std::memcpy(info_out, info, sizeof(info));
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_live_forward_compact")
 }
 
 namespace {

@@ -3,7 +3,8 @@
 //   k_f32_stream.hip  persistent fp32 stream kernels, fix-up, B-tail copy, zero fill
 //   k_f32_direct.hip  the no-barrier fp32 kernel of the one-tile plan (one block per step)
 //   k_f32_packed.hip  ... and its packed form (partly empty blocks of a tile share a step)
-//   k_h16.hip         fp16 / bf16 storage: LDS-staged and direct stream kernels, conversions
+//   k_h16.hip         fp16 / bf16 storage: LDS-staged and direct stream kernels, conversions (the direct kernel's body: k_h16_direct.inc)
+//   k_h16_live.hip    the live form of the direct 16-bit kernel: the same body on the compacted records of sparta_vbs_set_live_forward
 //   k_sparse.hip      sparse-row kernels, layout transposes, row-block pack
 //   k_spmm_t.hip      the transposed product on a handle's own stored blocks (sparta_vbs_spmm_t)
 //   k_update.hip      new values for the images of an updatable handle (sparta_vbs_set_values)
@@ -543,10 +544,21 @@ struct sparta_vbs {
     // word per step (fp32) / two per slice (16-bit) for its kernel: the map word -> block number is pattern only (built at the first enabling call), the words
     // are written from the snapshot by one launch of k_live.hip.  The two-pass form needs nothing of its own: it walks d_prune with d_live_keep.
     bool live_steps = false, live_steps_built = false;
+    bool live_words_built = false;                             // the word map and the words exist (live steps or live forward asked for them)
     int32_t* d_live_wmap = nullptr;                            // [live_n_words]
     uint32_t* d_live_words = nullptr;                          // [live_n_words]
     int64_t live_n_words = 0;
     int32_t step_last_live = 0;                                // the last step skipped dead blocks (sparta_vbs_step_info word 2)
+    // live forward (sparta_vbs_set_live_forward): the switch is host state and acts only while a live set is installed.  Handles that have the word map
+    // (16-bit, one stream image, no hub plan) hold a second record array and a second range array for that image; k_live.hip rewrites them from the live
+    // words behind every set_live_blocks, and the live kernels of k_h16_live.hip walk them.  The plain arrays are never written.
+    bool live_fwd = false, live_fwd_built = false;
+    int live_fwd_ty = -1;                                      // the stream image that has the live form, -1: none (the plain kernels run under the switch)
+    sparta_dev::StepRec* d_fwd_steps = nullptr;                // [n_steps[ty] + padding] d_steps[ty], every range's kept steps first
+    int32_t* d_fwd_wrange = nullptr;                           // the live ranges, as d_wrange[ty]
+    int32_t* d_fwd_seg_last = nullptr;                         // [n_steps[ty]] last record of every step's segment (pattern only)
+    int64_t fwd_n_ranges = 0, fwd_n_alloc = 0;
+    int32_t fwd_last_form[2] = {0, 0};                         // per stream image: the form the last 16-bit product ran (0 none yet, 1 plain, 2 live)
 };
 
 namespace sparta_dev {
@@ -651,6 +663,15 @@ void launch_live_spmm_t(hipStream_t st, const SpmmTItem* items, const SpmmTBlock
                         SpmmTItem* live_items, SpmmTBlock* live_blocks, int32_t* live_ids, int32_t* live_count);
 // ... and the live words of the steps' image kernels: words[i] = all ones if block wmap[i] is live in the snapshot, else 0 (wmap[i] < 0: 0)
 void launch_live_step_words(hipStream_t st, const int32_t* wmap, int64_t n_words, const uint8_t* snap, uint32_t* words);
+// ... and live forward: the records of one stream image compacted per range from the live words (two per step), the rule of live_forward_compact_host
+void launch_live_forward_compact(hipStream_t st, const StepRec* steps, const int32_t* seg_last, const int32_t* ranges, int64_t n_ranges, const uint32_t* words, bool pair,
+                                 StepRec* out, int32_t* ranges_out);
+// k_h16_live.hip: the live form of the no-barrier 16-bit kernel on those records (B not gathered, loads three steps ahead); k_h16.hip says whether the launch
+// that launch_h16_stream would make has a live sibling
+void launch_h16_live_stream(int kp, bool mi2, bool bf16, bool c_stage, bool wide, dim3 grid, hipStream_t st, const StreamParams& sp);
+void launch_h16_live_slab256(bool bf16, dim3 grid, hipStream_t st, const StreamParams& sp);
+void launch_h16_live_quad(int kp, bool bf16, dim3 grid, hipStream_t st, const StreamParams& sp);
+bool h16_live_form_available(int kp, bool mi2, bool c_stage, bool wide);
 
 // vbs_plan.cpp
 struct StreamPlanIn {
@@ -745,6 +766,10 @@ void live_lists_host(const LiveMapsHost& M, const uint8_t* keep, int32_t* sd_gro
 // first[i] of the range's mab (first[i] < 0: a slice half that is not there, wmap[i] = -1); wmap[i] = the number of the block they lie in, by the block table's
 // offsets (block_off[n_blocks], ascending, mab order).  SPARTA_ERR_INVALID if a word's first and last column lie in different blocks: the image kernels test one
 // bit per lane, which is right only where a step / slice half never leaves its block (block widths that are multiples of 32: every plan with an image kernel)
+// live forward: the end of every step's segment, and the compaction rule on the host (what vbs_fwdlive_compact_kernel computes), see vbs_plan.cpp
+void live_forward_segments(const StepRec* steps, int64_t n_steps, const int32_t* ranges, int64_t n_ranges, int32_t* seg_last);
+void live_forward_compact_host(const StepRec* steps, int64_t n_steps, const int32_t* ranges, int64_t n_ranges, bool pair, const uint8_t* live, StepRec* out,
+                               int32_t* ranges_out, int64_t* info);
 int build_live_word_map(const int64_t* block_off, int64_t n_blocks, int64_t nztot, const int64_t* first, const int32_t* ld, int64_t n_words, int64_t span, int32_t* wmap);
 // one block of the 16-bit image from its column-major h x w source
 void pack_spmm_t_block(const float* blk, int64_t h, int64_t w, bool bf16, uint16_t* dst);

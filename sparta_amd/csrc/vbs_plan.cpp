@@ -1238,4 +1238,76 @@ void live_lists_host(const LiveMapsHost& M, const uint8_t* keep, int32_t* sd_gro
     info[7] = 0;
 }
 
+// ---- live forward (sparta_vbs_set_live_forward): the rule that compacts the step records of one stream image, on the host ---------------------
+// A segment is the run of records of a range up to and including the next STEP_LAST record (or the end of the range): what one worker owns of a tile.
+// seg_last[q] = the position of the last record of step q's segment (-1 outside every range): pattern only, what the device form reads instead of searching.
+void live_forward_segments(const StepRec* steps, int64_t n_steps, const int32_t* ranges, int64_t n_ranges, int32_t* seg_last) {
+    for (int64_t q = 0; q < n_steps; q++) seg_last[q] = -1;
+    for (int64_t r = 0; r < n_ranges; r++) {
+        const int64_t b = ranges[2 * r], e = ranges[2 * r + 1];
+        for (int64_t q = b; q < e;) {
+            int64_t sl = q;
+            while (sl < e - 1 && !(steps[sl].mt_flags & STEP_LAST)) sl++;
+            for (int64_t s = q; s <= sl; s++) seg_last[s] = (int32_t)sl;
+            q = sl + 1;
+        }
+    }
+}
+
+// live[2 q] / live[2 q + 1]: rows 0..31 / rows 32..63 of step q.  A half counts where it is present: the lower half of every record of an image of <= 32-row
+// tiles, and on the 64-row image (pair) the halves without their absent flag.  Per range: the kept steps first and in order (every live step, and the first
+// step of a segment without one), the dropped steps behind them unchanged and in order, and the live range (begin, begin + kept).  A kept record keeps its
+// a_off, b_row, h, pad and STEP_TAIL; STEP_FIRST sits on the first kept step of its segment, STEP_LAST on the last one, which also takes STEP_SPLIT, c_row,
+// slot and the tile rows of the segment's last record; a dead half gets its absent flag, the kept step of an all-dead segment STEP_LO_ABSENT (the whole step
+// of a one-tile record) or both flags.  out[] outside the ranges = steps[].  info: {steps in ranges, kept steps, segments, all-dead segments, most kept
+// steps of a range, fewest, 0, 0}.
+void live_forward_compact_host(const StepRec* steps, int64_t n_steps, const int32_t* ranges, int64_t n_ranges, bool pair, const uint8_t* live, StepRec* out,
+                               int32_t* ranges_out, int64_t* info) {
+    for (int64_t q = 0; q < n_steps; q++) out[q] = steps[q];
+    for (int k = 0; k < 8; k++) info[k] = 0;
+    info[5] = n_ranges > 0 ? INT64_MAX : 0;
+    std::vector<StepRec> kept, dropped;
+    for (int64_t r = 0; r < n_ranges; r++) {
+        const int64_t b = ranges[2 * r], e = ranges[2 * r + 1];
+        kept.clear(); dropped.clear();
+        for (int64_t q = b; q < e;) {
+            int64_t sl = q;
+            while (sl < e - 1 && !(steps[sl].mt_flags & STEP_LAST)) sl++;
+            const StepRec& last = steps[sl];
+            auto lo_live = [&](int64_t s) { return (!pair || !(steps[s].mt_flags & STEP_LO_ABSENT)) && live[2 * s] != 0; };
+            auto hi_live = [&](int64_t s) { return pair && !(steps[s].mt_flags & STEP_HI_ABSENT) && live[2 * s + 1] != 0; };
+            int64_t first_live = -1, last_live = -1;
+            for (int64_t s = q; s <= sl; s++)
+                if (lo_live(s) || hi_live(s)) { if (first_live < 0) first_live = s; last_live = s; }
+            info[2]++;
+            if (first_live < 0) info[3]++;
+            for (int64_t s = q; s <= sl; s++) {
+                const bool lv = lo_live(s) || hi_live(s);
+                if (!lv && !(first_live < 0 && s == q)) { dropped.push_back(steps[s]); continue; }
+                StepRec k = steps[s];
+                const bool is_first = lv ? s == first_live : true, is_last = lv ? s == last_live : true;
+                k.mt_flags &= ~(STEP_FIRST | STEP_LAST | STEP_SPLIT);
+                if (is_first) k.mt_flags |= STEP_FIRST;
+                if (is_last) {
+                    k.mt_flags = (k.mt_flags & ~0xffff) | (last.mt_flags & 0xffff) | STEP_LAST | (last.mt_flags & STEP_SPLIT);
+                    k.c_row = last.c_row;
+                    k.slot = last.slot;
+                }
+                if (!lo_live(s)) k.mt_flags |= STEP_LO_ABSENT;
+                if (pair && !hi_live(s)) k.mt_flags |= STEP_HI_ABSENT;
+                kept.push_back(k);
+            }
+            q = sl + 1;
+        }
+        std::copy(kept.begin(), kept.end(), out + b);
+        std::copy(dropped.begin(), dropped.end(), out + b + (int64_t)kept.size());
+        ranges_out[2 * r] = (int32_t)b;
+        ranges_out[2 * r + 1] = (int32_t)(b + (int64_t)kept.size());
+        info[0] += std::max<int64_t>(e - b, 0);
+        info[1] += (int64_t)kept.size();
+        info[4] = std::max<int64_t>(info[4], (int64_t)kept.size());
+        info[5] = std::min<int64_t>(info[5], (int64_t)kept.size());
+    }
+}
+
 }  // namespace sparta_dev

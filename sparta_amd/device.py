@@ -523,6 +523,42 @@ class DeviceVBS(ValuesRecord):
             return
         check(lib.sparta_vbs_set_live_steps(self.h, 1, self._live_stream(stream)))
 
+    def set_live_forward(self, on, stream=None):
+        """sparta_vbs_set_live_forward: with on=True and a live set installed (set_live_blocks) the 16-bit forward product walks the steps of live blocks only:
+        a dead block adds nothing to C whatever the handle holds for it, and neither its values nor the rows of B are read on its behalf.  On values whose
+        dead blocks are zero (what BlockPruner leaves) C is the plain product, the sign of a zero aside.  Needs updatable=True.  Handles without the live form
+        (fp32, a hub plan, two stream images, block widths that are no multiple of 32) accept the switch and keep their kernels: live_forward_info() says
+        which.  Off by default; without a live set the switch does nothing.  The first enabling call builds helper arrays and cannot be captured; later
+        calls, and set_live_blocks from then on, are launches only (torch's current stream)."""
+        if not on:
+            check(lib.sparta_vbs_set_live_forward(self.h, 0, None))
+            return
+        check(lib.sparta_vbs_set_live_forward(self.h, 1, self._live_stream(stream)))
+
+    def live_forward_info(self, stream=None):
+        """sparta_vbs_live_forward_info (synchronises when a live set is installed): {"switch", "capable" (the stream image with the live form: 0 none, 1 the <= 32-row tiles, 2 the 64-row / pair tiles), "form_one_tile", "form_pair" (what the last 16-bit
+        product ran on each stream image: 0 none yet, 1 the plain kernels, 2 the live kernels), "steps", "kept_steps", "split_tiles", "ranges"}"""
+        a = np.zeros(8, np.int64)
+        check(lib.sparta_vbs_live_forward_info(self.h, a.ctypes.data_as(_i64p), self._live_stream(stream)))
+        keys = ["switch", "capable", "form_one_tile", "form_pair", "steps", "kept_steps", "split_tiles", "ranges"]
+        return {k: int(a[i]) for i, k in enumerate(keys)}
+
+    def live_forward_lists(self, stream=None):
+        """sparta_vbs_live_forward_lists_get (synchronises; for tests and records): {"steps": the plain records of the stream image with the live form (a
+        structured array, host.STEP_DTYPE), "ranges": int32 [ranges][2], "live": uint8 [steps][2] (rows 0..31 / 32..63 of every step's slice), "pair": whether
+        the image holds 64-row / pair tiles, "steps_live", "ranges_live": what the live kernels walk}.  host.live_forward_compact(steps, ranges, pair, live)
+        is the same rule on the host."""
+        from .host import STEP_DTYPE
+        fi = self.live_forward_info(stream)
+        n, nr = fi["steps"], fi["ranges"]
+        out = {"steps": np.zeros(n, STEP_DTYPE), "ranges": np.zeros((nr, 2), np.int32), "live": np.zeros((n, 2), np.uint8),
+               "steps_live": np.zeros(n, STEP_DTYPE), "ranges_live": np.zeros((nr, 2), np.int32)}
+        i32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+        check(lib.sparta_vbs_live_forward_lists_get(self.h, out["steps"].ctypes.data_as(C.c_void_p), out["ranges"].ctypes.data_as(i32p), out["live"].ctypes.data_as(u8p),
+                                                    out["steps_live"].ctypes.data_as(C.c_void_p), out["ranges_live"].ctypes.data_as(i32p), self._live_stream(stream)))
+        out["pair"] = fi["capable"] == 2
+        return out
+
     def _live_stream(self, stream):
         import torch
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream)

@@ -15,6 +15,29 @@ _i32p = C.POINTER(C.c_int32)
 _f32p = C.POINTER(C.c_float)
 
 
+# a step record of a stream image (StepRec, csrc/vbs_device.hpp): 32 bytes, as DeviceVBS.live_forward_lists returns them and live_forward_compact takes them
+STEP_DTYPE = np.dtype([("a_off", "<i8"), ("b_row", "<i4"), ("h", "<i4"), ("c_row", "<i4"), ("mt_flags", "<i4"), ("slot", "<i4"), ("pad", "<i4")])
+STEP_FIRST, STEP_LAST, STEP_SPLIT, STEP_TAIL, STEP_LO_ABSENT, STEP_HI_ABSENT = 1 << 16, 1 << 17, 1 << 18, 1 << 19, 1 << 27, 1 << 28
+
+
+def live_forward_compact(steps, ranges, pair, live):
+    """sparta_live_forward_compact: the rule of the live forward product (DeviceVBS.set_live_forward) as host code, no GPU.  steps: STEP_DTYPE records of one
+    stream image; ranges: int32 [n][2] disjoint (begin, end) pairs, each walked as one unit; pair: the records are 64-row / pair tiles; live: uint8
+    [steps][2], rows 0..31 / 32..63 of every step.  Returns (steps_out, ranges_out, info): per range the kept steps first and in order, the dropped ones
+    behind them, the live range (begin, begin + kept); info = {"steps", "kept", "segments", "dead_segments", "max_kept", "min_kept"}."""
+    steps = np.ascontiguousarray(steps, STEP_DTYPE)
+    ranges = np.ascontiguousarray(ranges, np.int32).reshape(-1, 2)
+    live = np.ascontiguousarray(live, np.uint8).reshape(-1)
+    if live.size != 2 * steps.size:
+        raise ValueError("live must hold two entries per step")
+    out, r_out, info = np.zeros_like(steps), np.zeros_like(ranges), np.zeros(8, np.int64)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None      # noqa: E731
+    check(lib.sparta_live_forward_compact(vp(steps), steps.size, _p32(ranges) if ranges.size else None, ranges.shape[0], 1 if pair else 0,
+                                          live.ctypes.data_as(C.POINTER(C.c_uint8)) if live.size else None, vp(out), _p32(r_out) if r_out.size else None, _p64(info)))
+    keys = ["steps", "kept", "segments", "dead_segments", "max_kept", "min_kept"]
+    return out, r_out, {k: int(info[i]) for i, k in enumerate(keys)}
+
+
 def _p64(a):
     return a.ctypes.data_as(_i64p)
 

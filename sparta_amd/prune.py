@@ -60,14 +60,21 @@ class BlockPruner:
 
     live_steps=True (needs skip_pruned=True): the handles are also switched to live steps (DeviceVBS.set_live_steps) once they have their mask, so that the
     optimizer's step skips the pruned blocks too -- it reads and writes the weights, the gradient and the state of the live blocks only, with the bits of the
-    plain step.  The pruned blocks of values must stay +0.0, which prune guarantees; their gradient and state are not looked at any more."""
+    plain step.  The pruned blocks of values must stay +0.0, which prune guarantees; their gradient and state are not looked at any more.
 
-    def __init__(self, optimizer_or_pairs, scope="global", normalize=True, skip_pruned=False, live_steps=False):
+    live_forward=True (needs skip_pruned=True): the handles are also switched to the live forward product (DeviceVBS.set_live_forward) once they have their
+    mask: the 16-bit forward product of a handle that has the live form walks the steps of the live blocks only.  The values of the pruned blocks are zero,
+    so the product is the same, the sign of a zero aside; handles without the live form (fp32 among them) keep their kernels."""
+
+    def __init__(self, optimizer_or_pairs, scope="global", normalize=True, skip_pruned=False, live_steps=False, live_forward=False):
         import torch
         if scope not in ("global", "layer"):
             raise ValueError("scope must be 'global' or 'layer'")
         if live_steps and not skip_pruned:
             raise ValueError("live_steps=True needs skip_pruned=True (the steps skip the blocks of the live set the handles are given)")
+        if live_forward and not skip_pruned:
+            raise ValueError("live_forward=True needs skip_pruned=True (the forward product skips the blocks of the live set the handles are given)")
+        self.live_forward = bool(live_forward)
         self.optimizer = optimizer_or_pairs if hasattr(optimizer_or_pairs, "pairs") else None
         self.pairs = [(h, v) for h, v in (self.optimizer.pairs if self.optimizer is not None else optimizer_or_pairs)]
         self.scope, self.normalize, self.skip_pruned, self.live_steps = scope, bool(normalize), bool(skip_pruned), bool(live_steps)
@@ -105,6 +112,8 @@ class BlockPruner:
             handle.set_live_blocks(self._keep[i])
             if self.live_steps:
                 handle.set_live_steps(True)
+            if self.live_forward:
+                handle.set_live_forward(True)
 
     def prune(self, sparsity):
         """select() on scores(), then per pair the pruned blocks zeroed in values, values.grad (if present) and the optimizer's state (where allocated), and
