@@ -692,6 +692,29 @@ int sparta_vbs_mask_blocks(sparta_vbs_t* A, const uint8_t* keep, float* T0, floa
  * sparta_vbs_live_lists_host: the same rule as host code (no GPU) on VBS arrays and a host keep, arguments as sparta_vbs_block_table_host; any of the four
  * outputs may be NULL (info_out[3] and [5] give the sizes). */
 int sparta_vbs_set_live_blocks(sparta_vbs_t* A, const uint8_t* keep, void* stream);
+/* sparta_vbs_sddmm_block_ssq: the block scores of X * Y^T on the stored blocks, without G -- what sparta_vbs_block_ssq would give on the G of
+ * sparta_vbs_sddmm, for the blocks `sel` selects, in one pass that writes one fp64 partial per (32-row tile, stored column) instead of nztot floats.  Device
+ * pointers only.  X, ldx, Y, ldy, k: the operands of sparta_vbs_sddmm; sel: n_blocks device bytes in the numbering of sparta_vbs_block_ssq / _mask_blocks (mab
+ * order, blocks of block-rows of height 0 included, a range handle: the numbering of its range), or NULL = every block; ssq_out: n_blocks doubles.  Takes every
+ * handle that both sparta_vbs_sddmm and sparta_vbs_block_ssq take, all three types, any creation flags (handles of sparta_vbs_create_from_csr / _transposed:
+ * SPARTA_ERR_UNSUPPORTED).  SPARTA_ERR_INVALID, nothing launched: a NULL handle; X, Y or ssq_out NULL with n_blocks > 0; k <= 0; ssq_out not 8-byte aligned;
+ * ldx < rows, ldy < cols, an odd ldx or ldy on a 16-bit handle.  n_blocks == 0 succeeds and launches nothing.  THE CONTRACT:
+ *   - a SELECTED block (sel == NULL or sel[b] != 0): ssq_out[b] = the fp64 sum of the exact fp64 squares of the block's n_in elements inside the matrix, the
+ *     elements being exactly the fp32 values sparta_vbs_sddmm(accumulate = 0) stores for the block on a handle without a live set (the same kernel body: the
+ *     same MFMA sequence over k, the same accumulator bits).  Positions past `cols` contribute nothing.  The order of the sum is fixed per handle and sel: rows
+ *     of a tile by xor-shuffle, then the block's (tile, column) partials 64 apart per lane in tile-major order, then the lanes by xor-shuffle.  Bit-identical
+ *     from run to run, no atomics, plain IEEE: an Inf or NaN inside the block makes that block's score non-finite and no other;
+ *   - an UNSELECTED block: ssq_out[b] = +0.0, written on every call.  Neither Y's rows nor, on its behalf alone, X's rows are read for it: the dependency rule
+ *     of a dead block of the live SDDMM ("WITH A LIVE-BLOCK SET INSTALLED" above);
+ *   - blocks of a block-row of height 0 score +0.0;
+ *   - the result does not depend on whether a live set is installed or on what it holds, and the call changes neither the live set, the live-steps switch, the
+ *     live-forward switch nor any image: it walks lists of its own, written from sel by the kernel of sparta_vbs_set_live_blocks;
+ *   - the FIRST call on a handle builds and uploads pattern-only helpers (those of the live set, a slot offset per block-row, 24 bytes per block) and allocates
+ *     its scratch (8 bytes per (32-row tile, stored column) of the pattern); under capture it returns SPARTA_ERR_UNSUPPORTED.  Every later call is three
+ *     launches (the lists of sel, the product, one wave per block for the final sums): no allocation, no synchronisation, capturable; a replay reads X, Y and
+ *     sel again.  dt_ms spans all three (and synchronises: refused under capture). */
+int sparta_vbs_sddmm_block_ssq(sparta_vbs_t* A, const void* X, int64_t ldx, const void* Y, int64_t ldy, int32_t k, const uint8_t* sel, double* ssq_out, void* stream,
+                               float* dt_ms);
 /* Live steps: with enable != 0 and a live set installed, sparta_vbs_sgd_step / _adam_step and their _ctl forms skip the dead blocks (the contract: "WITH A
  * LIVE-BLOCK SET INSTALLED AND LIVE STEPS ON" above).  Opt-in, off at creation.  The switch is host state, read when a step is called (or captured); it has an
  * effect only while a live set is installed: sparta_vbs_set_live_blocks(A, NULL, ...) puts the steps back on the plain kernels without clearing it, and the

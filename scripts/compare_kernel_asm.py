@@ -2,7 +2,8 @@
 """Compare the bodies of kernels in two `hipcc -S` outputs: compare_kernel_asm.py OLD.s NEW.s SUBSTRING
 
 For every global symbol whose name contains SUBSTRING, the text from its label to its .Lfunc_end label is taken from both files, comments and blank lines
-dropped, and compared line for line.  Prints one line per kernel that differs or is missing and a summary line; exit status 1 if anything differs.
+dropped, the function's index taken out of its local labels (.LBB<index>_<n>: the index counts the functions in front, so a kernel added before it
+renumbers them), and compared line for line.  Prints one line per kernel that differs or is missing and a summary line; exit status 1 if anything differs.
 Used to show that moving a kernel's body (into an .inc, behind `if constexpr`) left its instructions as they were (DESIGN.md sections 3.12 and 3.15)."""
 import re
 import sys
@@ -11,6 +12,7 @@ import sys
 def bodies(path, sub):
     out, name, cur = {}, None, []
     label = re.compile(r"^([A-Za-z_][\w$.]*):")
+    local = re.compile(r"\.LBB\d+_(\d+)")
     for line in open(path, errors="replace"):
         if name is None:
             m = label.match(line)
@@ -21,7 +23,7 @@ def bodies(path, sub):
             out[name] = cur
             name = None
             continue
-        text = line.split(";", 1)[0].rstrip()
+        text = local.sub(r".LBB_\1", line.split(";", 1)[0].rstrip())
         if text.strip():
             cur.append(text)
     return out

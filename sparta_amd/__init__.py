@@ -23,7 +23,7 @@ from .device import DeviceVBS, vbs_multiply, device_count  # noqa: F401
 from . import gen, dist, autograd, optim, gradctl, prune, epilogue  # noqa: F401
 from .optim import VbsSGD, VbsAdamW  # noqa: F401
 from .gradctl import GradCtl  # noqa: F401
-from .prune import BlockPruner  # noqa: F401
+from .prune import BlockPruner, BlockProbe, select_swap  # noqa: F401
 from .epilogue import epilogue_fwd, epilogue_bwd  # noqa: F401
 
 # revision tag of the device kernels: PMC-derived numbers kept under profiles/ (HBM traffic per launch) carry it, and bench.py

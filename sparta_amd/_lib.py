@@ -55,6 +55,7 @@ SYMBOLS = [
     "sparta_vbs_block_table_host", "sparta_vbs_block_count", "sparta_vbs_block_ssq", "sparta_vbs_mask_blocks",
     "sparta_vbs_set_live_blocks", "sparta_vbs_live_info", "sparta_vbs_live_lists_get", "sparta_vbs_live_lists_host", "sparta_vbs_set_live_steps", "sparta_vbs_set_live_forward", "sparta_vbs_live_forward_info", "sparta_vbs_live_forward_lists_get", "sparta_live_forward_compact",
     "sparta_epilogue_fwd", "sparta_epilogue_scratch_bytes", "sparta_epilogue_bwd",
+    "sparta_vbs_sddmm_block_ssq",
 ]
 
 
@@ -190,6 +191,7 @@ def _load():
     L.sparta_vbs_spmm.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp,
                                   C.c_int32, f32p]
     L.sparta_vbs_sddmm.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int32, f32p, C.c_int32, C.c_int32, vp, f32p]
+    L.sparta_vbs_sddmm_block_ssq.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_double), vp, f32p]
     L.sparta_vbs_spmm_gathered.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32, f32p]
     L.sparta_vbs_spmm_gathered_ld.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32, f32p]
     L.sparta_pack_blocks.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp]

@@ -27,7 +27,7 @@ def _function():
 
     class _VbsLinear(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, x, values, handle, refresh=False):
+        def forward(ctx, x, values, handle, refresh=False, probe=None):
             n = x.shape[0]
             rec = handle._autograd_values                       # (tensor, version) the handle's values were last taken from; None after any other set_values
             if (rec is None or rec[0] is not values or rec[1] != values._version or refresh
@@ -37,6 +37,7 @@ def _function():
             handle.spmm(x.detach(), y, n, accumulate=False)
             ctx.handle = handle
             ctx.rec = rec
+            ctx.probe = probe
             ctx.save_for_backward(x, values)
             return y
 
@@ -56,13 +57,15 @@ def _function():
             if ctx.needs_input_grad[1]:
                 grad_values = torch.empty(handle._nztot(), dtype=torch.float32, device=x.device)
                 handle.sddmm(gy, x.detach(), grad_values, n, accumulate=False)
-            return grad_x, grad_values, None, None
+            if ctx.probe is not None:                           # the block scores of the same product, for the blocks the probe selects
+                handle.sddmm_block_ssq(gy, x.detach(), n, sel=ctx.probe.sel, out=ctx.probe.out)
+            return grad_x, grad_values, None, None, None
 
     class _VbsLinearEpilogue(torch.autograd.Function):
         """y = act(x @ A^T + bias) in out_dtype.  The values logic is _VbsLinear's; the elementwise work is epilogue_fwd / epilogue_bwd."""
 
         @staticmethod
-        def forward(ctx, x, values, bias, handle, refresh, activation, out_dtype):
+        def forward(ctx, x, values, bias, handle, refresh, activation, out_dtype, probe=None):
             n = x.shape[0]
             rec = handle._autograd_values
             if (rec is None or rec[0] is not values or rec[1] != values._version or refresh
@@ -75,6 +78,7 @@ def _function():
             y = epilogue.epilogue_fwd(z, b, activation, out_dtype, out=z if in_place else None)
             ctx.handle = handle
             ctx.rec = rec
+            ctx.probe = probe
             ctx.activation = activation
             ctx.has_bias = bias is not None
             ctx.save_for_backward(x, values, *(() if bias is None else (bias,)), *(() if activation == "none" else (z,)))
@@ -90,8 +94,8 @@ def _function():
             n = x.shape[0]
             need_dbias = ctx.has_bias and ctx.needs_input_grad[2]
             grad_x = grad_values = grad_bias = None
-            if not (need_dbias or ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
-                return None, None, None, None, None, None, None
+            if not (need_dbias or ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.probe is not None):
+                return None, None, None, None, None, None, None, None
             # one pass: dz in the handle's operand type (what _VbsLinear's .to(x.dtype) did), and the bias gradient
             gy = grad_y.contiguous()
             if ctx.activation == "none" and not need_dbias and gy.dtype == x.dtype:
@@ -107,7 +111,9 @@ def _function():
             if ctx.needs_input_grad[1]:
                 grad_values = torch.empty(handle._nztot(), dtype=torch.float32, device=x.device)
                 handle.sddmm(dz, x.detach(), grad_values, n, accumulate=False)
-            return grad_x, grad_values, grad_bias, None, None, None, None
+            if ctx.probe is not None:                           # the block scores of the same product, for the blocks the probe selects
+                handle.sddmm_block_ssq(dz, x.detach(), n, sel=ctx.probe.sel, out=ctx.probe.out)
+            return grad_x, grad_values, grad_bias, None, None, None, None, None
 
     global _FN_EPILOGUE
     _FN = _VbsLinear
@@ -120,7 +126,7 @@ def _function_epilogue():
     return _FN_EPILOGUE
 
 
-def vbs_linear(x, handle, values, refresh=False, *, bias=None, activation="none", out_dtype=None):
+def vbs_linear(x, handle, values, refresh=False, *, bias=None, activation="none", out_dtype=None, probe=None):
     """y = x @ A^T, i.e. torch.nn.functional.linear(x, A) with A the block-sparse matrix of `handle` (a DeviceVBS made with updatable=True and
     transposable=True; ValueError otherwise) holding `values`.  With bias, activation or out_dtype: y = act(x @ A^T + bias) in out_dtype (below).
 
@@ -148,7 +154,12 @@ def vbs_linear(x, handle, values, refresh=False, *, bias=None, activation="none"
     float32 y; z is saved for backward only with an activation.  Backward: ONE kernel (epilogue.epilogue_bwd) turns grad_y (any of the three types) into
     dz = grad_y * act'(z + bias) in the handle's operand type -- the operand of spmm_t and sddmm -- and, if bias requires grad, into grad_bias (float32
     (rows,), the row sums of the fp32 dz in a fixed fp64 order: bit-identical from run to run); with only bias requiring grad neither product runs.
-    ValueError for anything else in the three arguments."""
+    ValueError for anything else in the three arguments.
+
+    probe: None, or an object with .sel (uint8 / bool, n_blocks) and .out (float64, n_blocks) on the handle's device, such as BlockPruner.probe(i) gives.
+    Backward then also calls handle.sddmm_block_ssq(dz, x, n, sel=probe.sel, out=probe.out) with the operands of its sddmm call -- the squared gradient
+    norm of every selected block, the pruned ones of a BlockPruner, which the live sddmm no longer computes -- whether or not values requires grad (as long
+    as backward runs at all).  With probe=None the launches and the results are those of the call without the argument."""
     import torch
     if not (handle.updatable and handle.transposable):
         raise ValueError("vbs_linear needs a handle made with updatable=True and transposable=True")
@@ -164,5 +175,5 @@ def vbs_linear(x, handle, values, refresh=False, *, bias=None, activation="none"
     if not (values.is_cuda and values.dtype == torch.float32 and values.dim() == 1 and values.numel() == handle._nztot() and values.is_contiguous()):
         raise ValueError("values must be a contiguous float32 device tensor of nztot = %d elements" % handle._nztot())
     if plain:
-        return _function().apply(x, values, handle, bool(refresh))
-    return _function_epilogue().apply(x, values, bias, handle, bool(refresh), activation, out_dtype)
+        return _function().apply(x, values, handle, bool(refresh), probe)
+    return _function_epilogue().apply(x, values, bias, handle, bool(refresh), activation, out_dtype, probe)

@@ -23,6 +23,10 @@
 // (accumulate = 0) or skipped, neither read nor written (accumulate = 1).  The groups without a live block are not visited: their zeros under accumulate = 0
 // come from a launch of the mask kernel of k_prune.hip on G and the snapshot, in front (vbs_capi.cpp).  (Storing them inside this kernel was built and
 // measured: 2 to 6 us faster at the median, inside the arms' ranges -- profiles/live/README.md -- and not kept.)
+//
+// Score form (sparta_vbs_sddmm_block_ssq; vbs_sdscore_*_kernel): a third mode of the two bodies, the LIVE form on the lists of the call's selection up to the
+// end of a group, where the accumulator is not stored but reduced -- sd_score -- to one fp64 sum of squares per stored column, written to a slot of the handle's
+// scratch (one per 32-row tile and stored column); vbs_sdscore_finish_kernel, one wave per block, sums a block's slots in one fixed order.  G is not touched.
 #include "vbs_kernel_common.hpp"
 
 namespace sparta_dev {
@@ -33,6 +37,7 @@ constexpr int kSdWaves = 4;
 constexpr int kSdGpw = kSdGroups / kSdWaves;      // groups per wave
 constexpr int kKC32 = 32;                          // k chunk, fp32 (16 MFMA steps of depth 2)
 constexpr int kKC16 = 32;                          // k chunk, 16-bit (2 MFMA steps of depth 16)
+constexpr int kSdPlain = 0, kSdLive = 1, kSdScore = 2;   // the modes of the two bodies; kSdScore is kSdLive up to the store
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -114,6 +119,44 @@ __device__ __forceinline__ void sd_store(const SddmmParams& p, const BlockRowDes
     }
 }
 
+// the score form's end of a group: instead of storing, the 32 x 32 accumulator is reduced to one fp64 sum of squares per stored column.  A lane squares its
+// sixteen values in fp64 (exact: 24 x 24 bits) under the masks of sd_store -- the column is inside the matrix and of a selected block, the row is one of the
+// tile's mt -- and the 32 lanes of a half-wave (the rows of the half's sixteen columns) are summed by halving: at distance 16 a lane keeps eight of its
+// registers and takes its partner's sums of the same eight for the eight it hands over, at 8 four, at 4 two, at 2 one, and the last exchange at distance 1
+// leaves both lanes of a pair with the sum of all 32 rows of register r = (lane >> 1) & 15 -- 16 shuffles of a double where 16 whole butterflies take 80, and
+// one fixed tree per column.  The even lane of the pair writes it, one 8-byte store, to the column's slot; a column of an unselected block has no slot
+// written (the finish kernel does not read it), a ragged column of a selected block gets +0.0.  Called by whole waves (the group loops are wave-uniform).
+template <int N>
+__device__ __forceinline__ void sd_halve(const double (&in)[2 * N], double (&out)[N], bool upper, int dist) {
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        const double mine = upper ? in[j + N] : in[j], theirs = upper ? in[j] : in[j + N];
+        out[j] = mine + __shfl_xor(theirs, dist);
+    }
+}
+
+__device__ __forceinline__ void sd_score(const SddmmParams& p, const BlockRowDesc& br, const f32x16& acc, double* slots, int64_t q0, int64_t nq, int mt, int lane,
+                                         const uint8_t* keep) {
+    const int i = lane & 31;
+    const int64_t cq = sd_column<true>(p, br, nq, q0 + i, keep);
+    const unsigned long long live = __ballot(cq >= 0);
+    const unsigned long long dead = __ballot(cq == -2);
+    double s16[16], s8[8], s4[4], s2[2], s1[1];
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int j = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const double d = (i < mt && ((live >> j) & 1)) ? (double)acc[r] : 0.0;
+        s16[r] = d * d;
+    }
+    sd_halve<8>(s16, s8, (lane & 16) != 0, 16);
+    sd_halve<4>(s8, s4, (lane & 8) != 0, 8);
+    sd_halve<2>(s4, s2, (lane & 4) != 0, 4);
+    sd_halve<1>(s2, s1, (lane & 2) != 0, 2);
+    const double sum = s1[0] + __shfl_xor(s1[0], 1);
+    const int r = i >> 1, j = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    if (!(lane & 1) && q0 + j < nq && !((dead >> j) & 1)) slots[q0 + j] = sum;
+}
+
 // the groups of an item.  LIVE: positions g0 .. g0 + 15 of the block-row's compacted list (ng = 0: the item has nothing to do); else g0 .. g0 + ng - 1
 template <bool LIVE>
 struct SdGroups {
@@ -132,8 +175,9 @@ struct SdGroups {
     }
 };
 
-template <bool LIVE>
-__device__ __forceinline__ void sddmm_f32_body(const SddmmParams& p, const SddmmLive& lv) {
+template <int MODE>
+__device__ __forceinline__ void sddmm_f32_body(const SddmmParams& p, const SddmmLive& lv, const SddmmScore& sc) {
+    constexpr bool LIVE = MODE != kSdPlain;
     __shared__ float xs[kKC32][32];
     const SddmmItem it = p.items[blockIdx.x];
     const SdGroups<LIVE> grp(it, lv);
@@ -198,12 +242,13 @@ __device__ __forceinline__ void sddmm_f32_body(const SddmmParams& p, const Sddmm
 #pragma unroll
     for (int t = 0; t < kSdGpw; t++) {
         if (wv + kSdWaves * t >= grp.ng) break;
-        sd_store<LIVE>(p, br, acc[t], p.G, base, (int64_t)gq[t] * 32, nq, br.h, mt, lane, p.accumulate, lv.keep);
+        if constexpr (MODE == kSdScore) sd_score(p, br, acc[t], sc.slots + sc.soff[it.brow] + (int64_t)(it.r0 >> 5) * nq, (int64_t)gq[t] * 32, nq, mt, lane, lv.keep);
+        else sd_store<LIVE>(p, br, acc[t], p.G, base, (int64_t)gq[t] * 32, nq, br.h, mt, lane, p.accumulate, lv.keep);
     }
 }
 
-__global__ __launch_bounds__(kThreads) void vbs_sddmm_f32_kernel(const SddmmParams p) { sddmm_f32_body<false>(p, SddmmLive{}); }
-__global__ __launch_bounds__(kThreads) void vbs_sdlive_f32_kernel(const SddmmParams p, const SddmmLive lv) { sddmm_f32_body<true>(p, lv); }
+__global__ __launch_bounds__(kThreads) void vbs_sddmm_f32_kernel(const SddmmParams p) { sddmm_f32_body<kSdPlain>(p, SddmmLive{}, SddmmScore{}); }
+__global__ __launch_bounds__(kThreads) void vbs_sdlive_f32_kernel(const SddmmParams p, const SddmmLive lv) { sddmm_f32_body<kSdLive>(p, lv, SddmmScore{}); }
 
 // 8 consecutive k (kb + 8 (lane >> 5) .. + 7) of entity lane & 31 from a [k][32] image of 16-bit values: two transposed reads.  Lane 4q + p of a
 // 16-lane group addresses row kb + 8 (lane >> 5) + 4 t + q, entities 16 ((lane >> 4) & 1) + 4 p .. + 3; lane i of the group receives entity i.
@@ -222,8 +267,9 @@ struct SdLds16 {
 
 // VEC (w, ldy multiples of 8, Y 16-byte aligned): a run of 8 stored columns is 8 consecutive columns of Y, 16 aligned bytes -- one load per lane
 // puts 8 columns of one k in the image (4 lanes a row of it); otherwise every lane gathers its own column, one 16-bit load per k
-template <bool BF16, bool VEC, bool LIVE>
-__device__ __forceinline__ void sddmm_h16_body(const SddmmParams& p, const SddmmLive& lv) {
+template <bool BF16, bool VEC, int MODE>
+__device__ __forceinline__ void sddmm_h16_body(const SddmmParams& p, const SddmmLive& lv, const SddmmScore& sc) {
+    constexpr bool LIVE = MODE != kSdPlain;
     __shared__ __attribute__((aligned(16))) SdLds16 lds;   // (the only LDS object: its base, and every row, is 16-byte aligned)
     const SddmmItem it = p.items[blockIdx.x];
     const SdGroups<LIVE> grp(it, lv);
@@ -313,14 +359,42 @@ __device__ __forceinline__ void sddmm_h16_body(const SddmmParams& p, const Sddmm
 #pragma unroll
     for (int t = 0; t < kSdGpw; t++) {
         if (wv + kSdWaves * t >= grp.ng) break;
-        sd_store<LIVE>(p, br, acc[t], p.G, base, (int64_t)gq[t] * 32, nq, br.h, mt, lane, p.accumulate, lv.keep);
+        if constexpr (MODE == kSdScore) sd_score(p, br, acc[t], sc.slots + sc.soff[it.brow] + (int64_t)(it.r0 >> 5) * nq, (int64_t)gq[t] * 32, nq, mt, lane, lv.keep);
+        else sd_store<LIVE>(p, br, acc[t], p.G, base, (int64_t)gq[t] * 32, nq, br.h, mt, lane, p.accumulate, lv.keep);
     }
 }
 
 template <bool BF16, bool VEC>
-__global__ __launch_bounds__(kThreads) void vbs_sddmm_h16_kernel(const SddmmParams p) { sddmm_h16_body<BF16, VEC, false>(p, SddmmLive{}); }
+__global__ __launch_bounds__(kThreads) void vbs_sddmm_h16_kernel(const SddmmParams p) { sddmm_h16_body<BF16, VEC, kSdPlain>(p, SddmmLive{}, SddmmScore{}); }
 template <bool BF16, bool VEC>
-__global__ __launch_bounds__(kThreads) void vbs_sdlive_h16_kernel(const SddmmParams p, const SddmmLive lv) { sddmm_h16_body<BF16, VEC, true>(p, lv); }
+__global__ __launch_bounds__(kThreads) void vbs_sdlive_h16_kernel(const SddmmParams p, const SddmmLive lv) { sddmm_h16_body<BF16, VEC, kSdLive>(p, lv, SddmmScore{}); }
+// the score forms (sparta_vbs_sddmm_block_ssq), behind the ten kernels above: the same bodies up to the end of a group, where sd_score stands for sd_store
+__global__ __launch_bounds__(kThreads) void vbs_sdscore_f32_kernel(const SddmmParams p, const SddmmLive lv, const SddmmScore sc) { sddmm_f32_body<kSdScore>(p, lv, sc); }
+template <bool BF16, bool VEC>
+__global__ __launch_bounds__(kThreads) void vbs_sdscore_h16_kernel(const SddmmParams p, const SddmmLive lv, const SddmmScore sc) {
+    sddmm_h16_body<BF16, VEC, kSdScore>(p, lv, sc);
+}
+
+// one wave per block, kPruneWaves blocks per workgroup (as k_prune.hip): an unselected block (per the snapshot) scores +0.0 and reads nothing; otherwise lane l
+// takes the block's slots l, l + 64, ... in the order tile by tile, column by column, and the lanes are summed by xor-shuffle.  No LDS, no barrier, no atomics.
+__global__ __launch_bounds__(kThreads) void vbs_sdscore_finish_kernel(const ScoreBlock* __restrict__ blocks, int64_t n_blocks, int w, const uint8_t* __restrict__ snap,
+                                                                     const double* __restrict__ slots, double* __restrict__ ssq_out) {
+    const int64_t b = (int64_t)blockIdx.x * kPruneWaves + (threadIdx.x >> 6);
+    if (b >= n_blocks) return;                  // (the whole wave)
+    const int lane = threadIdx.x & 63;
+    double s = 0.0;
+    if (snap[b] != 0) {                         // (the whole wave)
+        const ScoreBlock blk = blocks[b];
+        const int64_t n = (int64_t)blk.ntiles * w;
+        for (int64_t e = lane; e < n; e += 64) {
+            const int64_t t = e / w, c = e - t * w;
+            s += slots[blk.slot0 + t * blk.tstride + c];
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) ssq_out[b] = s;
+}
 
 }  // namespace
 
@@ -342,6 +416,21 @@ void launch_sddmm_live(int dtype, unsigned n_items, hipStream_t st, const SddmmP
     else if (dtype == SPARTA_BF16) hipLaunchKernelGGL((vbs_sdlive_h16_kernel<true, false>), dim3(n_items), dim3(kThreads), 0, st, p, lv);
     else if (vec) hipLaunchKernelGGL((vbs_sdlive_h16_kernel<false, true>), dim3(n_items), dim3(kThreads), 0, st, p, lv);
     else hipLaunchKernelGGL((vbs_sdlive_h16_kernel<false, false>), dim3(n_items), dim3(kThreads), 0, st, p, lv);
+}
+
+void launch_sddmm_score(int dtype, unsigned n_items, hipStream_t st, const SddmmParams& p, const SddmmLive& lv, const SddmmScore& sc) {
+    if (n_items == 0) return;
+    const bool vec = p.w % 8 == 0 && p.ldy % 8 == 0 && (uintptr_t)p.Y % 16 == 0;
+    if (dtype == SPARTA_F32) hipLaunchKernelGGL(vbs_sdscore_f32_kernel, dim3(n_items), dim3(kThreads), 0, st, p, lv, sc);
+    else if (dtype == SPARTA_BF16 && vec) hipLaunchKernelGGL((vbs_sdscore_h16_kernel<true, true>), dim3(n_items), dim3(kThreads), 0, st, p, lv, sc);
+    else if (dtype == SPARTA_BF16) hipLaunchKernelGGL((vbs_sdscore_h16_kernel<true, false>), dim3(n_items), dim3(kThreads), 0, st, p, lv, sc);
+    else if (vec) hipLaunchKernelGGL((vbs_sdscore_h16_kernel<false, true>), dim3(n_items), dim3(kThreads), 0, st, p, lv, sc);
+    else hipLaunchKernelGGL((vbs_sdscore_h16_kernel<false, false>), dim3(n_items), dim3(kThreads), 0, st, p, lv, sc);
+}
+
+void launch_sddmm_score_finish(hipStream_t st, const ScoreBlock* blocks, int64_t n_blocks, int w, const uint8_t* snap, const double* slots, double* ssq) {
+    if (n_blocks == 0) return;
+    hipLaunchKernelGGL(vbs_sdscore_finish_kernel, dim3((unsigned)((n_blocks + kPruneWaves - 1) / kPruneWaves)), dim3(kThreads), 0, st, blocks, n_blocks, w, snap, slots, ssq);
 }
 
 }  // namespace sparta_dev

@@ -136,6 +136,13 @@ void destroy_impl(sparta_vbs* v) {
     if (v->d_live_tcount) (void)hipFree(v->d_live_tcount);
     if (v->d_live_t_blocks) (void)hipFree(v->d_live_t_blocks);
     if (v->d_live_t_items) (void)hipFree(v->d_live_t_items);
+    if (v->d_score_keep) (void)hipFree(v->d_score_keep);
+    if (v->d_score_ones) (void)hipFree(v->d_score_ones);
+    if (v->d_score_groups) (void)hipFree(v->d_score_groups);
+    if (v->d_score_gcount) (void)hipFree(v->d_score_gcount);
+    if (v->d_score_soff) (void)hipFree(v->d_score_soff);
+    if (v->d_score_blocks) (void)hipFree(v->d_score_blocks);
+    if (v->d_score_slots) (void)hipFree(v->d_score_slots);
     if (v->d_live_wmap) (void)hipFree(v->d_live_wmap);
     if (v->d_live_words) (void)hipFree(v->d_live_words);
     if (v->d_fwd_steps) (void)hipFree(v->d_fwd_steps);
@@ -3161,6 +3168,96 @@ extern "C" int sparta_vbs_set_live_blocks(sparta_vbs_t* A, const uint8_t* keep, 
     A->live_on = true;
     return SPARTA_OK;
     SPARTA_GUARD_END("sparta_vbs_set_live_blocks")
+}
+
+// ---- sparta_vbs_sddmm_block_ssq: the score form of the SDDMM (k_sddmm.hip) -----------------------------------------------------------------------
+namespace {
+
+// the pattern-only helpers (the live set's goff, made without installing a set; the slot offset of every block-row; the finish record of every block) and the
+// arrays every call writes: the snapshot of sel, its group lists and counts, the slots
+int ensure_score_arrays(sparta_vbs_t* A, const char* entry) {
+    using sparta::fail;
+    if (A->score_built) return SPARTA_OK;
+    if (g_capturing) return capture_refusal("build and upload the helper arrays of the block scores", entry);
+    if (int rc = ensure_sddmm_items(A)) return rc;
+    if (int rc = ensure_live_arrays(A, entry)) return rc;
+    const int64_t nb = A->nblocks, w = A->w;
+    std::vector<int64_t> soff;
+    std::vector<ScoreBlock> rec((size_t)nb);
+    int64_t slots = 0, q = 0;
+    for (int64_t ib = 0; ib < A->block_rows; ib++) {
+        const int64_t h = A->h_row_part[(size_t)ib + 1] - A->h_row_part[(size_t)ib], tiles = (h + 31) / 32, nq = A->h_nzcount[(size_t)ib] * w;
+        if (h > 0) soff.push_back(slots);
+        for (int64_t b = 0; b < A->h_nzcount[(size_t)ib]; b++, q++) rec[(size_t)q] = ScoreBlock{slots + b * w, nq, (int32_t)tiles, 0};
+        slots += tiles * nq;
+    }
+    if ((int64_t)soff.size() != A->n_brows || q != nb) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": the score maps disagree with the handle's block-rows");
+    auto alloc = [](void** ptr, size_t bytes) {
+        if (*ptr) { (void)hipFree(*ptr); *ptr = nullptr; }
+        return hipMalloc(ptr, std::max<size_t>(bytes, 16));
+    };
+    HIP_TRY(alloc((void**)&A->d_score_keep, (size_t)nb));
+    HIP_TRY(alloc((void**)&A->d_score_ones, (size_t)nb));
+    HIP_TRY(alloc((void**)&A->d_score_groups, (size_t)A->live_n_groups * sizeof(int32_t)));
+    HIP_TRY(alloc((void**)&A->d_score_gcount, soff.size() * sizeof(int32_t)));
+    HIP_TRY(alloc((void**)&A->d_score_soff, soff.size() * sizeof(int64_t)));
+    HIP_TRY(alloc((void**)&A->d_score_blocks, rec.size() * sizeof(ScoreBlock)));
+    HIP_TRY(alloc((void**)&A->d_score_slots, (size_t)slots * sizeof(double)));
+    if (nb > 0) {
+        HIP_TRY(hipMemset(A->d_score_ones, 1, (size_t)nb));
+        HIP_TRY(hipMemcpy(A->d_score_blocks, rec.data(), rec.size() * sizeof(ScoreBlock), hipMemcpyHostToDevice));
+    }
+    if (!soff.empty()) HIP_TRY(hipMemcpy(A->d_score_soff, soff.data(), soff.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    A->score_built = true;
+    return SPARTA_OK;
+}
+
+}  // namespace
+
+extern "C" int sparta_vbs_sddmm_block_ssq(sparta_vbs_t* A, const void* X, int64_t ldx, const void* Y, int64_t ldy, int32_t k, const uint8_t* sel, double* ssq_out,
+                                          void* stream, float* dt_ms) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* entry = "sparta_vbs_sddmm_block_ssq";
+    if (k <= 0) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": k must be > 0");
+    if (!A) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": NULL handle");
+    if (A->ext_sparse)
+        return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the handle does not hold the dense blocks of every block-row (made by sparta_vbs_create_from_csr)");
+    if (int rc = prune_handle_check(A, entry)) return rc;
+    if (A->nblocks > 0 && (!X || !Y || !ssq_out)) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": X, Y or ssq_out is NULL");
+    if ((uintptr_t)ssq_out % 8 != 0) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": ssq_out must be 8-byte aligned");
+    if (ldx < A->rows || ldy < A->cols) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": ldx < rows or ldy < cols");
+    if (ldx > (INT64_C(1) << 61) / k || ldy > (INT64_C(1) << 61) / k) return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": ldx * k or ldy * k beyond 2^61");
+    if (A->dtype != SPARTA_F32 && ((ldx | ldy) & 1)) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": 16-bit handles need even ldx, ldy");
+    if (A->nblocks == 0) return SPARTA_OK;
+
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, true);
+    if (g_capturing && dt_ms) return capture_refusal("time the product (dt_ms != NULL synchronises)", entry);
+    if (int rc = ensure_score_arrays(A, entry)) return rc;
+
+    SddmmParams p;
+    p.brows = A->d_brows; p.jab = A->d_jab; p.items = A->d_sd_items;
+    p.X = X; p.Y = Y; p.G = nullptr;
+    p.ldx = ldx; p.ldy = ldy; p.cols = A->cols;
+    p.k = k; p.w = (int32_t)A->w; p.accumulate = 0; p.pad = 0;
+    if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
+    // the lists of sel, by the kernel of the live set into the score call's own arrays: the live set of the handle, installed or not, is neither read nor written
+    launch_live_sddmm(st, A->d_brows, A->n_brows, (int)A->w, sel ? sel : A->d_score_ones, A->nblocks, A->d_score_keep, A->d_live_goff, A->d_score_groups,
+                      A->d_score_gcount);
+    launch_sddmm_score(A->dtype, (unsigned)A->n_sd_items, st, p, SddmmLive{A->d_score_groups, A->d_live_goff, A->d_score_gcount, A->d_score_keep},
+                       SddmmScore{A->d_score_slots, A->d_score_soff});
+    launch_sddmm_score_finish(st, A->d_score_blocks, A->nblocks, (int)A->w, A->d_score_keep, A->d_score_slots, ssq_out);
+    HIP_TRY(hipGetLastError());
+    if (dt_ms) {
+        HIP_TRY(hipEventRecord(A->ev1, st));
+        HIP_TRY(hipEventSynchronize(A->ev1));
+        HIP_TRY(hipEventElapsedTime(dt_ms, A->ev0, A->ev1));
+    }
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_vbs_sddmm_block_ssq")
 }
 
 extern "C" int sparta_vbs_set_live_forward(sparta_vbs_t* A, int32_t enable, void* stream) {

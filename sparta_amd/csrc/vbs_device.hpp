@@ -275,6 +275,15 @@ struct SddmmLive {
     const int32_t* count;
     const uint8_t* keep;
 };
+// the score form (sparta_vbs_sddmm_block_ssq): the SddmmLive of the call holds the lists of `sel`; a wave writes the fp64 sum of squares of the tile's rows of
+// stored column q of block-row `brow`, tile r0 / 32, to slots[soff[brow] + (r0 / 32) * nb * w + q] -- one slot per (32-row tile, stored column) of the pattern;
+// the finish kernel sums a block's ntiles x w slots (slot0 + t * tstride + c) in one fixed order
+struct SddmmScore {
+    double* slots;
+    const int64_t* soff;
+};
+struct ScoreBlock { int64_t slot0, tstride; int32_t ntiles, pad; };
+static_assert(sizeof(ScoreBlock) == 24, "ScoreBlock must stay 24 bytes");
 
 // sparta_vbs_set_values (k_update.hip): where one 16-bit slice of an updatable handle comes from.  Row rr of the slice, column kk of its k range, is
 // mab[off_lo + kk * h_lo + rr] for rr < rows_lo, else mab[off_hi + kk * h_hi + (rr - 32)] for 32 <= rr < 32 + rows_hi, else zero.  An ordinary tile has
@@ -559,6 +568,16 @@ struct sparta_vbs {
     int32_t* d_fwd_seg_last = nullptr;                         // [n_steps[ty]] last record of every step's segment (pattern only)
     int64_t fwd_n_ranges = 0, fwd_n_alloc = 0;
     int32_t fwd_last_form[2] = {0, 0};                         // per stream image: the form the last 16-bit product ran (0 none yet, 1 plain, 2 live)
+    // block scores of the SDDMM (sparta_vbs_sddmm_block_ssq): a second snapshot / group list / count, written from `sel` by every call (goff is d_live_goff:
+    // pattern only), the all-ones selection that stands in for sel == NULL, and the pattern-only slot offsets, finish records and the fp64 slots themselves
+    bool score_built = false;
+    uint8_t* d_score_keep = nullptr;                           // [nblocks] the snapshot of sel
+    uint8_t* d_score_ones = nullptr;                           // [nblocks] 1
+    int32_t* d_score_groups = nullptr;                         // [live_n_groups]
+    int32_t* d_score_gcount = nullptr;                         // [n_brows]
+    int64_t* d_score_soff = nullptr;                           // [n_brows] first slot of the block-row
+    sparta_dev::ScoreBlock* d_score_blocks = nullptr;          // [nblocks]
+    double* d_score_slots = nullptr;                           // [sum over block-rows of ceil(h / 32) * nb * w]
 };
 
 namespace sparta_dev {
@@ -607,6 +626,10 @@ void launch_sddmm(int dtype, unsigned n_items, hipStream_t st, const SddmmParams
 // ... with a live set: an item's groups come from lv's compacted list, stored columns of dead blocks are not loaded (accumulate = 0: stored as +0.0f; 1: skipped);
 // the groups that are not on the list are not written: under accumulate = 0 the caller zeroes the dead blocks first (launch_mask_blocks with the snapshot)
 void launch_sddmm_live(int dtype, unsigned n_items, hipStream_t st, const SddmmParams& p, const SddmmLive& lv);
+// ... the score form: the live form on the lists of `sel` (lv), p.G unused; instead of storing, every wave writes its slots of sc.  Then one wave per block:
+// ssq[b] = the sum of the block's slots, +0.0 where snap[b] == 0
+void launch_sddmm_score(int dtype, unsigned n_items, hipStream_t st, const SddmmParams& p, const SddmmLive& lv, const SddmmScore& sc);
+void launch_sddmm_score_finish(hipStream_t st, const ScoreBlock* blocks, int64_t n_blocks, int w, const uint8_t* snap, const double* slots, double* ssq);
 // k_update.hip (sparta_vbs_set_values): new values, nztot floats in the mab layout, into the images of an updatable handle
 void launch_update_copy(hipStream_t st, const float* mab, int64_t n, float* A);        // the reference-layout image (fp32 handles)
 // the fragment image of the fp32 one-tile plan, k-compaction redone per step (position table, fragments, STEP_KPAIRS of steps[q].mt_flags);

@@ -462,6 +462,42 @@ class DeviceVBS(ValuesRecord):
                                        C.byref(dt) if timed else None))
         return (out, dt.value) if timed else out
 
+    def sddmm_block_ssq(self, X, Y, k, sel=None, out=None, ldx=None, ldy=None, timed=False, stream=None):
+        """sparta_vbs_sddmm_block_ssq, device tensors: per stored block the float64 sum of the squares of what sddmm(X, Y, accumulate=False) would store for
+        it on a handle without a live set -- block_ssq of that gradient -- without writing the gradient.  X, Y, k, ldx, ldy: as for sddmm.  sel: a contiguous
+        uint8 or bool tensor of n_blocks elements on this device (numbered as for mask_blocks), or None = every block; a block with sel[b] == 0 scores +0.0
+        and the operands are not read on its behalf.  out: a contiguous float64 tensor of n_blocks elements on this device, or None (allocated).  The live
+        set of the handle, installed or not, plays no part and is not changed.  Stream-ordered on torch's current stream; launches only after the first
+        call on the handle (capturable from then on; a replay reads X, Y and sel again).  Returns out, or (out, kernel ms) if timed."""
+        import torch
+        want = {_lib.F32: torch.float32, _lib.F16: torch.float16, _lib.BF16: torch.bfloat16}[self.dtype]
+        if not (X.is_cuda and Y.is_cuda and X.dtype == want and Y.dtype == want):
+            raise ValueError("X and Y must be %s tensors on the GPU" % want)
+        if X.device.index != self.device or Y.device.index != self.device:
+            raise ValueError("X and Y must live on device %d" % self.device)
+        k = int(k)
+        if k <= 0:
+            raise ValueError("k must be > 0")
+        ldx = self.rows if ldx is None else int(ldx)
+        ldy = self.cols if ldy is None else int(ldy)
+        if (X.numel() < ldx * (k - 1) + self.rows or Y.numel() < ldy * (k - 1) + self.cols or not X.is_contiguous() or not Y.is_contiguous()):
+            raise ValueError("X or Y too small / not contiguous for the stated leading dimensions")
+        n = self.n_blocks
+        if sel is not None and not (sel.is_cuda and sel.dtype in (torch.uint8, torch.bool) and sel.device.index == self.device and sel.is_contiguous()
+                                    and sel.numel() == n):
+            raise ValueError("sel must be a contiguous uint8 or bool tensor of n_blocks = %d elements on device %d" % (n, self.device))
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=X.device)
+        elif not (out.is_cuda and out.dtype == torch.float64 and out.device.index == self.device and out.is_contiguous() and out.numel() == n):
+            raise ValueError("out must be a contiguous float64 tensor of n_blocks = %d elements on device %d" % (n, self.device))
+        st = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+        dt = C.c_float(0)
+        sp = C.cast(C.c_void_p(sel.data_ptr() if sel is not None and n else None), C.POINTER(C.c_uint8))
+        check(lib.sparta_vbs_sddmm_block_ssq(self.h, C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy, k, sp,
+                                             C.cast(C.c_void_p(out.data_ptr() if n else None), C.POINTER(C.c_double)), C.c_void_p(st),
+                                             C.byref(dt) if timed else None))
+        return (out, dt.value) if timed else out
+
     def mask_blocks(self, keep, *tensors, timed=False, stream=None):
         """sparta_vbs_mask_blocks, device tensors: every block b with keep[b] == 0 stored as +0.0 -- all its elements, the positions past cols included
         -- in each of `tensors` (contiguous float32 tensors of nztot elements on this device in the layout of VBR.mab, updated in place; they must not

@@ -39,6 +39,66 @@ def select(scores, keep, sparsity, scope="global"):
     return list(torch.split(new, [k.numel() for k in keep]))
 
 
+def select_swap(mag_scores, grad_scores, keep, n_swap, scope="global"):
+    """The swap rule of dynamic sparse training (RigL, SET): drop the weakest live blocks, grow as many dead ones.  Pure torch, any device, no synchronisation.
+
+    mag_scores, grad_scores, keep: lists with one tensor per layer -- a magnitude score and a gradient score per block, and the current mask (uint8 or bool,
+    0 = dead).  Over all layers (scope "global", n_swap an int) or per layer ("layer", n_swap a list with one int per layer):
+      drop  the n_swap live blocks with the lowest magnitude score, in select's order: stable, ties to the lower (layer, block) index, a non-finite score last;
+      grow  the n_swap blocks with the highest gradient score among those that were dead BEFORE this call (a block dropped now is not grown now): stable,
+            ties to the lower index, a non-finite score counts as the lowest, and a block whose score is -inf is never grown (the caller marks the blocks
+            without an element inside the matrix that way).
+    If either side holds fewer candidates than n_swap both counts shrink to the smaller side, so the number of live blocks never changes; the counts are
+    tensors and are compared with the ranks on the device.  Returns the new masks, a list of uint8 tensors."""
+    import torch
+    if scope not in ("global", "layer"):
+        raise ValueError("scope must be 'global' or 'layer'")
+    if not (len(mag_scores) == len(grad_scores) == len(keep)) or any(m.numel() != k.numel() or g.numel() != k.numel() for m, g, k in zip(mag_scores, grad_scores, keep)):
+        raise ValueError("mag_scores, grad_scores and keep must hold one tensor per layer, of the same lengths")
+    per_layer = scope == "layer"
+    if per_layer:
+        if not isinstance(n_swap, (list, tuple)) or len(n_swap) != len(keep):
+            raise ValueError("scope 'layer' takes n_swap as a list with one count per layer")
+        counts = [int(n) for n in n_swap]
+    else:
+        counts = [int(sum(n_swap)) if isinstance(n_swap, (list, tuple)) else int(n_swap)]
+    if any(n < 0 for n in counts):
+        raise ValueError("n_swap must be >= 0")
+
+    def ranks(key, member):
+        """position of every member in ascending key order (stable: ties to the lower index); the others come behind all members"""
+        order = torch.sort(key, stable=True).indices
+        order = order[torch.sort((~member[order]).to(torch.uint8), stable=True).indices]
+        rank = torch.empty_like(order)
+        rank[order] = torch.arange(key.numel(), device=order.device)
+        return rank
+
+    def one(m, g, live, n):
+        m, g = m.reshape(-1).to(torch.float64), g.reshape(-1).to(torch.float64)
+        inf = torch.full_like(m, float("inf"))
+        cand = ~live & ~(g == -inf)                                                      # (NaN and +Inf may be grown, after every finite score)
+        drop_rank = ranks(torch.where(torch.isfinite(m), m, inf), live)
+        grow_rank = ranks(torch.where(torch.isfinite(g), -g, inf), cand)
+        count = torch.minimum(torch.minimum(live.sum(), cand.sum()), torch.full((), n, dtype=torch.int64, device=m.device))
+        return ((live & (drop_rank >= count)) | (cand & (grow_rank < count))).to(torch.uint8)
+
+    lives = [k.reshape(-1) != 0 for k in keep]
+    if per_layer:
+        return [one(m, g, l, n) for m, g, l, n in zip(mag_scores, grad_scores, lives, counts)]
+    if not keep:
+        return []
+    cat = lambda ts: torch.cat([t.reshape(-1).to(torch.float64) for t in ts])
+    new = one(cat(mag_scores), cat(grad_scores), torch.cat(lives), counts[0])
+    return list(torch.split(new, [k.numel() for k in keep]))
+
+
+class BlockProbe:
+    """what vbs_linear(probe=...) fills: sel, a uint8 tensor of n_blocks (1 = score this block), and out, a float64 tensor of n_blocks (the scores)"""
+
+    def __init__(self, sel, out):
+        self.sel, self.out = sel, out
+
+
 class BlockPruner:
     """Magnitude pruning of the stored blocks of block-sparse layers, on the device.
 
@@ -64,7 +124,11 @@ class BlockPruner:
 
     live_forward=True (needs skip_pruned=True): the handles are also switched to the live forward product (DeviceVBS.set_live_forward) once they have their
     mask: the 16-bit forward product of a handle that has the live form walks the steps of the live blocks only.  The values of the pruned blocks are zero,
-    so the product is the same, the sign of a zero aside; handles without the live form (fp32 among them) keep their kernels."""
+    so the product is the same, the sign of a zero aside; handles without the live form (fp32 among them) keep their kernels.
+
+    Regrowing (dynamic sparse training): pass probe(i) to pair i's vbs_linear(..., probe=...) and backward leaves the squared gradient norm of every PRUNED
+    block in it (DeviceVBS.sddmm_block_ssq: the live sddmm no longer computes those gradients).  regrow(fraction) then swaps: the weakest live blocks are
+    pruned and as many pruned blocks with the largest gradient come back, as zeros -- the number of live blocks stays what prune made it."""
 
     def __init__(self, optimizer_or_pairs, scope="global", normalize=True, skip_pruned=False, live_steps=False, live_forward=False):
         import torch
@@ -78,10 +142,14 @@ class BlockPruner:
         self.optimizer = optimizer_or_pairs if hasattr(optimizer_or_pairs, "pairs") else None
         self.pairs = [(h, v) for h, v in (self.optimizer.pairs if self.optimizer is not None else optimizer_or_pairs)]
         self.scope, self.normalize, self.skip_pruned, self.live_steps = scope, bool(normalize), bool(skip_pruned), bool(live_steps)
-        self._keep, self._n_in = [], []
+        self._keep, self._n_in, self._probes = [], [], []
         for handle, values in self.pairs:
             self._keep.append(torch.ones(handle.n_blocks, dtype=torch.uint8, device=values.device))
             self._n_in.append(handle.block_ssq(torch.ones_like(values, requires_grad=False)))          # 1 + 1 + ...: the elements inside the matrix, exactly
+            self._probes.append(BlockProbe(torch.zeros(handle.n_blocks, dtype=torch.uint8, device=values.device),
+                                           torch.zeros(handle.n_blocks, dtype=torch.float64, device=values.device)))
+        sizes = [k.numel() for k in self._keep]
+        self._live = sizes if self._per_layer() else [sum(sizes)]   # live blocks per pair, kept on the host; scope "global" knows only their sum
 
     def scores(self):
         """per pair: block_ssq(values), divided by the block's elements inside the matrix when normalize (a block without any scores +Inf)"""
@@ -107,6 +175,7 @@ class BlockPruner:
         handle, values = self.pairs[i]
         tensors = [values.detach()] + ([values.grad] if values.grad is not None else []) + self._state_tensors(i)
         handle.mask_blocks(self._keep[i], *tensors)
+        self._probes[i].sel.copy_(self._keep[i] == 0)
         handle.set_values(values.detach())
         if self.skip_pruned:
             handle.set_live_blocks(self._keep[i])
@@ -119,6 +188,42 @@ class BlockPruner:
         """select() on scores(), then per pair the pruned blocks zeroed in values, values.grad (if present) and the optimizer's state (where allocated), and
         the handle given the new values"""
         new = select(self.scores(), self._keep, sparsity, self.scope)
+        for i, k in enumerate(new):
+            self._keep[i].copy_(k)
+            self._apply(i)
+        # select is exact by count: floor(sparsity * blocks) are pruned per scope, or as many as were already
+        sizes = [k.numel() for k in self._keep]
+        if self._per_layer():
+            self._live = [min(l, n - int(math.floor(sparsity * n))) for l, n in zip(self._live, sizes)]
+        else:
+            self._live = [min(sum(self._live), sum(sizes) - int(math.floor(sparsity * sum(sizes))))]
+
+    def _per_layer(self):
+        return self.scope == "layer" or len(self.pairs) <= 1
+
+    def probe(self, i):
+        """pair i's probe for vbs_linear(..., probe=...): .sel (uint8, n_blocks) is kept equal to keep == 0 in place by prune, regrow and load_state_dict,
+        .out (float64, n_blocks) takes the scores of the pruned blocks in backward"""
+        return self._probes[i]
+
+    def regrow(self, fraction):
+        """One swap of dynamic sparse training.  Per scope n_swap = floor(fraction * live blocks) (counted on the host: prune is exact by count and a swap
+        keeps the count); select_swap on scores() and the probes' .out -- divided by the block's elements inside the matrix when normalize, -inf for a
+        block without any -- updates the masks in place.  Then per pair what prune does: the dropped blocks become +0.0 in values, values.grad and the
+        optimizer's state (the grown ones are +0.0 everywhere already: that is what prune maintains), the handle gets the values, its live set and the live
+        switches, and the probe's .sel follows.  Launches and torch device operations only.  The probes must hold the scores of a backward that ran with
+        the current masks."""
+        import torch
+        if not 0.0 <= fraction <= 1.0:
+            raise ValueError("fraction must lie in [0, 1]")
+        grad = []
+        for p, n_in in zip(self._probes, self._n_in):
+            g = p.out / n_in if self.normalize else p.out
+            grad.append(torch.where(n_in > 0, g, torch.full_like(g, float("-inf"))))
+        if self._per_layer():
+            new = select_swap(self.scores(), grad, self._keep, [int(math.floor(fraction * l)) for l in self._live], "layer")
+        else:
+            new = select_swap(self.scores(), grad, self._keep, int(math.floor(fraction * self._live[0])), "global")
         for i, k in enumerate(new):
             self._keep[i].copy_(k)
             self._apply(i)
@@ -157,3 +262,5 @@ class BlockPruner:
         for i, src in enumerate(sd["keep"]):
             self._keep[i].copy_((src != 0).to(torch.uint8))
             self._apply(i)
+        live = [int((src != 0).sum().item()) for src in sd["keep"]]                    # (synchronises if the masks are device tensors)
+        self._live = live if self._per_layer() else [sum(live)]
