@@ -762,6 +762,41 @@ int sparta_vbs_live_forward_lists_get(sparta_vbs_t* A, void* steps_plain, int32_
                                       void* stream);
 int sparta_live_forward_compact(const void* steps, int64_t n_steps, const int32_t* ranges, int64_t n_ranges, int32_t pair_image, const uint8_t* live /* [n_steps][2] */,
                                 void* steps_out, int32_t* ranges_out, int64_t* info_out /* [8] */);
+/* THE FP8 WEIGHT IMAGE (sparta_vbs_set_forward_a8): with the switch on, sparta_vbs_spmm on a 16-bit handle multiplies with an OCP e4m3 image of A -- one byte
+ * per stored element and one power-of-two scale per group -- widened to the handle's 16-bit type in registers (v_cvt_scalef32_pk_{f16,bf16}_fp8), right in
+ * front of the MFMAs the plain kernel issues.  Plans, records, B, accumulation order and epilogue are those of the plain product.  Everything else -- spmm_t,
+ * sddmm, block_ssq, the live set, the steps -- keeps reading the 16-bit image: a forward under the switch with a backward on the 16-bit image of the same
+ * values is quantisation-aware training, straight-through.  Opt-in, off at creation; with the switch off launches and results are what they were.
+ * THE RULE.  A GROUP is one half of one slice of the stream image: the <= 32 rows x KP (32 or 64) values of a stored block that one step multiplies.  Every
+ * stored element lies in exactly one group; image positions no stored element maps to hold code 0 and belong to no group.  For a group with fp32 values v:
+ *   amax = the largest |v| over the FINITE elements (0 for a group of zeros or of nothing finite);
+ *   e    = 0 if amax == 0; else with amax = m * 2^x, m in [0.5, 1): e = x - 9 if m <= 0.875, else x - 8 -- the smallest e with amax * 2^-e <= 448 -- clamped
+ *          to [-126, 127] (no finite fp32 reaches the upper clamp); the scale is the fp32 2^e;
+ *   code = v * 2^-e (one fp32 multiplication, exact) rounded to nearest even to e4m3fn: subnormals and the sign of zero kept, nothing exceeds 448 by
+ *          construction; NaN and +-Inf become the NaN code with their sign (0x7F / 0xFF) -- e4m3fn has no Inf, AN Inf WEIGHT BECOMES NaN UNDER THE SWITCH;
+ *   the value the product multiplies = code x 2^e in the handle's type as the conversion instruction gives it: exact whenever representable -- bf16 always,
+ *          outside bf16 subnormals; f16 for -15 <= e <= 7 -- and the instruction's rounding otherwise.
+ * The rounding is integer code on both sides; sparta_a8_quantize_group is the rule on the host for one group: v[k * ld + r] = row r < rows <= 32 of column
+ * k < kcols (32 or 64), codes[k * rows + r], *e_out = e.  It needs no device.
+ * sparta_vbs_set_forward_a8: the handle must be 16-bit, made with SPARTA_CREATE_UPDATABLE, and hold every stored element exactly once in ONE stream image (no
+ * hub plan, no second image, a block width that is a multiple of 32: the handles that take the live forward form); every other handle -- fp32, not updatable,
+ * made by sparta_vbs_create_from_csr / sparta_vbs_create_transposed -- gets SPARTA_ERR_UNSUPPORTED: the switch is never accepted and ignored.  Live forward
+ * and the fp8 image do not combine: enabling one while the other is on is SPARTA_ERR_UNSUPPORTED.  The FIRST enabling call allocates the image (half the bytes
+ * of the 16-bit image) and a private copy of the image's step records (32 bytes per step; the group exponents live in their last word) and is refused while
+ * the stream is being captured; later calls are host state.  The image is INVALID until the next write of values: while the switch is on
+ * sparta_vbs_set_values, sparta_vbs_sgd_step and sparta_vbs_adam_step (fused and two-pass forms, with and without a control record; a skipped step too) each
+ * append ONE launch of the quantise kernel on the W / mab they were given, in stream order -- no allocation, capturable, a replay requantises -- so a valid
+ * image is always the rule applied to the current values.  With a valid image sparta_vbs_spmm takes the a8 kernels (any n_cols, either layout of C); with an
+ * invalid one, a gathered B, SPARTA_H16_AHEAD=7 or SPARTA_H16_PATH=lds it takes the plain kernels on the 16-bit image.  Switching off invalidates the image.
+ * sparta_vbs_a8_info: info_out[8] = {the switch, the image is valid, which stream image has the form (0: none, 1: the <= 32-row tiles, 2: the 64-row / pair
+ * tiles), the form the last 16-bit product ran on the image of <= 32-row tiles and on the image of 64-row / pair tiles (0: none yet, 1: plain, 2: live,
+ * 3: a8), groups (one per 32-row slice, two per 64-row slice), bytes of the fp8 image (0 before the first enabling call), quantise launches so far}.
+ * sparta_vbs_a8_get: host pointers to nztot elements each in mab order, any may be NULL -- the code of every stored element, its group's exponent, its group's
+ * number (pattern only).  Synchronises the stream, refused under capture, SPARTA_ERR_UNSUPPORTED before the first enabling call; for tests and records. */
+int sparta_vbs_set_forward_a8(sparta_vbs_t* A, int32_t enable, void* stream);
+int sparta_vbs_a8_info(sparta_vbs_t* A, int64_t* info_out /* [8] */, void* stream);
+int sparta_vbs_a8_get(sparta_vbs_t* A, uint8_t* codes, int32_t* exps, int32_t* group, void* stream);
+int sparta_a8_quantize_group(const float* v, int64_t ld, int32_t rows, int32_t kcols, uint8_t* codes, int32_t* e_out);
 int sparta_vbs_live_info(sparta_vbs_t* A, int64_t* info_out /* [8] */, void* stream);
 int sparta_vbs_live_lists_get(sparta_vbs_t* A, int32_t* sd_groups, int32_t* sd_count, int32_t* t_blocks, int32_t* t_count, void* stream);
 int sparta_vbs_live_lists_host(int64_t cols, int64_t block_rows, int64_t block_col_size, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab,

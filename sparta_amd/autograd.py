@@ -146,6 +146,8 @@ def vbs_linear(x, handle, values, refresh=False, *, bias=None, activation="none"
     handles round grad_y to their type first and need even rows and cols (their operands are read with an even leading dimension).  `values` is
     saved for backward: changing it in place between forward and backward raises torch's RuntimeError, as for any saved tensor; if the handle
     took other values in between (a second forward with another tensor, a set_values), backward first writes the saved ones back.
+    On a handle with DeviceVBS.set_forward_a8 on, forward multiplies with the fp8 (e4m3) weights.  Backward uses the 16-bit image of the same values
+    (straight-through).
 
     bias: a contiguous float32 (rows,) tensor on the handle's device, in the VBS's REORDERED row order like y (bias[i] belongs to column i of y), or None.
     activation: "none" | "relu" | "gelu" (the erf form, torch's default).  out_dtype: torch.float32 (the default) | float16 | bfloat16 -- what the next layer

@@ -5,6 +5,15 @@
 //   * a step's slice of A is addressed by its own record (compaction leaves gaps between the slices a worker walks), not by one running offset;
 //   * the absent flags mean DEAD: on one-tile records STEP_LO_ABSENT marks the whole step (zero-record descriptors for A and B, B fragments ANDed with 0),
 //     on pair tiles a step with both flags set fetches no B either.
+// k_h16_a8.hip compiles the body a third time: H16_DIRECT_KERNEL = vbs_fwda8_h16_kernel, H16_DIRECT_A8 = 1 (the a8 form of sparta_vbs_set_forward_a8, DESIGN.md
+// section 3.17).  p.A is then the e4m3 image -- the slices in the same order and chunk order, ONE byte per element, so an element offset is a byte offset -- and
+// p.steps the handle's private copy of the records, whose last word (the shard index of gathered lists: unread here) holds the biased exponents of the slice's
+// two groups, rows 0..31 in bits 0..15 and rows 32..63 in bits 16..31.  The a8 form differs in how a step gets its A fragments and nowhere else: 8-byte loads
+// into half as many registers, two scalar shifts for the scales, and four v_cvt_scalef32_pk_{f16,bf16}_fp8 per fragment right in front of its MFMAs.  All of it
+// sits behind `if constexpr (A8)` or a constant-folded A8 term.
+#ifndef H16_DIRECT_A8
+#define H16_DIRECT_A8 0
+#endif
 #ifndef SPARTA_H16_ACCA
 #define SPARTA_H16_ACCA 1     // four-accumulator kernels: accumulators pinned to AGPRs (inline-assembly MFMA)
 #endif
@@ -30,9 +39,32 @@
 // B fragments are used twice.  One workgroup per CU (the 16-bit plans' own choice): the accumulators live in the upper half of the 512-register file.
 // Split tiles are allowed: a wave writes its 64 x 64 piece into the slot images of the two 128-column slabs its workgroup covers, in the layout the
 // fix-up kernel reads (four waves x 32 columns).
+// a chunk of A as the image holds it (16 bytes of 16-bit values / 8 bytes of e4m3 codes) and as the MFMA takes it
+template <bool A8>
+__device__ __forceinline__ std::conditional_t<A8, u32x2, u32x4> h16_load_chunk(const __amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
+    if constexpr (A8) return __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
+    else return __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
+}
+template <bool BF16>
+__device__ __forceinline__ u32x4 h16_widen(const u32x4& c, float) { return c; }
+template <bool BF16>
+__device__ __forceinline__ u32x4 h16_widen(const u32x2& c, float sc) {        // code x scale, two values per instruction (word_sel: the low / high pair of a dword)
+    if constexpr (BF16) return u32x4{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[0], sc, false)),
+                                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[0], sc, true)),
+                                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[1], sc, false)),
+                                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[1], sc, true))};
+    else return u32x4{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[0], sc, false)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[0], sc, true)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[1], sc, false)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[1], sc, true))};
+}
+
 template <int KP, bool MI2, bool BF16, bool GATHERED, bool CSTAGE = false, bool DEEP = false, bool TAIL = true, int WC = 32, bool SLAB = false>
 __global__ __launch_bounds__(kThreads, (MI2 && WC == 64) ? 1 : 2) void H16_DIRECT_KERNEL(const StreamParams p) {
     constexpr bool LIVE = H16_DIRECT_LIVE != 0;
+    constexpr bool A8 = H16_DIRECT_A8 != 0;
+    static_assert(!A8 || (!LIVE && !GATHERED && !DEEP && !(MI2 && WC == 64)), "the a8 form: plain records, B not gathered, three steps ahead, no four-accumulator form");
+    constexpr int ACH = A8 ? 8 : 16;                     // bytes of one chunk (8 consecutive k of one row) in the image of A
     static_assert(!SLAB || WC == 64, "256-column slabs are four 64-column waves");
     static_assert(!(CSTAGE && MI2), "the C ring holds 64 rows: tiles of <= 32 rows only");
     static_assert(WC == 32 || (WC == 64 && !CSTAGE && !DEEP && (!MI2 || SLAB)), "64-column waves: without ring, three steps ahead; two-tile form as 256-column slabs only");
@@ -82,7 +114,7 @@ __global__ __launch_bounds__(kThreads, (MI2 && WC == 64) ? 1 : 2) void H16_DIREC
     const uint32_t voffBt = (uint32_t)(((n0 + WC * wv + bc) * ld_t + bk) * 2);
     const uint32_t qstepB = (uint32_t)(CPI * p.ldb * 2), qstepBt = (uint32_t)(CPI * ld_t * 2);      // bytes from one column group to the next
     const uint32_t gstepB = (uint32_t)(32 * p.ldb * 2), gstepBt = (uint32_t)(32 * ld_t * 2);        // ... from one group of 32 columns to the next (WC = 64)
-    const uint32_t voffA = (uint32_t)((g * TM + lm) * 16);     // slice in memory: [k chunk = 2 q + g][row][8]: a wave load is one (TM = 32) or two contiguous pieces
+    const uint32_t voffA = (uint32_t)((g * TM + lm) * ACH);     // slice in memory: [k chunk = 2 q + g][row][8]: a wave load is one (TM = 32) or two contiguous pieces
     const int64_t n0off = (int64_t)nw * p.ldb;
     const uint32_t voffC = p.c_row_major ? (uint32_t)((lm * p.ldc + 4 * g) * 4) : (uint32_t)((lm + (4 * g) * p.ldc) * 4);
     char* const ldsw = lds + wave * (2 * NG * WSTAGE);   // this wave's two stages (NG images of 32 columns each)
@@ -92,13 +124,21 @@ __global__ __launch_bounds__(kThreads, (MI2 && WC == 64) ? 1 : 2) void H16_DIREC
     CRing cr;                                            // CSTAGE: finished tiles wait here for whole aligned blocks of 32 rows (vbs_kernel_common.hpp)
     cr.ring = reinterpret_cast<float*>(lds + 4 * 2 * NG * WSTAGE) + wave * kCRingFloats;
 
-    struct ASet { u32x4 a[NA][NK]; };
+    using afrag_t = std::conditional_t<A8, u32x2, u32x4>;  // a chunk as loaded: 8 codes or 8 16-bit values
+    struct ASet { afrag_t a[NA][NK]; };
     struct BSet { u32x4 b[NG * NK]; };
     ASet as0, as1, as2, as3;                             // A fragments of the steps i mod 4
     BSet bs0, bs1;                                       // B staging (steps of even / odd index)
 
     // the slices of A are laid out in step order: one running offset, taken from the first record of the range
     // (live form: every step's offset comes from its own record, see issue_loads)
+    auto a_slice = [&](int64_t off) __attribute__((always_inline)) -> void* {
+        if constexpr (A8) return const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(p.A) + off);
+        else return const_cast<uint16_t*>(A16 + off);
+    };
+    auto load_a = [&](const __amdgpu_buffer_rsrc_t r, uint32_t chunk) __attribute__((always_inline)) -> afrag_t {
+        return h16_load_chunk<A8>(r, voffA, chunk * (uint32_t)ACH);
+    };
     int64_t g_aoff = LIVE ? (int64_t)0 : ((int64_t)(uint32_t)field(0, F_AOFF_LO) | ((int64_t)field(0, F_AOFF_HI) << 32)) - (int64_t)TM * KP;
     uint32_t vo_cur = voffB;
     int32_t tail_prev = 0;
@@ -129,13 +169,13 @@ __global__ __launch_bounds__(kThreads, (MI2 && WC == 64) ? 1 : 2) void H16_DIREC
         }
         // (pair tiles, vbs_plan.cpp: a half of the slice whose block-row has no block in this column is zeros -- a descriptor of zero records returns them without a fetch;
         // the step then clears the B fragments of that half as well, see `half` below)
-        const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(A16 + g_aoff), 0, ((MI2 || LIVE) && (flags & STEP_LO_ABSENT)) ? 0 : 0x7ffffff0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rA1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(A16 + g_aoff), 0, (MI2 && (flags & STEP_HI_ABSENT)) ? 0 : 0x7ffffff0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(a_slice(g_aoff), 0, ((MI2 || LIVE) && (flags & STEP_LO_ABSENT)) ? 0 : 0x7ffffff0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rA1 = __builtin_amdgcn_make_buffer_rsrc(a_slice(g_aoff), 0, (MI2 && (flags & STEP_HI_ABSENT)) ? 0 : 0x7ffffff0, 0x00020000);
         if (!(SPARTA_H16_PROBE & 2) && !((SPARTA_H16_PROBE & 16) && wave != 0) && !((SPARTA_H16_PROBE & 32) && (wave & 1))) {   // 16: only wave 0 loads A; 32: waves 0 and 2
 #pragma unroll
             for (int mi = 0; mi < NA; mi++)
 #pragma unroll
-                for (int q = 0; q < NK; q++) ra.a[mi][q] = __builtin_amdgcn_raw_buffer_load_b128(mi == 0 ? rA : rA1, voffA, (uint32_t)((2 * q * TM + 32 * mi) * 16), 0);
+                for (int q = 0; q < NK; q++) ra.a[mi][q] = load_a(mi == 0 ? rA : rA1, (uint32_t)(2 * q * TM + 32 * mi));
         }
         return flags;
     };
@@ -197,12 +237,22 @@ __global__ __launch_bounds__(kThreads, (MI2 && WC == 64) ? 1 : 2) void H16_DIREC
             const uint32_t m = mi == 0 ? m_lo : m_hi;
             return u32x4{f[0] & m, f[1] & m, f[2] & m, f[3] & m};
         };
+        // a8 form: the scales of the slice's two groups, 2^e as fp32 bits from the biased exponents in the record (wave-uniform: scalar shifts), and a chunk's 8
+        // codes widened to the 16-bit fragment the MFMA takes -- code x scale in one instruction per pair
+        float sc_lo = 0.0f, sc_hi = 0.0f;
+        if constexpr (A8) {
+            const uint32_t ew = (uint32_t)field(i, F_SHARD);
+            sc_lo = __uint_as_float((ew & 0xffffu) << 23);
+            sc_hi = __uint_as_float((ew >> 16) << 23);
+        }
+        auto afrag = [&](const afrag_t& c, int mi) __attribute__((always_inline)) -> u32x4 { return h16_widen<BF16>(c, mi == 0 ? sc_lo : sc_hi); };
         if constexpr (!ILV) {
 #pragma unroll
             for (int q = 0; q < NK; q++) {
-                mfma(half(fb[q], 0), wa.a[0][q], acc0);
-                if constexpr (MI2) mfma(half(fb[q], 1), wa.a[1][q], acc1);
-                if constexpr (WC == 64 && !MI2) mfma(half(fb[NK + q], 0), wa.a[0][q], acc1);   // the wave's second 32 columns (acc1: free in the one-tile kernel)
+                const u32x4 a_lo = afrag(wa.a[0][q], 0);
+                mfma(half(fb[q], 0), a_lo, acc0);
+                if constexpr (MI2) mfma(half(fb[q], 1), afrag(wa.a[1][q], 1), acc1);
+                if constexpr (WC == 64 && !MI2) mfma(half(fb[NK + q], 0), a_lo, acc1);   // the wave's second 32 columns (acc1: free in the one-tile kernel)
                 if constexpr (QUAD) { mfma(half(fb[NK + q], 0), wa.a[0][q], acc2); mfma(half(fb[NK + q], 1), wa.a[1][q], acc3); }
             }
             fq_new = issue_loads(std::integral_constant<int, i + D>{}, nb, na);   // G(i + D)
@@ -221,14 +271,14 @@ __global__ __launch_bounds__(kThreads, (MI2 && WC == 64) ? 1 : 2) void H16_DIREC
             const uint16_t* bptr = B16 + (GATHERED ? (int64_t)field(i + D, F_SHARD) * p.shard_stride : (int64_t)0) + gk0 + n0off;
             const bool dead_all_n = LIVE && (flags_n & (STEP_LO_ABSENT | STEP_HI_ABSENT)) == (STEP_LO_ABSENT | STEP_HI_ABSENT);
             const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(bptr), 0, dead_all_n ? 0 : 0x7ffffff0, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(A16 + g_aoff), 0, (flags_n & STEP_LO_ABSENT) ? 0 : 0x7ffffff0, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rA1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(A16 + g_aoff), 0, (flags_n & STEP_HI_ABSENT) ? 0 : 0x7ffffff0, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(a_slice(g_aoff), 0, (flags_n & STEP_LO_ABSENT) ? 0 : 0x7ffffff0, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rA1 = __builtin_amdgcn_make_buffer_rsrc(a_slice(g_aoff), 0, (flags_n & STEP_HI_ABSENT) ? 0 : 0x7ffffff0, 0x00020000);
             __builtin_amdgcn_sched_barrier(0);
             static_for<0, NM>([&](auto t_tag) __attribute__((always_inline)) {
                 constexpr int t = decltype(t_tag)::value;
                 constexpr int q = t / (NA * NG), c = (t / NA) % NG, mi = t % NA;       // k group, column group, row half
                 f32x16& acc = (c == 0) ? (mi == 0 ? acc0 : acc1) : (mi == 0 ? acc2 : acc3);
-                mfma(half(fb[c * NK + q], mi), wa.a[mi][q], acc);
+                mfma(half(fb[c * NK + q], mi), afrag(wa.a[mi][q], mi), acc);
                 __builtin_amdgcn_sched_barrier(0);
                 // what goes behind MFMA t: first the NW writes of W(i + 1), then the loads of step i + D spread over the remaining MFMAs
                 constexpr int slots = NM;
@@ -243,7 +293,7 @@ __global__ __launch_bounds__(kThreads, (MI2 && WC == 64) ? 1 : 2) void H16_DIREC
 #pragma unroll
                     for (int x = lb0; x < lb1; x++) nb.b[x] = __builtin_amdgcn_raw_buffer_load_b128(rB, vo_cur, gstepB * (x / NK) + qstepB * (x % NK), 0);
 #pragma unroll
-                    for (int x = la0; x < la1; x++) na.a[x / NK][x % NK] = __builtin_amdgcn_raw_buffer_load_b128((x / NK) == 0 ? rA : rA1, voffA, (uint32_t)((2 * (x % NK) * TM + 32 * (x / NK)) * 16), 0);
+                    for (int x = la0; x < la1; x++) na.a[x / NK][x % NK] = load_a((x / NK) == 0 ? rA : rA1, (uint32_t)(2 * (x % NK) * TM + 32 * (x / NK)));
                 }
                 __builtin_amdgcn_sched_barrier(0);
             });

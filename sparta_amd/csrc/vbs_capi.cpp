@@ -148,6 +148,8 @@ void destroy_impl(sparta_vbs* v) {
     if (v->d_fwd_steps) (void)hipFree(v->d_fwd_steps);
     if (v->d_fwd_wrange) (void)hipFree(v->d_fwd_wrange);
     if (v->d_fwd_seg_last) (void)hipFree(v->d_fwd_seg_last);
+    if (v->d_a8) (void)hipFree(v->d_a8);
+    if (v->d_a8_steps) (void)hipFree(v->d_a8_steps);
     if (v->d_t_items) (void)hipFree(v->d_t_items);
     if (v->d_t_blocks) (void)hipFree(v->d_t_blocks);
     if (v->d_t_A) (void)hipFree(v->d_t_A);
@@ -1768,6 +1770,9 @@ int spmm16_core(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
         // live forward (sparta_vbs_set_live_forward): with a live set installed and the switch on, the stream image that has compacted records is walked by
         // the live kernels (k_h16_live.hip) on them; read here, when the product is called or captured.  Not for a gathered B.
         const bool fwd_live = A->live_on && A->live_fwd && A->live_fwd_built && A->live_fwd_ty >= 0 && shard_rows == 0;
+        // the fp8 weight image (sparta_vbs_set_forward_a8): with the switch on and a valid image, the stream image that has one is multiplied by the a8 kernels
+        // (k_h16_a8.hip) from the codes, on the handle's private records.  Not for a gathered B; never together with live forward (the switches exclude each other).
+        const bool fwd_a8 = A->a8_on && A->a8_valid && A->a8_built && A->a8_ty >= 0 && shard_rows == 0;
         for (int ty = 1; ty >= 0; ty--) {
             if (A->n_steps[ty] == 0) continue;
             sp.steps = shard_rows > 0 ? A->d_steps_g[ty] : A->d_steps[ty]; sp.worker_range = A->d_wrange[ty]; sp.c_nt = c_store_nt(A, ty, sp.C, sp.ldc, sp.c_row_major != 0);
@@ -1777,20 +1782,27 @@ int spmm16_core(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
             const int cst = [] { const char* e = std::getenv("SPARTA_CSTAGE"); return e ? atoi(e) : -1; }();
             const bool c_stage = ty == 0 && !gth && c_layout == SPARTA_COL_MAJOR && (cst >= 0 ? cst != 0 : ring_tiles(A)) && h16_uses_direct_kernel(A->kp16, false);
             if (c_stage) sp.c_nt = c_store_nt(A, ty, sp.C, sp.ldc, false, true);
+            // (the a8 kernels exist where the live ones do, in their 128-column forms: a call that takes them takes neither the 256-column slab nor the four accumulators)
+            const bool a8_form = fwd_a8 && ty == A->a8_ty && h16_live_form_available(A->kp16, ty != 0, c_stage && !(ty == 0 && A->wide16), ty == 0 && A->wide16);
             // 256-column slabs for the one-tile plan of 32-wide blocks (A read once per 256 columns; flagship matrix, N = 256: 42.2 -> 35.7 us, N = 512: 88.0 -> 77.0):
             // N % 256 == 0, no split tile, not through the ring, the plain plan (on the plan with two sub-worker ranges per workgroup a workgroup walks its tiles in
             // two ascending passes and the gain is gone: 41.1 us; allowed there with SPARTA_H16_SLAB256=2).  SPARTA_H16_SLAB256=0: off.
             const bool slab256 = ty == 0 && A->kp16 == 32 && !gth && !c_stage && A->n_split == 0 && n_cols % 256 == 0 && h16_uses_direct_kernel(32, false) && ldb16 * 64 * 2 < ((int64_t)1 << 31) - 65536 &&
                                  [&] { const char* e = std::getenv("SPARTA_H16_SLAB256"); const int m = e ? atoi(e) : 1; return m == 2 || (m == 1 && !A->wide16); }() &&
-                                 !(fwd_live && ty == A->live_fwd_ty && A->wide16);      // (live ranges of two sub-workers are not adjacent: the non-slab kernel there)
+                                 !(fwd_live && ty == A->live_fwd_ty && A->wide16) &&    // (live ranges of two sub-workers are not adjacent: the non-slab kernel there)
+                                 !a8_form;
             // 64-row tiles of 64-wide blocks (the dense hub of a power-law matrix under the fixed 64 x 64 grid), N % 256 == 0: four accumulators per wave over
             // 256-column slabs -- A read once per 256 columns, every B fragment used twice (k_h16.hip, QUAD); split tiles allowed.  SPARTA_H16_QUAD=0: off.
             const bool quad = ty == 1 && n_cols % 256 == 0 && h16_uses_direct_kernel(A->kp16, true) && ldb16 * 64 * 2 < ((int64_t)1 << 31) - 65536 &&
-                              [] { const char* e = std::getenv("SPARTA_H16_QUAD"); return !e || atoi(e) != 0; }();
+                              [] { const char* e = std::getenv("SPARTA_H16_QUAD"); return !e || atoi(e) != 0; }() && !a8_form;
             const bool wide = ty == 0 && A->wide16;
             const bool live_form = fwd_live && ty == A->live_fwd_ty && (quad || slab256 || h16_live_form_available(A->kp16, ty != 0, c_stage && !wide, wide));
-            A->fwd_last_form[ty] = live_form ? 2 : 1;
-            if (live_form) {
+            A->fwd_last_form[ty] = a8_form ? 3 : live_form ? 2 : 1;
+            if (a8_form) {
+                sp.A = reinterpret_cast<const float*>(A->d_a8); sp.steps = A->d_a8_steps; sp.sub_ranges = 0;
+                launch_h16_a8_stream(A->kp16, ty != 0, bf16, c_stage, wide, grid, st, sp);
+                sp.A = A->d_A;
+            } else if (live_form) {
                 sp.steps = A->d_fwd_steps; sp.worker_range = A->d_fwd_wrange; sp.sub_ranges = 0;
                 if (quad) launch_h16_live_quad(A->kp16, bf16, dim3((unsigned)A->n_workers, (unsigned)(n_cols / 256)), st, sp);
                 else if (slab256) launch_h16_live_slab256(bf16, dim3((unsigned)A->n_workers, (unsigned)(n_cols / 256)), st, sp);
@@ -2422,6 +2434,16 @@ namespace {
 
 // every device image of an updatable handle written from `src` (nztot floats in the mab layout, device memory): the launches of sparta_vbs_set_values, which
 // sparta_vbs_sgd_step repeats behind its elementwise kernel.  Returns the number of launches.
+// the fp8 image behind a write of values (sparta_vbs_set_forward_a8): while the switch is on, one launch of the quantise kernel on the array the images were
+// just written from, in stream order.  Launches only: capturable, and a replay requantises.
+void a8_requantize(sparta_vbs_t* A, hipStream_t st, const float* src) {
+    if (!A->a8_on || !A->a8_built || A->a8_ty < 0 || A->nztot <= 0) return;
+    const int ty = A->a8_ty;
+    launch_a8_quantize(ty ? 64 : 32, A->kp16, st, A->d_upd_map[ty], A->n_steps[ty], src, A->d_a8 + A->upd_base[ty], A->d_a8_steps);
+    A->a8_valid = true;
+    A->a8_launches++;
+}
+
 int launch_images_from(sparta_vbs_t* A, hipStream_t st, const float* src) {
     int launches = 0;
     if (A->dtype == SPARTA_F32) {
@@ -2466,6 +2488,7 @@ int set_values_impl(sparta_vbs_t* A, const float* mab, int32_t ptr_space, void* 
     if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
     if (A->nztot > 0) {
         (void)launch_images_from(A, st, src);
+        a8_requantize(A, st, src);
         HIP_TRY(hipGetLastError());
     }
     if (dt_ms) {
@@ -2555,6 +2578,7 @@ int sgd_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G, 
             else launch_sgd_step(st, A->nztot, W, G, M, c, ctl);
             launches = 1 + launch_images_from(A, st, W);
         }
+        a8_requantize(A, st, W);                  // (a step the control record skipped left W as it was: the image comes out as it stood)
         HIP_TRY(hipGetLastError());
     }
     A->step_last_live = live ? 1 : 0;
@@ -2644,6 +2668,7 @@ int adam_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G,
             else launch_adam_step(st, A->nztot, a);
             launches += 1 + launch_images_from(A, st, W);
         }
+        a8_requantize(A, st, W);                  // (as in sgd_step_impl)
         HIP_TRY(hipGetLastError());
     }
     A->step_last_live = live ? 1 : 0;
@@ -3271,6 +3296,8 @@ extern "C" int sparta_vbs_set_live_forward(sparta_vbs_t* A, int32_t enable, void
         A->live_fwd = false;
         return SPARTA_OK;
     }
+    if (A->a8_on)
+        return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the fp8 weight image is on (sparta_vbs_set_forward_a8) and the two do not combine -- switch it off first");
     DeviceGuard guard(A->device);
     if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
@@ -3342,6 +3369,150 @@ extern "C" int sparta_vbs_live_forward_lists_get(sparta_vbs_t* A, void* steps_pl
     }
     return SPARTA_OK;
     SPARTA_GUARD_END("sparta_vbs_live_forward_lists_get")
+}
+
+// ---- sparta_vbs_set_forward_a8: the fp8 (e4m3) weight image of a 16-bit handle (k_h16_a8.hip) ---------------------------------------------------
+namespace {
+
+// the image and the private records: a 16-bit updatable handle whose one stream image holds every stored element exactly once (what live forward asks), with
+// slice s of the image behind step s of the records (the quantise kernel writes the exponents of slice s into record s)
+int ensure_a8_arrays(sparta_vbs_t* A, const char* entry) {
+    using sparta::fail;
+    if (A->a8_built) return SPARTA_OK;
+    if (g_capturing) return capture_refusal("allocate the fp8 image", entry);
+    const int ty = live_forward_image(A);
+    if (ty < 0)
+        return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": needs a 16-bit handle made with SPARTA_CREATE_UPDATABLE whose one stream image holds every stored "
+                                                                 "element (no hub plan, no second image, a block width that is a multiple of 32)");
+    const std::vector<StepRec>& hs = A->h_steps[ty];
+    const int64_t n = A->n_steps[ty], slice = (int64_t)(ty ? 64 : 32) * A->kp16;
+    if ((int64_t)hs.size() < n) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": the handle keeps no host copy of its step records");
+    for (int64_t q = 0; q < n; q++)
+        if (hs[(size_t)q].a_off != A->upd_base[ty] + q * slice)
+            return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the slices of the stream image are not in step order");
+    A->a8_bytes = A->a_bytes / (int64_t)sizeof(uint16_t);      // one byte per element of the 16-bit image, its padding included
+    HIP_TRY(hipMalloc((void**)&A->d_a8, (size_t)A->a8_bytes));
+    HIP_TRY(hipMemset(A->d_a8, 0, (size_t)A->a8_bytes));
+    HIP_TRY(hipMalloc((void**)&A->d_a8_steps, hs.size() * sizeof(StepRec)));
+    HIP_TRY(hipMemcpy(A->d_a8_steps, hs.data(), hs.size() * sizeof(StepRec), hipMemcpyHostToDevice));
+    A->a8_n_groups = n * (ty ? 2 : 1);
+    A->a8_ty = ty;
+    A->a8_built = true;
+    return SPARTA_OK;
+}
+
+}  // namespace
+
+extern "C" int sparta_vbs_set_forward_a8(sparta_vbs_t* A, int32_t enable, void* stream) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* entry = "sparta_vbs_set_forward_a8";
+    if (!A) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": NULL handle");
+    if (!enable) {                               // host state only; the image goes stale from here on
+        A->a8_on = false;
+        A->a8_valid = false;
+        return SPARTA_OK;
+    }
+    if (A->ext_sparse || A->dtype == SPARTA_F32 || !(A->create_flags & SPARTA_CREATE_UPDATABLE))
+        return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": needs a 16-bit handle made with SPARTA_CREATE_UPDATABLE (sparta_vbs_create_range_ex)");
+    if (A->live_fwd)
+        return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": live forward is on (sparta_vbs_set_live_forward) and the two do not combine -- switch it off first");
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, true);
+    if (int rc = ensure_a8_arrays(A, entry)) return rc;
+    if (!A->a8_on) A->a8_valid = false;          // invalid until the next write of values
+    A->a8_on = true;
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_vbs_set_forward_a8")
+}
+
+extern "C" int sparta_vbs_a8_info(sparta_vbs_t* A, int64_t* info_out, void* stream) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* entry = "sparta_vbs_a8_info";
+    if (!A || !info_out) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": NULL argument");
+    std::memset(info_out, 0, 8 * sizeof(int64_t));
+    const int ty = A->a8_built ? A->a8_ty : ((A->ext_sparse || A->dtype == SPARTA_F32) ? -1 : live_forward_image(A));
+    info_out[0] = A->a8_on ? 1 : 0;
+    info_out[1] = A->a8_on && A->a8_valid ? 1 : 0;
+    info_out[2] = ty + 1;
+    info_out[3] = A->fwd_last_form[0];
+    info_out[4] = A->fwd_last_form[1];
+    info_out[5] = ty >= 0 ? A->n_steps[ty] * (ty ? 2 : 1) : 0;
+    info_out[6] = A->a8_bytes;
+    info_out[7] = A->a8_launches;
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_vbs_a8_info")
+}
+
+extern "C" int sparta_vbs_a8_get(sparta_vbs_t* A, uint8_t* codes, int32_t* exps, int32_t* group, void* stream) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* entry = "sparta_vbs_a8_get";
+    if (!A) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": NULL handle");
+    if (!A->a8_built || A->a8_ty < 0) return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the handle has no fp8 image (sparta_vbs_set_forward_a8 was never on)");
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, true);
+    if (g_capturing) return capture_refusal("read the fp8 image back (synchronises)", entry);
+    HIP_TRY(hipStreamSynchronize(st));
+    const int ty = A->a8_ty, tms = ty ? 64 : 32, kp = A->kp16;
+    const int64_t n = A->n_steps[ty], slice = (int64_t)tms * kp;
+    std::vector<UpdSlice> map((size_t)n);
+    std::vector<StepRec> recs((size_t)n);
+    std::vector<uint8_t> img((size_t)(n * slice));
+    if (n > 0) {
+        HIP_TRY(hipMemcpy(map.data(), A->d_upd_map[ty], map.size() * sizeof(UpdSlice), hipMemcpyDeviceToHost));
+        if (exps) HIP_TRY(hipMemcpy(recs.data(), A->d_a8_steps, recs.size() * sizeof(StepRec), hipMemcpyDeviceToHost));
+        if (codes) HIP_TRY(hipMemcpy(img.data(), A->d_a8 + A->upd_base[ty], img.size(), hipMemcpyDeviceToHost));
+    }
+    for (int64_t s = 0; s < n; s++) {
+        const UpdSlice& u = map[(size_t)s];
+        const uint32_t word = (uint32_t)recs[(size_t)s].pad;
+        for (int rr = 0; rr < tms; rr++) {
+            int64_t at0 = -1, ld = 0;                           // (the rows vbs_a8quant_kernel reads, see k_h16_a8.hip)
+            if (rr < u.rows_lo) { at0 = u.off_lo + rr; ld = u.h_lo; }
+            else if (rr >= 32 && rr - 32 < u.rows_hi) { at0 = u.off_hi + (rr - 32); ld = u.h_hi; }
+            if (at0 < 0) continue;
+            const int hf = rr >> 5;
+            for (int k = 0; k < kp; k++) {
+                const int64_t i = at0 + (int64_t)k * ld;
+                if (i < 0 || i >= A->nztot) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": the slice map points outside the stored elements");
+                if (codes) codes[i] = img[(size_t)(s * slice + ((int64_t)(k / 8) * tms + rr) * 8 + (k & 7))];
+                if (exps) exps[i] = (int32_t)((word >> (16 * hf)) & 0xffffu) - 127;
+                if (group) group[i] = (int32_t)(s * (tms / 32) + hf);
+            }
+        }
+    }
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_vbs_a8_get")
+}
+
+extern "C" int sparta_a8_quantize_group(const float* v, int64_t ld, int32_t rows, int32_t kcols, uint8_t* codes, int32_t* e_out) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* entry = "sparta_a8_quantize_group";
+    if (rows < 0 || rows > 32 || (kcols != 32 && kcols != 64) || ld < rows || !e_out || (rows > 0 && (!v || !codes)))
+        return fail(SPARTA_ERR_INVALID, std::string(entry) + ": rows must lie in 0..32, kcols be 32 or 64, ld >= rows, and no pointer be NULL");
+    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
+    uint32_t amax = 0;
+    for (int32_t k = 0; k < kcols; k++)
+        for (int32_t r = 0; r < rows; r++) amax = a8_amax_bits(amax, bits(v[(int64_t)k * ld + r]));
+    const int32_t e = a8_exponent(amax);
+    const uint32_t inv_bits = a8_inv_scale_bits(e);
+    float inv;
+    std::memcpy(&inv, &inv_bits, 4);
+    for (int32_t k = 0; k < kcols; k++)
+        for (int32_t r = 0; r < rows; r++) {
+            volatile float x = v[(int64_t)k * ld + r] * inv;      // (one fp32 multiplication, as the kernel's)
+            codes[(int64_t)k * rows + r] = (uint8_t)a8_code(bits(x));
+        }
+    *e_out = e;
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_a8_quantize_group")
 }
 
 extern "C" int sparta_live_forward_compact(const void* steps, int64_t n_steps, const int32_t* ranges, int64_t n_ranges, int32_t pair_image, const uint8_t* live,

@@ -5,6 +5,7 @@
 //   k_f32_packed.hip  ... and its packed form (partly empty blocks of a tile share a step)
 //   k_h16.hip         fp16 / bf16 storage: LDS-staged and direct stream kernels, conversions (the direct kernel's body: k_h16_direct.inc)
 //   k_h16_live.hip    the live form of the direct 16-bit kernel: the same body on the compacted records of sparta_vbs_set_live_forward
+//   k_h16_a8.hip      the a8 form of the direct 16-bit kernel (fp8 e4m3 image of A, sparta_vbs_set_forward_a8) and the kernel that quantises the image
 //   k_sparse.hip      sparse-row kernels, layout transposes, row-block pack
 //   k_spmm_t.hip      the transposed product on a handle's own stored blocks (sparta_vbs_spmm_t)
 //   k_update.hip      new values for the images of an updatable handle (sparta_vbs_set_values)
@@ -36,6 +37,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // 4-byte aligned: global_load_dwordx4 on any float address
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kThreads = 256;
 constexpr int kTN = 128;   // columns of C per workgroup
@@ -567,7 +569,15 @@ struct sparta_vbs {
     int32_t* d_fwd_wrange = nullptr;                           // the live ranges, as d_wrange[ty]
     int32_t* d_fwd_seg_last = nullptr;                         // [n_steps[ty]] last record of every step's segment (pattern only)
     int64_t fwd_n_ranges = 0, fwd_n_alloc = 0;
-    int32_t fwd_last_form[2] = {0, 0};                         // per stream image: the form the last 16-bit product ran (0 none yet, 1 plain, 2 live)
+    int32_t fwd_last_form[2] = {0, 0};                         // per stream image: the form the last 16-bit product ran (0 none yet, 1 plain, 2 live, 3 a8)
+    // the fp8 weight image (sparta_vbs_set_forward_a8): the switch is host state.  The first enabling call allocates the e4m3 image of the one stream image (the
+    // slices of d_A in the same order, one byte per element, the same padding behind them) and a private copy of its step records whose last word holds the
+    // biased exponents of the slice's two groups.  vbs_a8quant_kernel rewrites both behind every write of values while the switch is on.
+    bool a8_on = false, a8_built = false, a8_valid = false;
+    int a8_ty = -1;                                            // the stream image that has the a8 form
+    uint8_t* d_a8 = nullptr;                                   // [a8_bytes]
+    sparta_dev::StepRec* d_a8_steps = nullptr;                 // [n_steps[a8_ty] + padding]
+    int64_t a8_bytes = 0, a8_n_groups = 0, a8_launches = 0;
     // block scores of the SDDMM (sparta_vbs_sddmm_block_ssq): a second snapshot / group list / count, written from `sel` by every call (goff is d_live_goff:
     // pattern only), the all-ones selection that stands in for sel == NULL, and the pattern-only slot offsets, finish records and the fp64 slots themselves
     bool score_built = false;
@@ -695,6 +705,10 @@ void launch_h16_live_stream(int kp, bool mi2, bool bf16, bool c_stage, bool wide
 void launch_h16_live_slab256(bool bf16, dim3 grid, hipStream_t st, const StreamParams& sp);
 void launch_h16_live_quad(int kp, bool bf16, dim3 grid, hipStream_t st, const StreamParams& sp);
 bool h16_live_form_available(int kp, bool mi2, bool c_stage, bool wide);
+// k_h16_a8.hip: the a8 form of the same launches on the handle's private records (the 128-column kernels only: a launch that would take the 256-column slab or the
+// four-accumulator form takes the 128-column sibling of its plan), and the kernel that writes the e4m3 image and the exponents from nztot floats in the mab layout
+void launch_h16_a8_stream(int kp, bool mi2, bool bf16, bool c_stage, bool wide, dim3 grid, hipStream_t st, const StreamParams& sp);
+void launch_a8_quantize(int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, const float* mab, uint8_t* dst, StepRec* recs);
 
 // vbs_plan.cpp
 struct StreamPlanIn {

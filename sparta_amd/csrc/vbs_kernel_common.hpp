@@ -55,6 +55,42 @@ inline int32_t f32_pack_blocks(int32_t n_blocks, const uint8_t* masks, int32_t* 
     return (int32_t)used.size();
 }
 
+// ---- the fp8 (e4m3) weight image of 16-bit handles (sparta_vbs_set_forward_a8): ONE rule for vbs_a8quant_kernel (k_h16_a8.hip) and the host -----------
+// (include/sparta_amd.h states it; integer code throughout, so that ties, subnormals and -0 are the same bits on either side)
+// a8_amax_bits: the running maximum of |v| over the FINITE elements of a group, as the bits of a non-negative float (ordered as unsigned integers).
+__host__ __device__ inline uint32_t a8_amax_bits(uint32_t amax, uint32_t v_bits) {
+    const uint32_t a = v_bits & 0x7fffffffu;
+    return (a < 0x7f800000u && a > amax) ? a : amax;
+}
+// the group's exponent e from its amax: the smallest e with amax * 2^-e <= 448, clamped to [-126, 127]; 0 for amax == 0.  amax = m * 2^x with m in [0.5, 1):
+// x = E - 126 for a normal float (m <= 0.875: mantissa field <= 0x600000); a subnormal amax has x <= -126 and clamps to -126.  (No finite fp32 reaches the
+// upper clamp: FLT_MAX gives 120.)
+__host__ __device__ inline int32_t a8_exponent(uint32_t amax) {
+    if (amax == 0u) return 0;
+    const int32_t E = (int32_t)(amax >> 23);
+    if (E == 0) return -126;
+    const int32_t e = E - 126 - ((amax & 0x7fffffu) <= 0x600000u ? 9 : 8);
+    return e < -126 ? -126 : (e > 127 ? 127 : e);
+}
+// 2^-e as fp32 bits (e in [-126, 126]: every e a8_exponent returns)
+__host__ __device__ inline uint32_t a8_inv_scale_bits(int32_t e) { return (uint32_t)(127 - e) << 23; }
+// the OCP e4m3fn code of x = v * 2^-e (its fp32 bits), round to nearest even: subnormals and the sign of zero kept, NaN and +-Inf the NaN code with their sign;
+// |x| <= 448 by the choice of e (anything above would saturate to 448: never taken)
+__host__ __device__ inline uint32_t a8_code(uint32_t x_bits) {
+    const uint32_t sign = (x_bits >> 24) & 0x80u, a = x_bits & 0x7fffffffu;
+    if (a >= 0x7f800000u) return sign | 0x7fu;
+    if (a >= (121u << 23)) {                               // |x| >= 2^-6: normal in e4m3 -- 20 mantissa bits go
+        const uint32_t r = (a + 0x7ffffu + ((a >> 20) & 1u)) >> 20;
+        const uint32_t c = r - (120u << 3);
+        return sign | (c > 0x7eu ? 0x7eu : c);
+    }
+    // |x| < 2^-6: multiples of 2^-9 -- |x| * 512 lies in [0, 8), adding 2^23 rounds it to an integer (to nearest even) in the low mantissa bits
+    union { uint32_t u; float f; } t;
+    t.u = a;
+    t.f = t.f * 512.0f + 8388608.0f;
+    return sign | (t.u & 0xfu);
+}
+
 }  // namespace sparta_dev
 
 #ifdef __HIP__            // what follows is device code: the host translation units stop here

@@ -595,6 +595,41 @@ class DeviceVBS(ValuesRecord):
         out["pair"] = fi["capable"] == 2
         return out
 
+    def set_forward_a8(self, on, values=None, stream=None):
+        """sparta_vbs_set_forward_a8: with on=True the 16-bit forward product multiplies with an fp8 (OCP e4m3) image of the weights -- one byte per element, one
+        power-of-two scale per group of <= 32 rows x 32 / 64 values of a stored block, widened to the handle's 16-bit type in registers -- instead of the 16-bit
+        image.  spmm_t, sddmm, the steps and everything else keep reading the 16-bit image: under vbs_linear that is quantisation-aware training with a
+        straight-through backward.  Needs updatable=True and a 16-bit handle whose one stream image holds every stored element (a8_info()["capable"]); every
+        other handle raises SpartaError (unsupported), as does a handle with live forward on.  The image is invalid (the product keeps the 16-bit weights) until
+        the next set_values / sgd_step / adam_step, each of which requantises behind itself while the switch is on; values=W is the switch followed by
+        set_values(W).  An Inf weight becomes NaN under the switch (e4m3fn has no Inf).  Off by default.  The first enabling call allocates and cannot be
+        captured."""
+        if not on:
+            check(lib.sparta_vbs_set_forward_a8(self.h, 0, None))
+            return
+        check(lib.sparta_vbs_set_forward_a8(self.h, 1, self._live_stream(stream)))
+        self._values_replaced()                                # (the next vbs_linear forward writes its values, and with them the image)
+        if values is not None:
+            self.set_values(values, stream=stream)
+
+    def a8_info(self, stream=None):
+        """sparta_vbs_a8_info: {"switch", "valid" (the image follows the current values), "capable" (the stream image with the a8 form: 0 none, 1 the <= 32-row
+        tiles, 2 the 64-row / pair tiles), "form_one_tile", "form_pair" (what the last 16-bit product ran on each stream image: 0 none yet, 1 the plain
+        kernels, 2 live, 3 a8), "groups", "image_bytes", "quantize_launches"}"""
+        a = np.zeros(8, np.int64)
+        check(lib.sparta_vbs_a8_info(self.h, a.ctypes.data_as(_i64p), self._live_stream(stream)))
+        keys = ["switch", "valid", "capable", "form_one_tile", "form_pair", "groups", "image_bytes", "quantize_launches"]
+        return {k: int(a[i]) for i, k in enumerate(keys)}
+
+    def a8_get(self, stream=None):
+        """sparta_vbs_a8_get (synchronises; for tests and records): (codes uint8, exps int32, group int32), nztot elements each in the layout of VBR.mab -- the
+        e4m3fn code of every stored element, the exponent of its group (its dequantised value is the code times 2^exp) and the number of its group."""
+        n = self._nztot()
+        codes, exps, group = np.zeros(n, np.uint8), np.zeros(n, np.int32), np.full(n, -1, np.int32)      # (an element no group covers would keep its -1)
+        i32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+        check(lib.sparta_vbs_a8_get(self.h, codes.ctypes.data_as(u8p), exps.ctypes.data_as(i32p), group.ctypes.data_as(i32p), self._live_stream(stream)))
+        return codes, exps, group
+
     def _live_stream(self, stream):
         import torch
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream)

@@ -38,6 +38,27 @@ def live_forward_compact(steps, ranges, pair, live):
     return out, r_out, {k: int(info[i]) for i, k in enumerate(keys)}
 
 
+def a8_quantize_group(v, kcols=None):
+    """sparta_a8_quantize_group: the rule of the fp8 weight image (DeviceVBS.set_forward_a8) on one group, as host code, no GPU.  v: float32 [kcols][ld], row r of
+    column k at v[k, r] (a column-major rows x kcols piece of a stored block, leading dimension ld >= rows); a 2-D array means rows = ld = v.shape[1], a pair
+    (array, rows) gives fewer rows than the leading dimension.  kcols: 32 or 64 (default: v.shape[0]).  Returns (codes, e): uint8 [kcols][rows] e4m3fn codes
+    and the group's exponent -- the dequantised value of an element is its code times 2^e."""
+    rows = None
+    if isinstance(v, tuple):
+        v, rows = v
+    v = np.ascontiguousarray(v, np.float32)
+    if v.ndim != 2:
+        raise ValueError("v must be a 2-D array [kcols][ld]")
+    kcols = v.shape[0] if kcols is None else int(kcols)
+    ld = v.shape[1]
+    rows = ld if rows is None else int(rows)
+    if kcols > v.shape[0]:
+        raise ValueError("v holds fewer than kcols columns")
+    codes, e = np.zeros((kcols, rows), np.uint8), np.zeros(1, np.int32)
+    check(lib.sparta_a8_quantize_group(_pf(v) if v.size else None, ld, rows, kcols, codes.ctypes.data_as(C.POINTER(C.c_uint8)) if codes.size else None, _p32(e)))
+    return codes, int(e[0])
+
+
 def _p64(a):
     return a.ctypes.data_as(_i64p)
 
