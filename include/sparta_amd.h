@@ -790,13 +790,37 @@ int sparta_live_forward_compact(const void* steps, int64_t n_steps, const int32_
  * invalid one, a gathered B, SPARTA_H16_AHEAD=7 or SPARTA_H16_PATH=lds it takes the plain kernels on the 16-bit image.  Switching off invalidates the image.
  * sparta_vbs_a8_info: info_out[8] = {the switch, the image is valid, which stream image has the form (0: none, 1: the <= 32-row tiles, 2: the 64-row / pair
  * tiles), the form the last 16-bit product ran on the image of <= 32-row tiles and on the image of 64-row / pair tiles (0: none yet, 1: plain, 2: live,
- * 3: a8), groups (one per 32-row slice, two per 64-row slice), bytes of the fp8 image (0 before the first enabling call), quantise launches so far}.
+ * 3: a8, 4: a8 on the live records, sparta_vbs_set_a8_live), groups (one per 32-row slice, two per 64-row slice), bytes of the fp8 image (0 before the first enabling call), quantise launches so far}.
  * sparta_vbs_a8_get: host pointers to nztot elements each in mab order, any may be NULL -- the code of every stored element, its group's exponent, its group's
  * number (pattern only).  Synchronises the stream, refused under capture, SPARTA_ERR_UNSUPPORTED before the first enabling call; for tests and records. */
 int sparta_vbs_set_forward_a8(sparta_vbs_t* A, int32_t enable, void* stream);
 int sparta_vbs_a8_info(sparta_vbs_t* A, int64_t* info_out /* [8] */, void* stream);
 int sparta_vbs_a8_get(sparta_vbs_t* A, uint8_t* codes, int32_t* exps, int32_t* group, void* stream);
 int sparta_a8_quantize_group(const float* v, int64_t ld, int32_t rows, int32_t kcols, uint8_t* codes, int32_t* e_out);
+/* THE FP8 IMAGE WITH A LIVE-BLOCK SET (sparta_vbs_set_a8_live): a third switch, for the combination the two above refuse.  sparta_vbs_set_live_forward governs
+ * the product on the 16-bit image, sparta_vbs_set_forward_a8 selects the fp8 image, and this switch says that the product on the fp8 image skips dead blocks.
+ * With the fp8 switch on and its image valid, this switch on and a live set installed, sparta_vbs_spmm walks the compacted records and live ranges of live
+ * forward (the rule under sparta_vbs_set_live_forward) on the e4m3 image:
+ *   a dead block contributes nothing to C, whatever W, the codes or the exponents hold for it; neither its codes nor, on its behalf, the rows of B are read;
+ *   rows of C reached only through dead blocks are +0.0 (accumulate: unchanged);
+ *   C equals bit for bit the live forward product of a plain handle with the same live set that was given the dequantised values, and -- the sign of a zero
+ *   aside -- the product under sparta_vbs_set_forward_a8 alone on values whose dead blocks are zero.
+ * Enabling needs the fp8 switch ON: SPARTA_ERR_UNSUPPORTED otherwise (so on every handle sparta_vbs_set_forward_a8 refuses).  The handles are those of the fp8
+ * image, which are those of the live forward form: no new class.  The FIRST enabling call builds what live forward's first call builds, where it does not exist
+ * yet (the word map, the segment ends, the second record and range arrays -- the same arrays), and is refused while the stream is being captured; later calls
+ * are host state plus launches.  If a set is installed the call launches the word kernel, the compaction kernel and the scale-placement kernel, so that the
+ * next product is right.  While the switch is on, ONE launch of the scale-placement kernel follows every compaction (sparta_vbs_set_live_blocks) and every
+ * quantise launch (every write of values): position p of the compacted records then holds, in its last word, the exponents of the slice its a_off names.  No
+ * allocation, no synchronisation, capturable.  The quantise kernel keeps covering every slice, dead ones included: switching off leaves a complete fp8 image.
+ * Off at creation.  sparta_vbs_set_forward_a8(A, 0) clears this switch too.  sparta_vbs_set_live_forward(A, 1) stays refused while the fp8 switch is on,
+ * whatever this switch says.  The product takes the plain kernels on the 16-bit image with an invalid fp8 image, a gathered B, SPARTA_H16_AHEAD=7 or
+ * SPARTA_H16_PATH=lds, and the a8 kernels on every block without a live set; with this switch off launches and results are what they were.  The form fields
+ * of sparta_vbs_a8_info and sparta_vbs_live_forward_info say 4 for this form.
+ * sparta_vbs_a8_live_info: info_out[8] = {the switch, active (fp8 switch on and image valid, this switch on, a live set installed), which stream image has the
+ * form (0: none, 1: the <= 32-row tiles, 2: the 64-row / pair tiles), its steps, kept steps (read back: synchronises the stream and is refused under capture
+ * when a set is installed and the lists exist; else 0), launches of the scale-placement kernel so far, 0, 0}. */
+int sparta_vbs_set_a8_live(sparta_vbs_t* A, int32_t enable, void* stream);
+int sparta_vbs_a8_live_info(sparta_vbs_t* A, int64_t* info_out /* [8] */, void* stream);
 int sparta_vbs_live_info(sparta_vbs_t* A, int64_t* info_out /* [8] */, void* stream);
 int sparta_vbs_live_lists_get(sparta_vbs_t* A, int32_t* sd_groups, int32_t* sd_count, int32_t* t_blocks, int32_t* t_count, void* stream);
 int sparta_vbs_live_lists_host(int64_t cols, int64_t block_rows, int64_t block_col_size, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab,

@@ -57,6 +57,7 @@ SYMBOLS = [
     "sparta_epilogue_fwd", "sparta_epilogue_scratch_bytes", "sparta_epilogue_bwd",
     "sparta_vbs_sddmm_block_ssq",
     "sparta_vbs_set_forward_a8", "sparta_vbs_a8_info", "sparta_vbs_a8_get", "sparta_a8_quantize_group",
+    "sparta_vbs_set_a8_live", "sparta_vbs_a8_live_info",
 ]
 
 
@@ -181,6 +182,8 @@ def _load():
     L.sparta_vbs_live_forward_lists_get.argtypes = [vp, vp, i32p, C.POINTER(C.c_uint8), vp, i32p, vp]
     L.sparta_vbs_set_forward_a8.argtypes = [vp, C.c_int32, vp]
     L.sparta_vbs_a8_info.argtypes = [vp, i64p, vp]
+    L.sparta_vbs_set_a8_live.argtypes = [vp, C.c_int32, vp]
+    L.sparta_vbs_a8_live_info.argtypes = [vp, i64p, vp]
     L.sparta_vbs_a8_get.argtypes = [vp, C.POINTER(C.c_uint8), i32p, i32p, vp]
     L.sparta_a8_quantize_group.argtypes = [C.POINTER(C.c_float), C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), i32p]
     L.sparta_live_forward_compact.argtypes = [vp, C.c_int64, i32p, C.c_int64, C.c_int32, C.POINTER(C.c_uint8), vp, i32p, i64p]

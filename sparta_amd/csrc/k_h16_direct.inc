@@ -11,6 +11,10 @@
 // two groups, rows 0..31 in bits 0..15 and rows 32..63 in bits 16..31.  The a8 form differs in how a step gets its A fragments and nowhere else: 8-byte loads
 // into half as many registers, two scalar shifts for the scales, and four v_cvt_scalef32_pk_{f16,bf16}_fp8 per fragment right in front of its MFMAs.  All of it
 // sits behind `if constexpr (A8)` or a constant-folded A8 term.
+// k_h16_a8_live.hip compiles it a fourth time: H16_DIRECT_KERNEL = vbs_fwdq8lv_h16_kernel, H16_DIRECT_LIVE = 1 and H16_DIRECT_A8 = 1 (sparta_vbs_set_a8_live,
+// DESIGN.md section 3.18).  The two sets of terms compose as they stand: p.steps are the compacted records, a step's offset from its own record is a byte offset
+// into the e4m3 image, a dead half reads codes of 0 (+0.0 under any scale) through the zero-record descriptor, and the scales come from the last word of the
+// compacted record, where vbs_q8lv_scales_kernel keeps them.
 #ifndef H16_DIRECT_A8
 #define H16_DIRECT_A8 0
 #endif
@@ -63,7 +67,7 @@ template <int KP, bool MI2, bool BF16, bool GATHERED, bool CSTAGE = false, bool 
 __global__ __launch_bounds__(kThreads, (MI2 && WC == 64) ? 1 : 2) void H16_DIRECT_KERNEL(const StreamParams p) {
     constexpr bool LIVE = H16_DIRECT_LIVE != 0;
     constexpr bool A8 = H16_DIRECT_A8 != 0;
-    static_assert(!A8 || (!LIVE && !GATHERED && !DEEP && !(MI2 && WC == 64)), "the a8 form: plain records, B not gathered, three steps ahead, no four-accumulator form");
+    static_assert(!A8 || (!GATHERED && !DEEP && !(MI2 && WC == 64)), "the a8 forms: B not gathered, three steps ahead, no four-accumulator form");
     constexpr int ACH = A8 ? 8 : 16;                     // bytes of one chunk (8 consecutive k of one row) in the image of A
     static_assert(!SLAB || WC == 64, "256-column slabs are four 64-column waves");
     static_assert(!(CSTAGE && MI2), "the C ring holds 64 rows: tiles of <= 32 rows only");

@@ -1797,8 +1797,15 @@ int spmm16_core(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
                               [] { const char* e = std::getenv("SPARTA_H16_QUAD"); return !e || atoi(e) != 0; }() && !a8_form;
             const bool wide = ty == 0 && A->wide16;
             const bool live_form = fwd_live && ty == A->live_fwd_ty && (quad || slab256 || h16_live_form_available(A->kp16, ty != 0, c_stage && !wide, wide));
-            A->fwd_last_form[ty] = a8_form ? 3 : live_form ? 2 : 1;
-            if (a8_form) {
+            // the fp8 image with a live-block set (sparta_vbs_set_a8_live): the a8 launch on the compacted records and live ranges of live forward, whose last
+            // words hold the exponents (vbs_q8lv_scales_kernel, k_h16_a8_live.hip).  The same instantiations as the a8 form, so the same exclusions.
+            const bool a8_live_form = a8_form && A->a8_live && A->live_on && A->live_fwd_built && A->live_fwd_ty == ty;
+            A->fwd_last_form[ty] = a8_live_form ? 4 : a8_form ? 3 : live_form ? 2 : 1;
+            if (a8_live_form) {
+                sp.A = reinterpret_cast<const float*>(A->d_a8); sp.steps = A->d_fwd_steps; sp.worker_range = A->d_fwd_wrange; sp.sub_ranges = 0;
+                launch_h16_a8_live_stream(A->kp16, ty != 0, bf16, c_stage, wide, grid, st, sp);
+                sp.A = A->d_A;
+            } else if (a8_form) {
                 sp.A = reinterpret_cast<const float*>(A->d_a8); sp.steps = A->d_a8_steps; sp.sub_ranges = 0;
                 launch_h16_a8_stream(A->kp16, ty != 0, bf16, c_stage, wide, grid, st, sp);
                 sp.A = A->d_A;
@@ -2436,12 +2443,22 @@ namespace {
 // sparta_vbs_sgd_step repeats behind its elementwise kernel.  Returns the number of launches.
 // the fp8 image behind a write of values (sparta_vbs_set_forward_a8): while the switch is on, one launch of the quantise kernel on the array the images were
 // just written from, in stream order.  Launches only: capturable, and a replay requantises.
+// the fp8 image with a live-block set (sparta_vbs_set_a8_live): the exponent words of the private records into the compacted records the product walks, one
+// launch in stream order behind whatever moved either of them (a compaction rewrites every position from the plain records, a quantise launch every exponent)
+void a8_live_place_scales(sparta_vbs_t* A, hipStream_t st) {
+    if (!A->a8_live || !A->a8_on || !A->a8_built || A->a8_ty < 0 || !A->live_fwd_built || A->live_fwd_ty != A->a8_ty) return;
+    const int ty = A->a8_ty;
+    launch_a8_live_scales(st, A->d_a8_steps, A->n_steps[ty], A->upd_base[ty], (int64_t)(ty ? 64 : 32) * A->kp16, A->d_fwd_steps);
+    A->a8_live_launches++;
+}
+
 void a8_requantize(sparta_vbs_t* A, hipStream_t st, const float* src) {
     if (!A->a8_on || !A->a8_built || A->a8_ty < 0 || A->nztot <= 0) return;
     const int ty = A->a8_ty;
     launch_a8_quantize(ty ? 64 : 32, A->kp16, st, A->d_upd_map[ty], A->n_steps[ty], src, A->d_a8 + A->upd_base[ty], A->d_a8_steps);
     A->a8_valid = true;
     A->a8_launches++;
+    a8_live_place_scales(A, st);
 }
 
 int launch_images_from(sparta_vbs_t* A, hipStream_t st, const float* src) {
@@ -3189,6 +3206,8 @@ extern "C" int sparta_vbs_set_live_blocks(sparta_vbs_t* A, const uint8_t* keep, 
     if (A->live_words_built && A->live_n_words > 0) launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
     // live forward: the compacted records of the stream image behind the words (likewise written once they exist, whatever the switch says right now)
     launch_live_forward_lists(A, st);
+    // the fp8 image with a live-block set: the compaction rewrote every position from the plain records, the exponent words go back in behind it
+    a8_live_place_scales(A, st);
     HIP_TRY(hipGetLastError());
     A->live_on = true;
     return SPARTA_OK;
@@ -3408,9 +3427,10 @@ extern "C" int sparta_vbs_set_forward_a8(sparta_vbs_t* A, int32_t enable, void* 
     using sparta::fail;
     const char* entry = "sparta_vbs_set_forward_a8";
     if (!A) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": NULL handle");
-    if (!enable) {                               // host state only; the image goes stale from here on
+    if (!enable) {                               // host state only; the image goes stale from here on (and sparta_vbs_set_a8_live, which needs it, goes off)
         A->a8_on = false;
         A->a8_valid = false;
+        A->a8_live = false;
         return SPARTA_OK;
     }
     if (A->ext_sparse || A->dtype == SPARTA_F32 || !(A->create_flags & SPARTA_CREATE_UPDATABLE))
@@ -3445,6 +3465,64 @@ extern "C" int sparta_vbs_a8_info(sparta_vbs_t* A, int64_t* info_out, void* stre
     info_out[7] = A->a8_launches;
     return SPARTA_OK;
     SPARTA_GUARD_END("sparta_vbs_a8_info")
+}
+
+// ---- sparta_vbs_set_a8_live: the product on the fp8 image skips dead blocks (k_h16_a8_live.hip) -------------------------------------------------
+extern "C" int sparta_vbs_set_a8_live(sparta_vbs_t* A, int32_t enable, void* stream) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* entry = "sparta_vbs_set_a8_live";
+    if (!A) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": NULL handle");
+    if (!enable) {                               // host state only
+        A->a8_live = false;
+        return SPARTA_OK;
+    }
+    if (!A->a8_on || !A->a8_built || A->a8_ty < 0)
+        return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the fp8 weight image is off -- switch it on first (sparta_vbs_set_forward_a8)");
+    if (int rc = prune_handle_check(A, entry)) return rc;
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, true);
+    if (int rc = ensure_live_forward_arrays(A, entry)) return rc;      // the word map, seg_last and the compacted arrays of live forward: the same ones
+    if (A->live_fwd_ty != A->a8_ty)
+        return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the stream image that has the fp8 image has no live forward lists");
+    A->a8_live = true;
+    if (A->live_on) {                            // a set is installed already: words, lists and scales follow from its snapshot
+        launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
+        launch_live_forward_lists(A, st);
+        a8_live_place_scales(A, st);
+        HIP_TRY(hipGetLastError());
+    }
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_vbs_set_a8_live")
+}
+
+extern "C" int sparta_vbs_a8_live_info(sparta_vbs_t* A, int64_t* info_out, void* stream) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* entry = "sparta_vbs_a8_live_info";
+    if (!A || !info_out) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": NULL argument");
+    std::memset(info_out, 0, 8 * sizeof(int64_t));
+    const int ty = A->a8_built ? A->a8_ty : ((A->ext_sparse || A->dtype == SPARTA_F32) ? -1 : live_forward_image(A));
+    const bool lists = A->live_fwd_built && ty >= 0 && A->live_fwd_ty == ty;
+    info_out[0] = A->a8_live ? 1 : 0;
+    info_out[1] = A->a8_live && A->a8_on && A->a8_valid && A->a8_built && A->live_on && lists ? 1 : 0;
+    info_out[2] = ty + 1;
+    info_out[3] = ty >= 0 ? A->n_steps[ty] : 0;
+    info_out[5] = A->a8_live_launches;
+    if (!A->live_on || !lists) return SPARTA_OK;
+    DeviceGuard guard(A->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, true);
+    if (g_capturing) return capture_refusal("read the live ranges back (synchronises)", entry);
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<int32_t> ranges((size_t)A->fwd_n_ranges * 2);
+    if (!ranges.empty()) HIP_TRY(hipMemcpy(ranges.data(), A->d_fwd_wrange, ranges.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int64_t r = 0; r < A->fwd_n_ranges; r++) info_out[4] += std::max(0, ranges[(size_t)(2 * r + 1)] - ranges[(size_t)(2 * r)]);
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_vbs_a8_live_info")
 }
 
 extern "C" int sparta_vbs_a8_get(sparta_vbs_t* A, uint8_t* codes, int32_t* exps, int32_t* group, void* stream) {

@@ -569,7 +569,7 @@ struct sparta_vbs {
     int32_t* d_fwd_wrange = nullptr;                           // the live ranges, as d_wrange[ty]
     int32_t* d_fwd_seg_last = nullptr;                         // [n_steps[ty]] last record of every step's segment (pattern only)
     int64_t fwd_n_ranges = 0, fwd_n_alloc = 0;
-    int32_t fwd_last_form[2] = {0, 0};                         // per stream image: the form the last 16-bit product ran (0 none yet, 1 plain, 2 live, 3 a8)
+    int32_t fwd_last_form[2] = {0, 0};                         // per stream image: the form the last 16-bit product ran (0 none yet, 1 plain, 2 live, 3 a8, 4 a8 live)
     // the fp8 weight image (sparta_vbs_set_forward_a8): the switch is host state.  The first enabling call allocates the e4m3 image of the one stream image (the
     // slices of d_A in the same order, one byte per element, the same padding behind them) and a private copy of its step records whose last word holds the
     // biased exponents of the slice's two groups.  vbs_a8quant_kernel rewrites both behind every write of values while the switch is on.
@@ -578,6 +578,11 @@ struct sparta_vbs {
     uint8_t* d_a8 = nullptr;                                   // [a8_bytes]
     sparta_dev::StepRec* d_a8_steps = nullptr;                 // [n_steps[a8_ty] + padding]
     int64_t a8_bytes = 0, a8_n_groups = 0, a8_launches = 0;
+    // the fp8 image with a live-block set (sparta_vbs_set_a8_live): host state; acts while a8 is on and valid and a live set is installed.  The product then walks
+    // the compacted records of live forward (d_fwd_steps, d_fwd_wrange: live_fwd is off by the refusals, so they have no other reader) on d_a8, and
+    // vbs_q8lv_scales_kernel keeps the exponent words in their last words, behind every compaction and every quantise launch.
+    bool a8_live = false;
+    int64_t a8_live_launches = 0;
     // block scores of the SDDMM (sparta_vbs_sddmm_block_ssq): a second snapshot / group list / count, written from `sel` by every call (goff is d_live_goff:
     // pattern only), the all-ones selection that stands in for sel == NULL, and the pattern-only slot offsets, finish records and the fp64 slots themselves
     bool score_built = false;
@@ -709,6 +714,10 @@ bool h16_live_form_available(int kp, bool mi2, bool c_stage, bool wide);
 // four-accumulator form takes the 128-column sibling of its plan), and the kernel that writes the e4m3 image and the exponents from nztot floats in the mab layout
 void launch_h16_a8_stream(int kp, bool mi2, bool bf16, bool c_stage, bool wide, dim3 grid, hipStream_t st, const StreamParams& sp);
 void launch_a8_quantize(int tms, int kp, hipStream_t st, const UpdSlice* map, int64_t n_slices, const float* mab, uint8_t* dst, StepRec* recs);
+// k_h16_a8_live.hip: the a8 form on the compacted records of live forward (the launches of launch_h16_a8_stream), and the kernel that copies the exponent word of
+// every slice (a8_recs[s].pad) into the compacted record whose a_off = base + s * slice names it
+void launch_h16_a8_live_stream(int kp, bool mi2, bool bf16, bool c_stage, bool wide, dim3 grid, hipStream_t st, const StreamParams& sp);
+void launch_a8_live_scales(hipStream_t st, const StepRec* a8_recs, int64_t n_steps, int64_t base, int64_t slice, StepRec* live_recs);
 
 // vbs_plan.cpp
 struct StreamPlanIn {

@@ -565,7 +565,8 @@ class DeviceVBS(ValuesRecord):
         dead blocks are zero (what BlockPruner leaves) C is the plain product, the sign of a zero aside.  Needs updatable=True.  Handles without the live form
         (fp32, a hub plan, two stream images, block widths that are no multiple of 32) accept the switch and keep their kernels: live_forward_info() says
         which.  Off by default; without a live set the switch does nothing.  The first enabling call builds helper arrays and cannot be captured; later
-        calls, and set_live_blocks from then on, are launches only (torch's current stream)."""
+        calls, and set_live_blocks from then on, are launches only (torch's current stream).  Refused while set_forward_a8 is on: set_a8_live is the switch
+        for the product on the fp8 image."""
         if not on:
             check(lib.sparta_vbs_set_live_forward(self.h, 0, None))
             return
@@ -603,7 +604,7 @@ class DeviceVBS(ValuesRecord):
         other handle raises SpartaError (unsupported), as does a handle with live forward on.  The image is invalid (the product keeps the 16-bit weights) until
         the next set_values / sgd_step / adam_step, each of which requantises behind itself while the switch is on; values=W is the switch followed by
         set_values(W).  An Inf weight becomes NaN under the switch (e4m3fn has no Inf).  Off by default.  The first enabling call allocates and cannot be
-        captured."""
+        captured.  set_a8_live is the switch that lets this product skip pruned blocks."""
         if not on:
             check(lib.sparta_vbs_set_forward_a8(self.h, 0, None))
             return
@@ -619,6 +620,27 @@ class DeviceVBS(ValuesRecord):
         a = np.zeros(8, np.int64)
         check(lib.sparta_vbs_a8_info(self.h, a.ctypes.data_as(_i64p), self._live_stream(stream)))
         keys = ["switch", "valid", "capable", "form_one_tile", "form_pair", "groups", "image_bytes", "quantize_launches"]
+        return {k: int(a[i]) for i, k in enumerate(keys)}
+
+    def set_a8_live(self, on, stream=None):
+        """sparta_vbs_set_a8_live: with on=True, the fp8 switch on (set_forward_a8) and a live set installed (set_live_blocks) the product on the fp8 image walks
+        the steps of live blocks only: a dead block adds nothing to C whatever W, the codes or the exponents hold for it, and neither its codes nor the rows of
+        B are read on its behalf.  C is, bit for bit, the live forward product of a plain handle on the dequantised values.  Needs set_forward_a8 on: SpartaError
+        (unsupported) otherwise; set_forward_a8(False) clears this switch too.  Off by default; without a live set the a8 kernels multiply every block.  The first
+        enabling call builds the helper arrays of live forward and cannot be captured; later calls, and set_live_blocks and every write of values from then on,
+        are launches only (torch's current stream).  a8_info()["form_*"] says 4 when the product took this form."""
+        if not on:
+            check(lib.sparta_vbs_set_a8_live(self.h, 0, None))
+            return
+        check(lib.sparta_vbs_set_a8_live(self.h, 1, self._live_stream(stream)))
+
+    def a8_live_info(self, stream=None):
+        """sparta_vbs_a8_live_info (synchronises when a live set is installed): {"switch", "active" (the fp8 switch on and its image valid, this switch on, a live
+        set installed), "capable" (the stream image with the form: 0 none, 1 the <= 32-row tiles, 2 the 64-row / pair tiles), "steps", "kept_steps",
+        "scale_launches" (launches of the scale-placement kernel so far)}"""
+        a = np.zeros(8, np.int64)
+        check(lib.sparta_vbs_a8_live_info(self.h, a.ctypes.data_as(_i64p), self._live_stream(stream)))
+        keys = ["switch", "active", "capable", "steps", "kept_steps", "scale_launches"]
         return {k: int(a[i]) for i, k in enumerate(keys)}
 
     def a8_get(self, stream=None):

@@ -126,11 +126,14 @@ class BlockPruner:
     mask: the 16-bit forward product of a handle that has the live form walks the steps of the live blocks only.  The values of the pruned blocks are zero,
     so the product is the same, the sign of a zero aside; handles without the live form (fp32 among them) keep their kernels.
 
+    a8_live=True (needs skip_pruned=True, excludes live_forward=True): for handles whose fp8 weight image is on (DeviceVBS.set_forward_a8) -- the handles are
+    switched to the live form of the product on that image (DeviceVBS.set_a8_live) once they have their mask.  A handle with the fp8 switch off raises there.
+
     Regrowing (dynamic sparse training): pass probe(i) to pair i's vbs_linear(..., probe=...) and backward leaves the squared gradient norm of every PRUNED
     block in it (DeviceVBS.sddmm_block_ssq: the live sddmm no longer computes those gradients).  regrow(fraction) then swaps: the weakest live blocks are
     pruned and as many pruned blocks with the largest gradient come back, as zeros -- the number of live blocks stays what prune made it."""
 
-    def __init__(self, optimizer_or_pairs, scope="global", normalize=True, skip_pruned=False, live_steps=False, live_forward=False):
+    def __init__(self, optimizer_or_pairs, scope="global", normalize=True, skip_pruned=False, live_steps=False, live_forward=False, a8_live=False):
         import torch
         if scope not in ("global", "layer"):
             raise ValueError("scope must be 'global' or 'layer'")
@@ -138,7 +141,12 @@ class BlockPruner:
             raise ValueError("live_steps=True needs skip_pruned=True (the steps skip the blocks of the live set the handles are given)")
         if live_forward and not skip_pruned:
             raise ValueError("live_forward=True needs skip_pruned=True (the forward product skips the blocks of the live set the handles are given)")
+        if a8_live and not skip_pruned:
+            raise ValueError("a8_live=True needs skip_pruned=True (the product on the fp8 image skips the blocks of the live set the handles are given)")
+        if a8_live and live_forward:
+            raise ValueError("a8_live=True and live_forward=True exclude each other (live forward is refused while the fp8 weight image is on)")
         self.live_forward = bool(live_forward)
+        self.a8_live = bool(a8_live)
         self.optimizer = optimizer_or_pairs if hasattr(optimizer_or_pairs, "pairs") else None
         self.pairs = [(h, v) for h, v in (self.optimizer.pairs if self.optimizer is not None else optimizer_or_pairs)]
         self.scope, self.normalize, self.skip_pruned, self.live_steps = scope, bool(normalize), bool(skip_pruned), bool(live_steps)
@@ -183,6 +191,8 @@ class BlockPruner:
                 handle.set_live_steps(True)
             if self.live_forward:
                 handle.set_live_forward(True)
+            if self.a8_live:
+                handle.set_a8_live(True)
 
     def prune(self, sparsity):
         """select() on scores(), then per pair the pruned blocks zeroed in values, values.grad (if present) and the optimizer's state (where allocated), and
