@@ -827,6 +827,46 @@ int sparta_vbs_live_lists_host(int64_t cols, int64_t block_rows, int64_t block_c
                                int64_t block_row_begin, int64_t block_row_end, const uint8_t* keep, int32_t* sd_groups, int32_t* sd_count, int32_t* t_blocks,
                                int32_t* t_count, int64_t* info_out /* [8] */);
 
+/* ---- repattern: a trained layer moved onto a new block pattern (k_repattern.hip) ------------------------------------------------------------------
+ * The new pattern is the old one minus dropped blocks plus added ones; the new handle is an ordinary handle created from the new arrays, and the values and
+ * the optimizer state are moved from the old mab layout to the new one on the device.
+ *
+ * sparta_vbs_repattern_host (pure host code, no GPU): the pattern rule.  cols .. block_row_end as for sparta_vbs_block_table_host.  keep: host bytes, one per
+ * stored block of the range in the numbering of sparta_vbs_mask_blocks (0 = drop); NULL keeps all.  add: n_add pairs of int64 (block-row, block column); the
+ * block-row is numbered over the WHOLE matrix and must lie in [block_row_begin, block_row_end).
+ *   nzcount_out[block_rows], jab_out[new nblocks]: the arrays of the WHOLE matrix; block-rows outside the range keep their blocks as they are (their jab
+ *     entries are copied, not looked at).  row_part and block_col_size do not change.
+ *   map_out[new blocks of the range], int32: per block of the range in the NEW numbering the old block number in the range, or -1 for an added block.
+ *   counts_out[4] = {new nblocks, new nztot, new blocks in the range, new nztot of the range}.
+ * Inside each block-row of the range the new blocks are the kept old blocks plus the added ones, in strictly ascending block column.  Blocks of block-rows of
+ * height 0 are carried (and added) like any other: they have n_all = 0.  With jab_out == NULL and map_out == NULL the call only counts (nzcount_out may be
+ * NULL as well; it is written whenever it is given).
+ * SPARTA_ERR_INVALID, with NOTHING written: bad dimensions or range; the old jab not strictly ascending inside a block-row of the range, or an entry outside
+ * [0, block_cols); an added pair outside the range or with a block column >= block_cols (or negative); an added pair given twice; an added pair that names
+ * a block the old pattern stores, kept or not (a stored dead block comes back through keep, not through add); a NULL pointer whose count is above 0 (jab,
+ * keep excepted, add; of jab_out and map_out exactly one NULL while its count is above 0; counts_out always).  More than 2^31 - 1 blocks in the new range:
+ * SPARTA_ERR_UNSUPPORTED.
+ *
+ * sparta_vbs_move_blocks: S0..S3 are device tensors in src's mab layout (nztot(src) floats: a range handle's slice from 0), D0..D3 device tensors in dst's;
+ * any 4-byte alignment.  A pair with both pointers NULL is skipped; exactly one NULL: SPARTA_ERR_INVALID.  map: HOST, n_blocks(dst) int32.
+ *   every dst block b with map[b] >= 0 receives all n_all elements of src block map[b] bit for bit -- positions past cols, NaN payloads and -0.0 included;
+ *   every dst block b with map[b] == -1 receives n_all stores of +0.0f and nothing is read for it;
+ *   every element of a D belongs to exactly one block, so D may be uninitialised; no byte outside the tensors is written and no S is written.
+ * Validated on the host before anything is launched: both handles made from VBS arrays (others: SPARTA_ERR_UNSUPPORTED, as sparta_vbs_mask_blocks) and on the
+ * same device; every map entry in [-1, n_blocks(src)); mapped blocks of equal n_all (the handles need not come from sparta_vbs_repattern_host: any two
+ * patterns whose mapped blocks agree in size will do; a block of 2^31 or more elements: SPARTA_ERR_UNSUPPORTED); no D overlaps an S or another D; 4-byte
+ * alignment.  The call builds one 24-byte record per dst block (source offset, destination offset, n_all, moved or new), uploads them into storage the dst
+ * handle owns (grown when needed, freed by sparta_vbs_destroy) and launches ONE kernel for up to four pairs: one wave per dst block, a block's record read
+ * once, 16-byte stores on the destination's 16-byte grid, 16-byte loads where source and destination agree modulo 16 bytes and 4-byte loads elsewhere.
+ * It is a rare operation: it synchronises the stream (the records of an earlier call may still be read) and returns SPARTA_ERR_UNSUPPORTED while the stream is
+ * being captured.  dt_ms covers the kernel only.  n_blocks(dst) == 0, nztot(dst) == 0 or four skipped pairs: success, nothing launched.  src is not changed. */
+int sparta_vbs_repattern_host(int64_t cols, int64_t block_rows, int64_t block_col_size, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab,
+                              int64_t block_row_begin, int64_t block_row_end, const uint8_t* keep, const int64_t* add /* [n_add][2] */, int64_t n_add,
+                              int64_t* nzcount_out, int64_t* jab_out, int32_t* map_out, int64_t* counts_out /* [4] */);
+int sparta_vbs_move_blocks(sparta_vbs_t* dst, const sparta_vbs_t* src, const int32_t* map /* host, n_blocks(dst) */,
+                           const float* S0, float* D0, const float* S1, float* D1, const float* S2, float* D2, const float* S3, float* D3,
+                           void* stream, float* dt_ms);
+
 /* Ct (+)= A^T * X on the stored blocks of A: the gradient of the dense operand of C = A * B (X = dC, Ct = dB), on the handle itself, so that
  * it follows sparta_vbs_set_values in stream order.  Only handles made with SPARTA_CREATE_TRANSPOSE take the call; every other handle
  * (flags without the bit, sparta_vbs_create, _create_range, _create_from_csr, _create_transposed): SPARTA_ERR_UNSUPPORTED.

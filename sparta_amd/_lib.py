@@ -58,6 +58,7 @@ SYMBOLS = [
     "sparta_vbs_sddmm_block_ssq",
     "sparta_vbs_set_forward_a8", "sparta_vbs_a8_info", "sparta_vbs_a8_get", "sparta_a8_quantize_group",
     "sparta_vbs_set_a8_live", "sparta_vbs_a8_live_info",
+    "sparta_vbs_repattern_host", "sparta_vbs_move_blocks",
 ]
 
 
@@ -189,7 +190,10 @@ def _load():
     L.sparta_live_forward_compact.argtypes = [vp, C.c_int64, i32p, C.c_int64, C.c_int32, C.POINTER(C.c_uint8), vp, i32p, i64p]
     L.sparta_vbs_live_lists_get.argtypes = [vp, i32p, i32p, i32p, i32p, vp]
     L.sparta_vbs_live_lists_host.argtypes = [C.c_int64, C.c_int64, C.c_int64, i64p, i64p, i64p, C.c_int64, C.c_int64, C.POINTER(C.c_uint8), i32p, i32p, i32p, i32p, i64p]
-    L.sparta_vbs_create_from_csr.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, i64p, i32p, f32p, i64p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]
+    L.sparta_vbs_repattern_host.argtypes = [C.c_int64, C.c_int64, C.c_int64, i64p, i64p, i64p, C.c_int64, C.c_int64, C.POINTER(C.c_uint8), i64p, C.c_int64,
+                                            i64p, i64p, i32p, i64p]
+    L.sparta_vbs_move_blocks.argtypes = [vp, vp, i32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, vp, f32p]
+    L.sparta_vbs_create_from_csr.argtypes =[C.POINTER(vp), C.c_int64, C.c_int64, i64p, i32p, f32p, i64p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]
     L.sparta_vbs_plan_stats.argtypes = [C.c_int64, C.c_int64, i64p, i32p, f32p, i64p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, i64p]
     L.sparta_vbs_prepare_b.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, vp, C.POINTER(vp)]
     L.sparta_vbs_spmm_prepared.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, f32p]

@@ -127,6 +127,7 @@ void destroy_impl(sparta_vbs* v) {
     if (v->d_upd_hub) (void)hipFree(v->d_upd_hub);
     if (v->d_upd_ws) (void)hipFree(v->d_upd_ws);
     if (v->d_prune) (void)hipFree(v->d_prune);
+    if (v->d_repat) (void)hipFree(v->d_repat);
     if (v->d_live_keep) (void)hipFree(v->d_live_keep);
     if (v->d_live_goff) (void)hipFree(v->d_live_goff);
     if (v->d_live_groups) (void)hipFree(v->d_live_groups);
@@ -3012,6 +3013,197 @@ extern "C" int sparta_vbs_mask_blocks(sparta_vbs_t* A, const uint8_t* keep, floa
     return prune_call(A, "sparta_vbs_mask_blocks", A->nblocks == 0 || A->nztot == 0 || none, stream, dt_ms,
                       [&](hipStream_t st) { launch_mask_blocks(st, A->d_prune, A->n_prune, keep, T0, T1, T2, T3); });
     SPARTA_GUARD_END("sparta_vbs_mask_blocks")
+}
+
+// ---- repattern: sparta_vbs_repattern_host (the pattern rule, host only), sparta_vbs_move_blocks (k_repattern.hip) -------------------------------------
+// Everything is validated before the first output is written: an INVALID call leaves the caller's arrays as they were.
+extern "C" int sparta_vbs_repattern_host(int64_t cols, int64_t block_rows, int64_t w, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, int64_t br0,
+                                         int64_t br1, const uint8_t* keep, const int64_t* add, int64_t n_add, int64_t* nzcount_out, int64_t* jab_out,
+                                         int32_t* map_out, int64_t* counts_out) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* me = "sparta_vbs_repattern_host";
+    if (cols <= 0 || block_rows <= 0 || w <= 0 || !row_part || !nzcount || !counts_out || n_add < 0)
+        return fail(SPARTA_ERR_INVALID, std::string(me) + ": bad dimensions or NULL argument");
+    if (br0 < 0 || br1 > block_rows || br0 > br1) return fail(SPARTA_ERR_INVALID, std::string(me) + ": bad block-row range");
+    if (n_add > 0 && !add) return fail(SPARTA_ERR_INVALID, std::string(me) + ": add is NULL with n_add > 0");
+    const int64_t block_cols = (cols - 1) / w + 1;
+    int64_t jab_lo = 0, n_range = 0, n_after = 0, nz_outside = 0;
+    for (int64_t ib = 0; ib < block_rows; ib++) {
+        if (row_part[ib + 1] < row_part[ib] || nzcount[ib] < 0 || nzcount[ib] > block_cols) return fail(SPARTA_ERR_INVALID, std::string(me) + ": invalid row_part / nzcount");
+        if (ib < br0) jab_lo += nzcount[ib];
+        else if (ib < br1) n_range += nzcount[ib];
+        else n_after += nzcount[ib];
+        if (ib < br0 || ib >= br1) nz_outside += nzcount[ib] * (row_part[ib + 1] - row_part[ib]) * w;
+    }
+    if (jab_lo + n_range + n_after > 0 && !jab) return fail(SPARTA_ERR_INVALID, std::string(me) + ": jab is NULL");
+    // the old pattern of the range: strictly ascending block columns inside [0, block_cols)
+    for (int64_t ib = br0, q = jab_lo; ib < br1; ib++)
+        for (int64_t b = 0; b < nzcount[ib]; b++, q++) {
+            if (jab[q] < 0 || jab[q] >= block_cols) return fail(SPARTA_ERR_INVALID, std::string(me) + ": jab entry out of range");
+            if (b > 0 && jab[q] <= jab[q - 1]) return fail(SPARTA_ERR_INVALID, std::string(me) + ": jab is not strictly ascending inside a block-row of the range");
+        }
+    // the added blocks, sorted by (block-row, block column): inside the range, inside the matrix, each once, none stored already
+    std::vector<std::pair<int64_t, int64_t>> adds((size_t)n_add);
+    for (int64_t a = 0; a < n_add; a++) {
+        adds[(size_t)a] = {add[2 * a], add[2 * a + 1]};
+        if (add[2 * a] < br0 || add[2 * a] >= br1) return fail(SPARTA_ERR_INVALID, std::string(me) + ": an added block lies outside the block-row range");
+        if (add[2 * a + 1] < 0 || add[2 * a + 1] >= block_cols) return fail(SPARTA_ERR_INVALID, std::string(me) + ": an added block has a block column outside the matrix");
+    }
+    std::sort(adds.begin(), adds.end());
+    for (size_t a = 1; a < adds.size(); a++)
+        if (adds[a] == adds[a - 1]) return fail(SPARTA_ERR_INVALID, std::string(me) + ": an added block is given twice");
+    std::vector<int64_t> row_first((size_t)(br1 - br0) + 1, 0);          // first old block (numbered in the range) of every block-row of the range
+    for (int64_t ib = br0; ib < br1; ib++) row_first[(size_t)(ib - br0) + 1] = row_first[(size_t)(ib - br0)] + nzcount[ib];
+    for (const auto& ad : adds) {
+        const int64_t* lo = jab + jab_lo + row_first[(size_t)(ad.first - br0)];
+        const int64_t* hi = jab + jab_lo + row_first[(size_t)(ad.first - br0) + 1];
+        if (std::binary_search(lo, hi, ad.second))
+            return fail(SPARTA_ERR_INVALID, std::string(me) + ": an added block is stored by the old pattern (a stored dead block comes back through keep)");
+    }
+    // counts
+    int64_t new_range = n_add, nz_range = 0;
+    {
+        size_t a = 0;
+        for (int64_t ib = br0; ib < br1; ib++) {
+            int64_t n = 0;
+            for (int64_t q = row_first[(size_t)(ib - br0)]; q < row_first[(size_t)(ib - br0) + 1]; q++) n += !keep || keep[q] != 0;
+            new_range += n;
+            while (a < adds.size() && adds[a].first == ib) { n++; a++; }
+            nz_range += n * (row_part[ib + 1] - row_part[ib]) * w;
+        }
+    }
+    if (new_range > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, std::string(me) + ": more than 2^31 - 1 blocks in the new range");
+    const int64_t new_total = jab_lo + new_range + n_after;
+    const bool count_only = !jab_out && !map_out;
+    if (!count_only) {
+        if (!nzcount_out) return fail(SPARTA_ERR_INVALID, std::string(me) + ": nzcount_out is NULL");
+        if ((!jab_out && new_total > 0) || (!map_out && new_range > 0)) return fail(SPARTA_ERR_INVALID, std::string(me) + ": jab_out or map_out is NULL");
+    }
+    // ---- nothing was written up to here ----
+    counts_out[0] = new_total; counts_out[1] = nz_outside + nz_range; counts_out[2] = new_range; counts_out[3] = nz_range;
+    if (nzcount_out) {
+        size_t a = 0;
+        for (int64_t ib = 0; ib < block_rows; ib++) {
+            int64_t n = nzcount[ib];
+            if (ib >= br0 && ib < br1) {
+                n = 0;
+                for (int64_t q = row_first[(size_t)(ib - br0)]; q < row_first[(size_t)(ib - br0) + 1]; q++) n += !keep || keep[q] != 0;
+                while (a < adds.size() && adds[a].first == ib) { n++; a++; }
+            }
+            nzcount_out[ib] = n;
+        }
+    }
+    if (count_only) return SPARTA_OK;
+    int64_t o = 0;
+    for (int64_t q = 0; q < jab_lo; q++) jab_out[o++] = jab[q];
+    {
+        size_t a = 0;
+        int64_t m = 0;
+        for (int64_t ib = br0; ib < br1; ib++) {
+            int64_t q = row_first[(size_t)(ib - br0)];
+            const int64_t q1 = row_first[(size_t)(ib - br0) + 1];
+            for (;;) {                                                    // merge of two ascending lists that share no column
+                while (q < q1 && keep && keep[q] == 0) q++;
+                const bool has_add = a < adds.size() && adds[a].first == ib;
+                if (q >= q1 && !has_add) break;
+                if (has_add && (q >= q1 || adds[a].second < jab[jab_lo + q])) {
+                    jab_out[o++] = adds[a].second; map_out[m++] = -1; a++;
+                } else {
+                    jab_out[o++] = jab[jab_lo + q]; map_out[m++] = (int32_t)q; q++;
+                }
+            }
+        }
+    }
+    for (int64_t q = jab_lo + n_range; q < jab_lo + n_range + n_after; q++) jab_out[o++] = jab[q];
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_vbs_repattern_host")
+}
+
+namespace {
+
+// the block table of a handle on the host ([n_blocks][4], sparta_vbs_block_table_host over the handle's own block-rows), from the heights and counts kept at
+// creation and the handle's jab; the handle is not changed
+int host_block_table(const sparta_vbs_t* A, const char* entry, std::vector<int64_t>& table) {
+    using sparta::fail;
+    const int64_t nb = A->nblocks;
+    if (nb > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": more than 2^31 - 1 blocks");
+    std::vector<int32_t> jab32((size_t)nb);
+    if (nb > 0) HIP_TRY(hipMemcpy(jab32.data(), A->d_jab, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<int64_t> jab(jab32.begin(), jab32.end());
+    table.assign((size_t)nb * 4, 0);
+    int64_t n = 0;
+    if (int rc = build_block_table(A->cols, A->w, 0, A->block_rows, A->h_row_part.data(), A->h_nzcount.data(), jab.data(), 0, table.data(), &n)) return rc;
+    if (n != nb) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": the block table disagrees with the handle's block count");
+    return SPARTA_OK;
+}
+
+}  // namespace
+
+extern "C" int sparta_vbs_move_blocks(sparta_vbs_t* dst, const sparta_vbs_t* src, const int32_t* map, const float* S0, float* D0, const float* S1, float* D1,
+                                      const float* S2, float* D2, const float* S3, float* D3, void* stream, float* dt_ms) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* me = "sparta_vbs_move_blocks";
+    if (int rc = prune_handle_check(dst, me)) return rc;
+    if (int rc = prune_handle_check(src, me)) return rc;
+    if (dst->device != src->device) return fail(SPARTA_ERR_INVALID, std::string(me) + ": the two handles live on different devices");
+    const float* S[4] = {S0, S1, S2, S3};
+    float* D[4] = {D0, D1, D2, D3};
+    bool any = false;
+    for (int q = 0; q < 4; q++) {
+        if ((S[q] == nullptr) != (D[q] == nullptr)) return fail(SPARTA_ERR_INVALID, std::string(me) + ": a pair with exactly one NULL pointer");
+        if ((uintptr_t)S[q] % 4 != 0 || (uintptr_t)D[q] % 4 != 0) return fail(SPARTA_ERR_INVALID, std::string(me) + ": the tensors must be 4-byte aligned");
+        any = any || D[q] != nullptr;
+    }
+    const int64_t nb = dst->nblocks, nb_src = src->nblocks;
+    if (nb > 0 && !map) return fail(SPARTA_ERR_INVALID, std::string(me) + ": map is NULL");
+    for (int64_t b = 0; b < nb; b++)
+        if (map[b] < -1 || map[b] >= nb_src) return fail(SPARTA_ERR_INVALID, std::string(me) + ": a map entry outside [-1, n_blocks(src))");
+    // no D may overlap an S or another D (byte ranges; an empty tensor overlaps nothing)
+    const uintptr_t s_bytes = (uintptr_t)src->nztot * 4, d_bytes = (uintptr_t)dst->nztot * 4;
+    auto overlap = [](uintptr_t a, uintptr_t an, uintptr_t b, uintptr_t bn) { return an > 0 && bn > 0 && a < b + bn && b < a + an; };
+    for (int q = 0; q < 4; q++) {
+        if (!D[q]) continue;
+        for (int r = 0; r < 4; r++) {
+            if (S[r] && overlap((uintptr_t)D[q], d_bytes, (uintptr_t)S[r], s_bytes)) return fail(SPARTA_ERR_INVALID, std::string(me) + ": a destination tensor overlaps a source tensor");
+            if (r > q && D[r] && overlap((uintptr_t)D[q], d_bytes, (uintptr_t)D[r], d_bytes)) return fail(SPARTA_ERR_INVALID, std::string(me) + ": two destination tensors overlap");
+        }
+    }
+    DeviceGuard guard(dst->device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(me) + ": hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const CaptureScope capture(st, true);
+    if (g_capturing) return capture_refusal("build and upload the records of the move (it synchronises)", me);
+    std::vector<int64_t> td, ts;
+    if (int rc = host_block_table(dst, me, td)) return rc;
+    if (int rc = host_block_table(src, me, ts)) return rc;
+    std::vector<MoveBlock> rec((size_t)nb);
+    for (int64_t b = 0; b < nb; b++) {
+        const int64_t n_all = td[(size_t)(4 * b + 2)];
+        if (n_all > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, std::string(me) + ": a block of 2^31 or more elements");
+        const int64_t m = map[b];
+        if (m >= 0 && ts[(size_t)(4 * m + 2)] != n_all) return fail(SPARTA_ERR_INVALID, std::string(me) + ": a mapped block differs in size (n_all) from its source block");
+        rec[(size_t)b] = MoveBlock{m >= 0 ? ts[(size_t)(4 * m)] : 0, td[(size_t)(4 * b)], (int32_t)n_all, m >= 0 ? 1 : 0};
+    }
+    const bool nothing_to_do = nb == 0 || dst->nztot == 0 || !any;
+    if (!nothing_to_do) {
+        HIP_TRY(hipStreamSynchronize(st));                                // (the kernel of an earlier call may still read the records)
+        if (int rc = ensure_scratch(&dst->d_repat, &dst->d_repat_bytes, rec.size() * sizeof(MoveBlock))) return rc;
+        HIP_TRY(hipMemcpy(dst->d_repat, rec.data(), rec.size() * sizeof(MoveBlock), hipMemcpyHostToDevice));
+    }
+    if (dt_ms) HIP_TRY(hipEventRecord(dst->ev0, st));
+    if (!nothing_to_do) {
+        launch_move_blocks(st, (const MoveBlock*)dst->d_repat, nb, S, D);
+        HIP_TRY(hipGetLastError());
+    }
+    if (dt_ms) {
+        HIP_TRY(hipEventRecord(dst->ev1, st));
+        HIP_TRY(hipEventSynchronize(dst->ev1));
+        HIP_TRY(hipEventElapsedTime(dt_ms, dst->ev0, dst->ev1));
+    }
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_vbs_move_blocks")
 }
 
 // ---- the live-block set: sparta_vbs_set_live_blocks, _live_info, _live_lists_get, _live_lists_host (k_live.hip) ----------------------------------

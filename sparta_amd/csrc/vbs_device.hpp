@@ -336,6 +336,10 @@ constexpr int kSpmmTSlab = 128;     // columns of X / Ct per workgroup (32 per w
 struct PruneBlock { int64_t off; int32_t n_in, n_all; };
 static_assert(sizeof(PruneBlock) == 16, "PruneBlock must stay 16 bytes");
 constexpr int kPruneWaves = kThreads / 64;    // blocks per workgroup: one wave each
+// repattern (k_repattern.hip): one record per block of the DESTINATION handle, mab order: where its elements come from in the source layout, where they go,
+// how many (n_all), and whether the block is moved (1) or new (0: zeros, nothing read)
+struct MoveBlock { int64_t src_off, dst_off; int32_t n_all, moved; };
+static_assert(sizeof(MoveBlock) == 24, "MoveBlock must stay 24 bytes");
 
 // the epilogue of a linear layer (k_epilogue.hip): column-major rows x n_cols operands.  A work item = a tile of kThreads rows x a run of kEpRun columns.
 // Rows [head, head + 4 n4) are the body (vec_tiles tiles, a lane owns four rows: every operand is aligned there in every column), the others the edge
@@ -537,6 +541,9 @@ struct sparta_vbs {
     std::vector<int64_t> h_row_part, h_nzcount;                // [block_rows + 1] (from 0), [block_rows]
     sparta_dev::PruneBlock* d_prune = nullptr;
     int64_t n_prune = -1;                                      // -1: not built yet
+    // repattern (sparta_vbs_move_blocks with this handle as the destination): the records of the last call, grown when needed
+    void* d_repat = nullptr;
+    size_t d_repat_bytes = 0;
     // the live-block set (sparta_vbs_set_live_blocks): whether one is installed is host state; the helper arrays (pattern only) are built at the first call,
     // the snapshot and the compacted lists are written by the launches of every call (k_live.hip)
     bool live_on = false, live_built = false;
@@ -691,6 +698,8 @@ void launch_grad_ctl_finish(hipStream_t st, void* R, float max_norm, float growt
 // keep[b] == 0 stored as +0.0f (all n_all elements) in each non-NULL T[0..3]
 void launch_block_ssq(hipStream_t st, const PruneBlock* blocks, int64_t n_blocks, const float* W, double* ssq);
 void launch_mask_blocks(hipStream_t st, const PruneBlock* blocks, int64_t n_blocks, const uint8_t* keep, float* T0, float* T1, float* T2, float* T3);
+// k_repattern.hip: one wave per record; per non-NULL pair (S[q], D[q]) the block copied bit for bit from the source layout or stored as +0.0f
+void launch_move_blocks(hipStream_t st, const MoveBlock* blocks, int64_t n_blocks, const float* const* S, float* const* D);
 // k_epilogue.hip: Y = act(Z + bias); dZ = dY * act'(Z + bias), and with p.dbias the fixed-order fp64 row sums (a second launch folds the runs when n_runs != 1)
 void launch_epilogue_fwd(hipStream_t st, int y_dtype, const EpilogueParams& p);
 void launch_epilogue_bwd(hipStream_t st, int dy_dtype, int dz_dtype, const EpilogueParams& p);

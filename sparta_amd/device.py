@@ -678,6 +678,38 @@ class DeviceVBS(ValuesRecord):
                                             self._live_stream(stream)))
         return out
 
+    def move_blocks(self, src, map, *pairs, timed=False, stream=None):
+        """sparta_vbs_move_blocks with this handle as the destination: tensors moved from the mab layout of `src` (another DeviceVBS on this device) to this
+        handle's.  map: int32, one entry per block of THIS handle -- the block of src it receives, or -1 for a new block, which becomes +0.0 (VBR.repattern
+        returns such a map; any map whose mapped blocks agree in size will do).  pairs: (src_tensor, dst_tensor), contiguous float32 tensors on this device of
+        nztot(src) and nztot(this) elements; the destinations are overwritten completely (they may be torch.empty) and must overlap nothing.  Blocks travel bit
+        for bit.  One launch per group of up to four pairs.  The handles' own images are NOT changed: follow with set_values.  A rare operation: it
+        synchronises the stream (torch's current one) and cannot be captured.  Returns kernel ms if timed else None."""
+        import torch
+        if not isinstance(src, DeviceVBS) or src.device != self.device:
+            raise ValueError("src must be a DeviceVBS on device %d" % self.device)
+        bmap = np.ascontiguousarray(map, np.int32).reshape(-1)
+        if bmap.size != self.n_blocks:
+            raise ValueError("map must hold n_blocks = %d elements" % self.n_blocks)
+        ptrs = []
+        for i, (s, d) in enumerate(pairs):
+            sp, dp = src._prune_operand("source tensor %d" % i, s), self._prune_operand("destination tensor %d" % i, d)
+            if d.numel() == 0:                                 # (nothing to write: an empty tensor has no address to give, and a half-NULL pair is refused)
+                continue
+            if s.numel() == 0:                                 # (every block is new and nothing is read: any valid address stands for the empty source)
+                keep_alive = torch.empty(1, dtype=torch.float32, device=d.device)
+                sp = C.cast(C.c_void_p(keep_alive.data_ptr()), _f32p)
+            ptrs.append((sp, dp))
+        st = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+        mp = bmap.ctypes.data_as(C.POINTER(C.c_int32)) if bmap.size else None
+        total = 0.0
+        for g in range(0, max(len(ptrs), 1), 4):
+            grp = [p for pair in ptrs[g:g + 4] for p in pair] + [None] * (8 - 2 * len(ptrs[g:g + 4]))
+            dt = C.c_float(0)
+            check(lib.sparta_vbs_move_blocks(self.h, src.h, mp, *grp, C.c_void_p(st), C.byref(dt) if timed else None))
+            total += dt.value
+        return total if timed else None
+
     def set_values_host(self, mab):
         """set_values with a host array (numpy, fp32, nztot elements), staged through scratch of the handle.  Returns kernel ms."""
         mab = np.ascontiguousarray(mab, np.float32).reshape(-1)
@@ -820,6 +852,38 @@ class PreparedB:
             self.close()
         except Exception:
             pass
+
+
+def repattern(vbmat, handle, tensors, keep=None, add=None, block_row_range=None):
+    """A trained layer moved onto a new block pattern: the old pattern minus the blocks with keep[b] == 0 plus the blocks of `add` (VBR.repattern states the
+    rule).  vbmat: the VBR whose arrays `handle` was created from (its pattern is what counts; its mab is not read); block_row_range: the range the handle was
+    created with, if any; tensors: float32 device tensors in the handle's mab layout -- the values FIRST, then whatever shares their layout (momentum,
+    exp_avg, exp_avg_sq).  Returns (new_vbmat, new_handle, new_tensors, map):
+      new_vbmat    the new pattern (pattern only: its mab is all zero -- the values live in new_tensors[0])
+      new_handle   an ordinary fresh handle of the old one's dtype, device, range and creation flags: the planner deals its steps anew and its images hold
+                   what is kept; created from zeros, then given new_tensors[0] by set_values.  The old handle must be updatable.
+      new_tensors  one torch.empty tensor per entry of `tensors`, filled by ONE move_blocks call per four tensors: kept blocks bit for bit, added blocks +0.0
+      map          int32 numpy: per new block of the range the old block number, or -1
+    If the old handle multiplies with its fp8 weight image (set_forward_a8) the new one is switched on as well.  The live set and the live switches are NOT
+    carried: the new handle has no dead blocks unless the caller keeps some (BlockPruner.grow re-applies its own).  The old handle is left open and unchanged.
+    This call synchronises: a keep given as a device tensor is downloaded, and move_blocks synchronises the stream."""
+    import torch
+    if not handle.updatable:
+        raise ValueError("repattern needs a handle created with updatable=True (the new handle takes the moved values through set_values)")
+    if not tensors:
+        raise ValueError("repattern needs at least the values tensor")
+    if keep is not None and hasattr(keep, "detach"):
+        keep = keep.detach().cpu().numpy()                     # (synchronises)
+    new_vbmat, bmap = vbmat.repattern(keep=keep, add=add, block_row_range=block_row_range, values=False)
+    new_handle = DeviceVBS(new_vbmat, device=handle.device, dtype=handle.dtype, block_row_range=block_row_range, updatable=True,
+                           transposable=handle.transposable)
+    n = new_handle._nztot()
+    new_tensors = [torch.empty(n, dtype=torch.float32, device=t.device) for t in tensors]
+    new_handle.move_blocks(handle, bmap, *zip(tensors, new_tensors))
+    if handle.dtype != _lib.F32 and handle.a8_info()["switch"]:
+        new_handle.set_forward_a8(True)
+    new_handle.set_values(new_tensors[0])
+    return new_vbmat, new_handle, new_tensors, bmap
 
 
 def vbs_multiply(vbmat, B, B_cols, C_out, n_streams=None, device=0):

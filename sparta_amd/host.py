@@ -418,6 +418,43 @@ class VBR:
         out["info"] = info
         return out
 
+    def repattern(self, keep=None, add=None, block_row_range=None, values=True):
+        """sparta_vbs_repattern_host and the move on the host: this matrix on a new block pattern -- the old one minus the blocks of the block-rows
+        block_row_range = (b0, b1) (default: all) with keep[b] == 0, plus the blocks of `add`.  keep: n_blocks bytes in the numbering of block_table(block_row_range)
+        (None keeps all); add: a list of (block-row, block column) pairs, the block-row numbered over the whole matrix and inside the range, none of them stored
+        by the old pattern.  Returns (new VBR, map): the new VBR has this one's row_part and block_col_size; map is an int32 array with one entry per block of the
+        range in the NEW numbering, the old block number in the range or -1 for an added block.  The new mab holds the old values of every kept block, bit
+        for bit (the stored positions past cols included), and zeros in the added blocks; values=False leaves the new mab all zero (a pattern-only VBR)."""
+        b0, b1 = (0, self.block_rows) if block_row_range is None else (int(block_row_range[0]), int(block_row_range[1]))
+        rp, nz, jab = (np.ascontiguousarray(a, np.int64) for a in (self.row_part, self.nzcount, self.jab))
+        u8p = C.POINTER(C.c_uint8)
+        if keep is not None:
+            keep = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8).reshape(-1)
+            if not (0 <= b0 <= b1 <= self.block_rows) or keep.size != int(nz[b0:b1].sum()):
+                raise ValueError("keep must hold one element per stored block of the block-row range")
+        addv = np.ascontiguousarray(np.asarray([] if add is None else add, np.int64).reshape(-1, 2))
+        args = (self.cols, self.block_rows, self.block_col_size, rp.ctypes.data_as(_i64p), nz.ctypes.data_as(_i64p), jab.ctypes.data_as(_i64p), b0, b1,
+                None if keep is None else keep.ctypes.data_as(u8p), addv.ctypes.data_as(_i64p) if len(addv) else None, len(addv))
+        counts = np.zeros(4, np.int64)
+        check(lib.sparta_vbs_repattern_host(*args, None, None, None, counts.ctypes.data_as(_i64p)))
+        nz_new, jab_new, bmap = np.zeros(self.block_rows, np.int64), np.zeros(int(counts[0]), np.int64), np.zeros(int(counts[2]), np.int32)
+        check(lib.sparta_vbs_repattern_host(*args, nz_new.ctypes.data_as(_i64p), jab_new.ctypes.data_as(_i64p) if len(jab_new) else None,
+                                            bmap.ctypes.data_as(_i32p) if len(bmap) else None, counts.ctypes.data_as(_i64p)))
+        new = VBR.from_arrays(self.rows, self.cols, self.block_col_size, rp.copy(), nz_new, jab_new, np.zeros(int(counts[1]), np.float32))
+        if values:
+            per_row = np.diff(rp) * int(self.block_col_size)
+            lo, hi = int((per_row * nz)[:b0].sum()), int((per_row * nz)[:b1].sum())                      # the range's slice of the old mab
+            lo_n, hi_n = int((per_row * nz_new)[:b0].sum()), int((per_row * nz_new)[:b1].sum())          # ... and of the new one (lo_n == lo)
+            old = np.ascontiguousarray(self.mab, np.float32).view(np.uint32)
+            out = new.mab.view(np.uint32)
+            out[:lo_n] = old[:lo]
+            out[hi_n:] = old[hi:]
+            t_old, t_new = self.block_table((b0, b1)), new.block_table((b0, b1))
+            for b, m in enumerate(bmap):
+                if m >= 0:
+                    out[lo_n + t_new[b, 0]:lo_n + t_new[b, 0] + t_new[b, 2]] = old[lo + t_old[m, 0]:lo + t_old[m, 0] + t_old[m, 2]]
+        return new, bmap
+
     def to_device(self, device=0, dtype=_lib.F32, block_row_range=None, updatable=False, transposable=False):
         from .device import DeviceVBS
         return DeviceVBS(self, device=device, dtype=dtype, block_row_range=block_row_range, updatable=updatable, transposable=transposable)

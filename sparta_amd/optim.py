@@ -28,6 +28,22 @@ class VbsSGD:
             handle.sgd_step(values, values.grad, self._bufs[i], lr=self.lr, momentum=self.momentum, weight_decay=self.weight_decay,
                             grad_scale=grad_scale, ctl=ctl)
 
+    def repattern(self, i, vbmat, keep=None, add=None, block_row_range=None):
+        """Pair i moved onto a new block pattern (sparta_amd.repattern: the old pattern minus the blocks with keep[b] == 0 plus the blocks of `add`; vbmat is the
+        VBR of the pair's handle, block_row_range the range the handle was created with).  The pair is replaced by the new handle and a new leaf `values`
+        with the old one's requires_grad and grad = None; the momentum buffer, where it is allocated, travels in the same launch.  The old handle is left
+        open and the old tensors are left as they are.  last_map holds the block map of the call.  Synchronises.  Returns (new_vbmat, new_handle, new_values)."""
+        from .device import repattern
+        handle, values = self.pairs[i]
+        buf = self._bufs[i]
+        new_vbmat, new_handle, new_t, self.last_map = repattern(vbmat, handle, [values.detach()] + ([buf] if buf is not None else []), keep=keep, add=add,
+                                                                block_row_range=block_row_range)
+        new_values = new_t[0].requires_grad_(values.requires_grad)
+        self.pairs[i] = (new_handle, new_values)
+        if buf is not None:
+            self._bufs[i] = new_t[1]
+        return new_vbmat, new_handle, new_values
+
     def zero_grad(self, set_to_none=True):
         for _, values in self.pairs:
             if values.grad is None:
@@ -37,6 +53,26 @@ class VbsSGD:
             else:
                 values.grad.detach_()
                 values.grad.zero_()
+
+    def state_dict(self):
+        """{"momentum_buffer": [per pair: None (no step with momentum yet) or a copy of the buffer], "hyper": {...}}"""
+        return {"momentum_buffer": [None if b is None else b.detach().clone() for b in self._bufs],
+                "hyper": {"lr": self.lr, "momentum": self.momentum, "weight_decay": self.weight_decay}}
+
+    def load_state_dict(self, sd):
+        import torch
+        if len(sd["momentum_buffer"]) != len(self.pairs):
+            raise ValueError("the state dict holds %d pairs, the optimizer %d" % (len(sd["momentum_buffer"]), len(self.pairs)))
+        for i, src in enumerate(sd["momentum_buffer"]):
+            values = self.pairs[i][1]
+            if src is not None and src.numel() != values.numel():
+                raise ValueError("pair %d: momentum_buffer holds %d elements, expected %d" % (i, src.numel(), values.numel()))
+        for i, src in enumerate(sd["momentum_buffer"]):
+            values = self.pairs[i][1]
+            self._bufs[i] = None if src is None else src.detach().to(device=values.device, dtype=torch.float32).clone().reshape(-1)
+        h = sd.get("hyper", {})
+        self.lr, self.momentum = float(h.get("lr", self.lr)), float(h.get("momentum", self.momentum))
+        self.weight_decay = float(h.get("weight_decay", self.weight_decay))
 
 
 class VbsAdamW:
@@ -76,6 +112,20 @@ class VbsAdamW:
             s = self._state_of(i)
             handle.adam_step(values, values.grad, s["exp_avg"], s["exp_avg_sq"], s["state"], lr=self.lr, betas=self.betas, eps=self.eps,
                              weight_decay=self.weight_decay, decoupled=self.decoupled, grad_scale=grad_scale, ctl=ctl)
+
+    def repattern(self, i, vbmat, keep=None, add=None, block_row_range=None):
+        """VbsSGD.repattern for Adam: exp_avg and exp_avg_sq, where they are allocated, travel with the values in the same launch; the 8-word device state,
+        which holds the step count, is kept as it is (the same tensor).  Returns (new_vbmat, new_handle, new_values)."""
+        from .device import repattern
+        handle, values = self.pairs[i]
+        st = self._state[i]
+        new_vbmat, new_handle, new_t, self.last_map = repattern(vbmat, handle, [values.detach()] + ([st["exp_avg"], st["exp_avg_sq"]] if st is not None else []),
+                                                                keep=keep, add=add, block_row_range=block_row_range)
+        new_values = new_t[0].requires_grad_(values.requires_grad)
+        self.pairs[i] = (new_handle, new_values)
+        if st is not None:
+            self._state[i] = {"exp_avg": new_t[1], "exp_avg_sq": new_t[2], "state": st["state"]}
+        return new_vbmat, new_handle, new_values
 
     def zero_grad(self, set_to_none=True):
         VbsSGD.zero_grad(self, set_to_none)

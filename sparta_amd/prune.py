@@ -1,7 +1,8 @@
 """Block pruning for block-sparse layers on VBS handles: a score per stored block (sparta_vbs_block_ssq), a selection rule in torch, and the chosen blocks
 written as zeros -- and kept zero through training -- in the weights, the optimizer state and the gradients (sparta_vbs_mask_blocks).  The block pattern
 of a handle stays as creation made it: a pruned block is a stored block of zeros, which the fp32 forward product already skips (the k-compaction of
-set_values follows the zero pattern of the new values).  torch is imported when first used, as in optim.py."""
+set_values follows the zero pattern of the new values).  A new pattern is a new handle: BlockPruner.compact and .grow move a
+layer onto one, with its values and optimizer state (sparta_amd.repattern).  torch is imported when first used, as in optim.py."""
 import math
 
 
@@ -131,7 +132,11 @@ class BlockPruner:
 
     Regrowing (dynamic sparse training): pass probe(i) to pair i's vbs_linear(..., probe=...) and backward leaves the squared gradient norm of every PRUNED
     block in it (DeviceVBS.sddmm_block_ssq: the live sddmm no longer computes those gradients).  regrow(fraction) then swaps: the weakest live blocks are
-    pruned and as many pruned blocks with the largest gradient come back, as zeros -- the number of live blocks stays what prune made it."""
+    pruned and as many pruned blocks with the largest gradient come back, as zeros -- the number of live blocks stays what prune made it.
+
+    Changing the pattern: compact(vbmats) drops the pruned blocks for good -- every pair moves onto a fresh handle that stores its live blocks only, with its
+    values and the optimizer's state (sparta_amd.repattern) -- and grow(i, vbmat, add) adds blocks the pattern does not store.  Both replace handles, values,
+    masks and probes by new objects of the new sizes: fetch pairs, keep_masks() and probe(i) again afterwards."""
 
     def __init__(self, optimizer_or_pairs, scope="global", normalize=True, skip_pruned=False, live_steps=False, live_forward=False, a8_live=False):
         import torch
@@ -213,7 +218,7 @@ class BlockPruner:
 
     def probe(self, i):
         """pair i's probe for vbs_linear(..., probe=...): .sel (uint8, n_blocks) is kept equal to keep == 0 in place by prune, regrow and load_state_dict,
-        .out (float64, n_blocks) takes the scores of the pruned blocks in backward"""
+        .out (float64, n_blocks) takes the scores of the pruned blocks in backward.  compact and grow replace the probe of a pair they move: fetch it again"""
         return self._probes[i]
 
     def regrow(self, fraction):
@@ -238,6 +243,77 @@ class BlockPruner:
             self._keep[i].copy_(k)
             self._apply(i)
 
+    def _repattern_pair(self, i, vbmat, keep, add, block_row_range):
+        """pair i on its new pattern, through the optimizer where there is one (its state travels); returns (new_vbmat, map)"""
+        if self.optimizer is not None:
+            new_vbmat, handle, values = self.optimizer.repattern(i, vbmat, keep=keep, add=add, block_row_range=block_row_range)
+            bmap = self.optimizer.last_map
+        else:
+            from .device import repattern
+            old = self.pairs[i][1]
+            new_vbmat, handle, new_t, bmap = repattern(vbmat, self.pairs[i][0], [old.detach()], keep=keep, add=add, block_row_range=block_row_range)
+            values = new_t[0].requires_grad_(old.requires_grad)
+        self.pairs[i] = (handle, values)
+        return new_vbmat, bmap
+
+    def compact(self, vbmats, block_row_ranges=None):
+        """The pruned blocks dropped for good: every pair moves onto the pattern of its live blocks (VbsSGD / VbsAdamW.repattern(i, vbmat, keep=mask), or
+        sparta_amd.repattern on values where the pruner was given pairs), so that the handle's images, values and the optimizer's state hold the live blocks
+        only and the planner deals the steps anew.  vbmats: per pair the VBR its handle was created from; block_row_ranges: per pair the range its handle was
+        created with (None: whole matrices).  Afterwards the pruner starts afresh on the new sizes: all-ones masks, new block sizes, zeroed probes, every
+        block live -- keep_masks() and probe(i) return NEW tensors, and pairs / optimizer.pairs hold new handles and new leaf values (grad None): fetch
+        them again.  The new handles carry no live set (they have no dead blocks); the next prune installs one.  The old handles stay open.  Synchronises.
+        Returns the new vbmats."""
+        import torch
+        if len(vbmats) != len(self.pairs):
+            raise ValueError("compact needs one vbmat per pair")
+        out = []
+        for i, vbmat in enumerate(vbmats):
+            br = None if block_row_ranges is None else block_row_ranges[i]
+            new_vbmat, _ = self._repattern_pair(i, vbmat, self._keep[i], None, br)
+            out.append(new_vbmat)
+            handle, values = self.pairs[i]
+            self._keep[i] = torch.ones(handle.n_blocks, dtype=torch.uint8, device=values.device)
+            self._n_in[i] = handle.block_ssq(torch.ones_like(values, requires_grad=False))
+            self._probes[i] = BlockProbe(torch.zeros(handle.n_blocks, dtype=torch.uint8, device=values.device),
+                                         torch.zeros(handle.n_blocks, dtype=torch.float64, device=values.device))
+        sizes = [k.numel() for k in self._keep]
+        self._live = sizes if self._per_layer() else [sum(sizes)]
+        return out
+
+    def grow(self, i, vbmat, add, block_row_range=None):
+        """Pair i grown beyond its stored pattern: the blocks of `add` -- (block-row, block column) pairs the pattern does not store -- are added, as zeros in
+        values and in the optimizer's state, and are LIVE.  The masks, the block sizes and the probe are re-laid through the block map: existing blocks keep
+        their entries (a pruned block stays pruned and stored), added ones get keep = 1 and a probe score of 0.  With skip_pruned=True the new handle gets the
+        live set and the pruner's live switches again.  keep_masks()[i] and probe(i) are NEW tensors, and the pair holds a new handle and new leaf values.
+        To choose the blocks, score candidates the handle does not store with a pattern-only handle of the candidates and sddmm_block_ssq.
+        Synchronises.  Returns the new vbmat."""
+        import torch
+        add = [(int(a), int(b)) for a, b in add]
+        old_keep, old_out = self._keep[i], self._probes[i].out
+        new_vbmat, bmap = self._repattern_pair(i, vbmat, None, add, block_row_range)
+        handle, values = self.pairs[i]
+        m = torch.from_numpy(bmap.astype("int64")).to(values.device)
+        old = m >= 0
+        src = m.clamp(min=0)
+        keep = torch.ones(handle.n_blocks, dtype=torch.uint8, device=values.device)
+        keep[old] = old_keep[src[old]]
+        out = torch.zeros(handle.n_blocks, dtype=torch.float64, device=values.device)
+        out[old] = old_out[src[old]]
+        self._keep[i] = keep
+        self._n_in[i] = handle.block_ssq(torch.ones_like(values, requires_grad=False))
+        self._probes[i] = BlockProbe((keep == 0).to(torch.uint8), out)
+        self._live[i if self._per_layer() else 0] += len(add)
+        if self.skip_pruned:
+            handle.set_live_blocks(keep)
+            if self.live_steps:
+                handle.set_live_steps(True)
+            if self.live_forward:
+                handle.set_live_forward(True)
+            if self.a8_live:
+                handle.set_a8_live(True)
+        return new_vbmat
+
     def mask_grads(self):
         """the gradient of every pruned block made zero: call it after backward and before GradCtl.collect / step, so that the clipped norm is that of the
         live blocks and the step leaves the pruned ones at zero"""
@@ -246,7 +322,8 @@ class BlockPruner:
                 handle.mask_blocks(keep, values.grad)
 
     def keep_masks(self):
-        """per pair the mask, a uint8 device tensor of n_blocks elements (0 = pruned); updated in place by prune"""
+        """per pair the mask, a uint8 device tensor of n_blocks elements (0 = pruned); updated in place by prune.  compact and grow change the number of blocks:
+        after them this returns NEW tensors, of the new sizes"""
         return list(self._keep)
 
     def sparsity(self):
