@@ -864,10 +864,35 @@ def repattern(vbmat, handle, tensors, keep=None, add=None, block_row_range=None)
                    what is kept; created from zeros, then given new_tensors[0] by set_values.  The old handle must be updatable.
       new_tensors  one torch.empty tensor per entry of `tensors`, filled by ONE move_blocks call per four tensors: kept blocks bit for bit, added blocks +0.0
       map          int32 numpy: per new block of the range the old block number, or -1
-    If the old handle multiplies with its fp8 weight image (set_forward_a8) the new one is switched on as well.  The live set and the live switches are NOT
+    If the old handle multiplies with its fp8 weight image (set_forward_a8) the new one is switched on as well -- and must qualify for it: whether a handle
+    has the ONE stream image that holds every element depends on the pattern (an emptied block-row leaves its partner of a pair tile behind, a pattern of no
+    block has no image at all).  Where the new pattern does not qualify the call raises SpartaError (unsupported) naming that reason, with the new handle
+    closed and nothing else touched: switch the image off (set_forward_a8(False)) or choose another pattern.  The live set and the live switches are NOT
     carried: the new handle has no dead blocks unless the caller keeps some (BlockPruner.grow re-applies its own).  The old handle is left open and unchanged.
-    This call synchronises: a keep given as a device tensor is downloaded, and move_blocks synchronises the stream."""
-    import torch
+    This call synchronises: a keep given as a device tensor is downloaded, and move_blocks synchronises the stream.
+    The two halves are repattern_prepare (everything that can refuse) and repattern_commit (the move): BlockPruner.compact prepares all its pairs first."""
+    plan = repattern_prepare(vbmat, handle, tensors, keep=keep, add=add, block_row_range=block_row_range)
+    return repattern_commit(plan)
+
+
+class RepatternPlan:
+    """what repattern_prepare hands to repattern_commit: the new pattern, the open new handle, the block map and the old side.  close() gives the new handle
+    up (a plan that is not committed must be closed)"""
+
+    def __init__(self, vbmat, handle, tensors, new_vbmat, new_handle, bmap, a8):
+        self.vbmat, self.handle, self.tensors = vbmat, handle, list(tensors)
+        self.new_vbmat, self.new_handle, self.bmap, self.a8 = new_vbmat, new_handle, bmap, a8
+
+    def close(self):
+        if self.new_handle is not None:
+            self.new_handle.close()
+            self.new_handle = None
+
+
+def repattern_prepare(vbmat, handle, tensors, keep=None, add=None, block_row_range=None):
+    """The first half of repattern, with its arguments: the checks, the host rule, the new handle, and -- if the old handle multiplies with its fp8 weight
+    image -- whether the new one has the form for it (a8_info()["capable"]).  Moves nothing and changes nothing on the old side.  A refusal closes the new
+    handle before it raises.  Returns a RepatternPlan for repattern_commit (or plan.close())."""
     if not handle.updatable:
         raise ValueError("repattern needs a handle created with updatable=True (the new handle takes the moved values through set_values)")
     if not tensors:
@@ -875,15 +900,40 @@ def repattern(vbmat, handle, tensors, keep=None, add=None, block_row_range=None)
     if keep is not None and hasattr(keep, "detach"):
         keep = keep.detach().cpu().numpy()                     # (synchronises)
     new_vbmat, bmap = vbmat.repattern(keep=keep, add=add, block_row_range=block_row_range, values=False)
+    a8 = bool(handle.dtype != _lib.F32 and handle.a8_info()["switch"])
     new_handle = DeviceVBS(new_vbmat, device=handle.device, dtype=handle.dtype, block_row_range=block_row_range, updatable=True,
                            transposable=handle.transposable)
-    n = new_handle._nztot()
-    new_tensors = [torch.empty(n, dtype=torch.float32, device=t.device) for t in tensors]
-    new_handle.move_blocks(handle, bmap, *zip(tensors, new_tensors))
-    if handle.dtype != _lib.F32 and handle.a8_info()["switch"]:
-        new_handle.set_forward_a8(True)
-    new_handle.set_values(new_tensors[0])
-    return new_vbmat, new_handle, new_tensors, bmap
+    try:
+        for i, t in enumerate(tensors):
+            handle._prune_operand("tensor %d" % i, t)         # (what move_blocks would refuse in the middle of the commit)
+        if a8 and not new_handle.a8_info()["capable"]:
+            raise _lib.SpartaError(_lib.ERR_UNSUPPORTED, "repattern: the old handle multiplies with its fp8 weight image (set_forward_a8) and the new pattern does "
+                                   "not qualify for one: its %d blocks do not lie in one stream image that holds every stored element (an emptied block-row "
+                                   "leaves its partner of a pair tile behind; a pattern without a block has no image).  Nothing was changed: switch the image "
+                                   "off first, or keep / add blocks so that the pattern qualifies" % new_handle.n_blocks)
+    except Exception:
+        new_handle.close()
+        raise
+    return RepatternPlan(vbmat, handle, tensors, new_vbmat, new_handle, bmap, a8)
+
+
+def repattern_commit(plan):
+    """The second half of repattern: the tensors moved in one move_blocks call per four, the fp8 switch set where the old handle has it on, the new handle
+    given its values.  Returns (new_vbmat, new_handle, new_tensors, map).  A failure closes the new handle; the old side is never written."""
+    import torch
+    new_handle = plan.new_handle
+    try:
+        n = new_handle._nztot()
+        new_tensors = [torch.empty(n, dtype=torch.float32, device=t.device) for t in plan.tensors]
+        new_handle.move_blocks(plan.handle, plan.bmap, *zip(plan.tensors, new_tensors))
+        if plan.a8:
+            new_handle.set_forward_a8(True)
+        new_handle.set_values(new_tensors[0])
+    except Exception:
+        plan.close()
+        raise
+    plan.new_handle = None
+    return plan.new_vbmat, new_handle, new_tensors, plan.bmap
 
 
 def vbs_multiply(vbmat, B, B_cols, C_out, n_streams=None, device=0):

@@ -32,12 +32,24 @@ class VbsSGD:
         """Pair i moved onto a new block pattern (sparta_amd.repattern: the old pattern minus the blocks with keep[b] == 0 plus the blocks of `add`; vbmat is the
         VBR of the pair's handle, block_row_range the range the handle was created with).  The pair is replaced by the new handle and a new leaf `values`
         with the old one's requires_grad and grad = None; the momentum buffer, where it is allocated, travels in the same launch.  The old handle is left
-        open and the old tensors are left as they are.  last_map holds the block map of the call.  Synchronises.  Returns (new_vbmat, new_handle, new_values)."""
-        from .device import repattern
+        open and the old tensors are left as they are.  last_map holds the block map of the call.  Synchronises.  Returns (new_vbmat, new_handle, new_values).
+        A refusal (sparta_amd.repattern: a new pattern that does not qualify for the fp8 weight image the old handle multiplies with, among others) raises
+        before anything of the optimizer is replaced."""
+        return self.repattern_commit(i, self.repattern_prepare(i, vbmat, keep=keep, add=add, block_row_range=block_row_range))
+
+    def repattern_prepare(self, i, vbmat, keep=None, add=None, block_row_range=None):
+        """the first half of repattern (sparta_amd.repattern_prepare on the pair's values and momentum buffer): everything that can refuse, nothing moved and
+        nothing of the optimizer changed.  Returns the plan for repattern_commit(i, plan); a plan that is not committed must be closed (plan.close())"""
+        from .device import repattern_prepare
         handle, values = self.pairs[i]
         buf = self._bufs[i]
-        new_vbmat, new_handle, new_t, self.last_map = repattern(vbmat, handle, [values.detach()] + ([buf] if buf is not None else []), keep=keep, add=add,
-                                                                block_row_range=block_row_range)
+        return repattern_prepare(vbmat, handle, [values.detach()] + ([buf] if buf is not None else []), keep=keep, add=add, block_row_range=block_row_range)
+
+    def repattern_commit(self, i, plan):
+        """the second half: the move, then the pair and the momentum buffer replaced.  Returns (new_vbmat, new_handle, new_values)"""
+        from .device import repattern_commit
+        values, buf = self.pairs[i][1], self._bufs[i]
+        new_vbmat, new_handle, new_t, self.last_map = repattern_commit(plan)
         new_values = new_t[0].requires_grad_(values.requires_grad)
         self.pairs[i] = (new_handle, new_values)
         if buf is not None:
@@ -116,11 +128,21 @@ class VbsAdamW:
     def repattern(self, i, vbmat, keep=None, add=None, block_row_range=None):
         """VbsSGD.repattern for Adam: exp_avg and exp_avg_sq, where they are allocated, travel with the values in the same launch; the 8-word device state,
         which holds the step count, is kept as it is (the same tensor).  Returns (new_vbmat, new_handle, new_values)."""
-        from .device import repattern
+        return self.repattern_commit(i, self.repattern_prepare(i, vbmat, keep=keep, add=add, block_row_range=block_row_range))
+
+    def repattern_prepare(self, i, vbmat, keep=None, add=None, block_row_range=None):
+        """VbsSGD.repattern_prepare on the pair's values, exp_avg and exp_avg_sq"""
+        from .device import repattern_prepare
         handle, values = self.pairs[i]
         st = self._state[i]
-        new_vbmat, new_handle, new_t, self.last_map = repattern(vbmat, handle, [values.detach()] + ([st["exp_avg"], st["exp_avg_sq"]] if st is not None else []),
-                                                                keep=keep, add=add, block_row_range=block_row_range)
+        return repattern_prepare(vbmat, handle, [values.detach()] + ([st["exp_avg"], st["exp_avg_sq"]] if st is not None else []), keep=keep, add=add,
+                                 block_row_range=block_row_range)
+
+    def repattern_commit(self, i, plan):
+        """VbsSGD.repattern_commit: the move, then the pair and its moments replaced (the step words stay the same tensor)"""
+        from .device import repattern_commit
+        values, st = self.pairs[i][1], self._state[i]
+        new_vbmat, new_handle, new_t, self.last_map = repattern_commit(plan)
         new_values = new_t[0].requires_grad_(values.requires_grad)
         self.pairs[i] = (new_handle, new_values)
         if st is not None:

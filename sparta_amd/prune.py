@@ -243,15 +243,22 @@ class BlockPruner:
             self._keep[i].copy_(k)
             self._apply(i)
 
-    def _repattern_pair(self, i, vbmat, keep, add, block_row_range):
-        """pair i on its new pattern, through the optimizer where there is one (its state travels); returns (new_vbmat, map)"""
+    def _prepare_pair(self, i, vbmat, keep, add, block_row_range):
+        """the first half of pair i's repattern (sparta_amd.repattern_prepare), through the optimizer where there is one: may refuse, changes nothing"""
         if self.optimizer is not None:
-            new_vbmat, handle, values = self.optimizer.repattern(i, vbmat, keep=keep, add=add, block_row_range=block_row_range)
+            return self.optimizer.repattern_prepare(i, vbmat, keep=keep, add=add, block_row_range=block_row_range)
+        from .device import repattern_prepare
+        return repattern_prepare(vbmat, self.pairs[i][0], [self.pairs[i][1].detach()], keep=keep, add=add, block_row_range=block_row_range)
+
+    def _commit_pair(self, i, plan):
+        """the second half: pair i on its new pattern (the optimizer's state travels); returns (new_vbmat, map)"""
+        if self.optimizer is not None:
+            new_vbmat, handle, values = self.optimizer.repattern_commit(i, plan)
             bmap = self.optimizer.last_map
         else:
-            from .device import repattern
+            from .device import repattern_commit
             old = self.pairs[i][1]
-            new_vbmat, handle, new_t, bmap = repattern(vbmat, self.pairs[i][0], [old.detach()], keep=keep, add=add, block_row_range=block_row_range)
+            new_vbmat, handle, new_t, bmap = repattern_commit(plan)
             values = new_t[0].requires_grad_(old.requires_grad)
         self.pairs[i] = (handle, values)
         return new_vbmat, bmap
@@ -263,14 +270,29 @@ class BlockPruner:
         created with (None: whole matrices).  Afterwards the pruner starts afresh on the new sizes: all-ones masks, new block sizes, zeroed probes, every
         block live -- keep_masks() and probe(i) return NEW tensors, and pairs / optimizer.pairs hold new handles and new leaf values (grad None): fetch
         them again.  The new handles carry no live set (they have no dead blocks); the next prune installs one.  The old handles stay open.  Synchronises.
+        Every pair is prepared (sparta_amd.repattern_prepare: the new handle, and whether it qualifies for the fp8 weight image the old one multiplies with)
+        before any pair is moved: a refusal closes the new handles, raises, and leaves pruner and optimizer as they were -- all pairs compact, or none.
         Returns the new vbmats."""
         import torch
         if len(vbmats) != len(self.pairs):
             raise ValueError("compact needs one vbmat per pair")
+        plans = []
+        try:
+            for i, vbmat in enumerate(vbmats):
+                br = None if block_row_ranges is None else block_row_ranges[i]
+                plans.append(self._prepare_pair(i, vbmat, self._keep[i], None, br))
+        except Exception:
+            for plan in plans:
+                plan.close()
+            raise
         out = []
-        for i, vbmat in enumerate(vbmats):
-            br = None if block_row_ranges is None else block_row_ranges[i]
-            new_vbmat, _ = self._repattern_pair(i, vbmat, self._keep[i], None, br)
+        for i, plan in enumerate(plans):
+            try:
+                new_vbmat, _ = self._commit_pair(i, plan)
+            except Exception:
+                for later in plans[i + 1:]:
+                    later.close()
+                raise
             out.append(new_vbmat)
             handle, values = self.pairs[i]
             self._keep[i] = torch.ones(handle.n_blocks, dtype=torch.uint8, device=values.device)
@@ -291,7 +313,7 @@ class BlockPruner:
         import torch
         add = [(int(a), int(b)) for a, b in add]
         old_keep, old_out = self._keep[i], self._probes[i].out
-        new_vbmat, bmap = self._repattern_pair(i, vbmat, None, add, block_row_range)
+        new_vbmat, bmap = self._commit_pair(i, self._prepare_pair(i, vbmat, None, add, block_row_range))      # (a refusal raises before anything is replaced)
         handle, values = self.pairs[i]
         m = torch.from_numpy(bmap.astype("int64")).to(values.device)
         old = m >= 0

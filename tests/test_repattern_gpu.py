@@ -324,3 +324,270 @@ def test_the_fp8_switch_travels():
     finally:
         for d in (old, new_h, fresh):
             d.close()
+
+
+# ---- repattern under the fp8 switch: the new handle must qualify for the image, or the call refuses and changes nothing -----------------------------------
+# Whether a 16-bit handle has the ONE stream image that holds every element depends on the pattern: two adjacent 32-row block-rows become a pair tile (the
+# 64-row image) only when both store a block, and a 32-row block-row left alone gets tiles of the one-tile image -- a handle with both images has no fp8 form,
+# nor has a handle without a block.  Failing cases: `pairs` (eight 32-row block-rows) with block-row 1 or block-row 0 emptied, `pairs` with nothing kept,
+# `rows3` (32, 32, 32, the last block-row empty) grown by one block into the empty block-row.  Controls: the same geometries with a mask that keeps three
+# blocks in every block-row, and a block added to a block-row of the pair.
+from test_adam_step_host import adam_ref  # noqa: E402
+
+A8_DT = (sa.F16, sa.BF16)
+A8_CASES = [("pairs", "empty1", (), False), ("pairs", "empty0", (), False), ("pairs", "none", (), False), ("rows3", None, ((2, 1),), False),
+            ("pairs", "second", (), True), ("rows3", None, ((0, 3),), True)]
+a8_cases = pytest.mark.parametrize("case", A8_CASES, ids=["%s-%s" % (k, m or "grow%d" % a[0][0]) for k, m, a, _ in A8_CASES])
+a8_dtypes = pytest.mark.parametrize("dtype", A8_DT, ids=[DT_ID[d] for d in A8_DT])
+ADAM = dict(lr=1e-2, weight_decay=0.01)
+
+
+@functools.lru_cache(maxsize=None)
+def a8_geometry(key):
+    if key == "pairs":
+        a = U._edge_arrays(8 * 32, 8 * 32 - 11, 32, [32] * 8, [U.poison_present(ib) for ib in range(8)])
+    elif key == "rows3":
+        a = U._edge_arrays(96, 128, 32, [32, 32, 32], [[0, 1, 2], [1, 3], []])
+    else:
+        return geometry(key)
+    n = int((np.diff(a[3]) * a[4]).sum()) * a[2]
+    return U.sa_vbr(a, (np.random.default_rng(8800 + len(key)).integers(-8, 9, n) / 8.0).astype(f32))
+
+
+def a8_keep(v, name):
+    T = v.block_table()
+    brow = T[:, 3] >> 32
+    if name is None:
+        return None
+    if name in ("empty0", "empty1"):
+        return (brow != int(name[-1])).astype(np.uint8)
+    if name == "none":
+        return np.zeros(len(T), np.uint8)
+    keep = np.ones(len(T), np.uint8)
+    keep[1::2] = 0
+    assert name == "second" and all((keep[brow == ib] != 0).any() for ib in np.unique(brow))
+    return keep
+
+
+def a8_product(d, v):
+    """the forward product of handle d on a seeded small-integer B of 64 columns, as uint32 words"""
+    Bd, ldb = dev_op(np.random.default_rng(5).integers(-4, 5, (v.cols, 64)).astype(np.float64), d.dtype)
+    Cd = torch.full((v.rows * 64,), float("nan"), dtype=torch.float32, device="cuda")
+    d.spmm(Bd, Cd, 64, ldb=ldb)
+    return Cd.cpu().numpy().view(np.uint32)
+
+
+def a8_form(d):
+    fi = d.a8_info()
+    return max(fi["form_one_tile"], fi["form_pair"])
+
+
+def a8_fresh_check(host_v, dtype, W2, new_h, ok, form=3):
+    """a fresh handle on the new pattern says whether the pattern qualifies -- the premise of the case -- and, where it does, the repatterned handle's
+    product under the switch equals its product bit for bit; form: 4 where the caller gave the new handle a live set and the a8 live switch (every block of
+    it live: the same product)"""
+    fresh = host_v.to_device(0, dtype=dtype, updatable=True, transposable=True)
+    try:
+        assert (fresh.a8_info()["capable"] > 0) == ok, (fresh.a8_info(), "the case does not test what it says")
+        if ok:
+            fresh.set_forward_a8(True, values=W2.detach().clone())
+            fi = new_h.a8_info()
+            assert fi["switch"] == 1 and fi["valid"] == 1, fi
+            a, b = a8_product(new_h, host_v), a8_product(fresh, host_v)
+            assert not np.isnan(a.view(f32)).any() and np.array_equal(a, b)
+            assert a8_form(new_h) == form and a8_form(fresh) == 3
+    finally:
+        fresh.close()
+
+
+def refused(err):
+    assert err.value.code == _lib.ERR_UNSUPPORTED and "fp8" in str(err.value) and "repattern" in str(err.value), str(err.value)
+
+
+@pytest.fixture
+def created(monkeypatch):
+    """every DeviceVBS made while the test runs"""
+    made = []
+    init = sa.DeviceVBS.__init__
+
+    def spy(self, *a, **k):
+        init(self, *a, **k)
+        made.append(self)
+
+    monkeypatch.setattr(sa.DeviceVBS, "__init__", spy)
+    return made
+
+
+def free_bytes():
+    torch.cuda.synchronize()
+    return torch.cuda.mem_get_info()[0]
+
+
+@a8_dtypes
+@a8_cases
+def test_fp8_repattern_qualifies_or_refuses(case, dtype, created):
+    """sparta_amd.repattern"""
+    key, kname, add, ok = case
+    v = a8_geometry(key)
+    keep = a8_keep(v, kname)
+    old = v.to_device(0, dtype=dtype, updatable=True, transposable=True)
+    W = torch.from_numpy(v.mab.copy()).cuda()
+    M = torch.from_numpy(int_values(v.nztot, 78)).cuda()
+    old.set_forward_a8(True, values=W)
+    host_v, host_map = v.repattern(keep=keep, add=list(add))
+    before = a8_product(old, v)
+    del created[:]
+    new_h = None
+    try:
+        if ok:
+            new_v, new_h, (W2, M2), bmap = sa.repattern(v, old, [W, M], keep=keep, add=list(add))
+            assert np.array_equal(bmap, host_map) and np.array_equal(new_v.jab, host_v.jab)
+            assert np.array_equal(M2.cpu().numpy().view(np.uint32), R.move_vbr(v, (host_v.nzcount, host_v.jab), bmap, 0, v.block_rows, M.cpu().numpy()))
+            a8_fresh_check(host_v, dtype, W2, new_h, True)
+        else:
+            with pytest.raises(sa.SpartaError) as err:
+                sa.repattern(v, old, [W, M], keep=keep, add=list(add))
+            refused(err)
+            assert len(created) == 1 and not created[0].h, "the new handle was left open"
+            free0 = free_bytes()                                                             # (the runtime's own pools are warm now: the same call once more)
+            with pytest.raises(sa.SpartaError):
+                sa.repattern(v, old, [W, M], keep=keep, add=list(add))
+            assert free_bytes() == free0, "device memory is not back after the refusal"
+            a8_fresh_check(host_v, dtype, None, None, False)
+        # the old side is as it was, and still multiplies with its image
+        assert np.array_equal(W.cpu().numpy(), v.mab) and old.a8_info()["switch"] == 1 and old.a8_info()["valid"] == 1
+        assert np.array_equal(a8_product(old, v), before) and a8_form(old) == 3
+    finally:
+        for d in [old] + ([new_h] if new_h is not None else []):
+            d.close()
+
+
+class A8Train:
+    """pairs under one VbsAdamW (and a BlockPruner with the live switches of the fp8 product), every handle with its fp8 image on, one step taken so that the
+    optimizer's state exists"""
+
+    def __init__(self, vs, dtype):
+        self.vs, self.dtype = list(vs), dtype
+        handles = [v.to_device(0, dtype=dtype, updatable=True, transposable=True) for v in vs]
+        self.opened = list(handles)
+        Ws = [torch.from_numpy(v.mab.copy()).cuda().requires_grad_(True) for v in vs]
+        for h, w in zip(handles, Ws):
+            h.set_forward_a8(True, values=w.detach())
+        self.opt = sa.VbsAdamW(list(zip(handles, Ws)), **ADAM)
+        self.pruner = sa.BlockPruner(self.opt, skip_pruned=True, live_steps=True, a8_live=True)
+        self.t = 0
+        self.step()
+
+    def grads(self):
+        self.t += 1
+        return [(np.random.default_rng(4100 + 10 * self.t + i).integers(-8, 9, w.numel()) / 8.0).astype(f32) for i, (_, w) in enumerate(self.opt.pairs)]
+
+    def step(self):
+        """one AdamW step on seeded gradients (zero in the pruned blocks, as vbs_linear leaves them), every pair held to adam_ref bit for bit"""
+        G = self.grads()
+        keeps = [k.cpu().numpy() for k in self.pruner.keep_masks()]
+        want = []
+        for i, (h, w) in enumerate(self.opt.pairs):
+            T = self.vs[i].block_table()
+            for q in np.flatnonzero(keeps[i] == 0):
+                G[i][T[q, 0]:T[q, 0] + T[q, 2]] = 0
+            s = self.opt._state[i]
+            old = (w.detach().cpu().numpy(),) + ((np.zeros(w.numel(), f32),) * 2 + (np.zeros(8, np.uint32),) if s is None else
+                                                 (s["exp_avg"].cpu().numpy(), s["exp_avg_sq"].cpu().numpy(), s["state"].cpu().numpy().view(np.uint32)))
+            want.append(adam_ref(old[0], G[i], old[1], old[2], old[3], ADAM))
+            w.grad = torch.from_numpy(G[i]).cuda()
+        self.opt.step()
+        self.opt.zero_grad()
+        torch.cuda.synchronize()
+        for i, (h, w) in enumerate(self.opt.pairs):
+            s = self.opt._state[i]
+            got = (w.detach(), s["exp_avg"], s["exp_avg_sq"], s["state"])
+            for name, g, r in zip("WMVS", got, want[i]):
+                assert np.array_equal(g.cpu().numpy().view(np.uint32), np.asarray(r).view(np.uint32)), (i, name, "the step differs from adam_ref")
+            assert h.a8_info()["valid"] == 1
+
+    def identity(self):
+        """the objects a refused call must leave in place"""
+        out = [id(self.opt.pairs), id(self.pruner.pairs)]
+        for (h, w), (ph, pw), s, k, p in zip(self.opt.pairs, self.pruner.pairs, self.opt._state, self.pruner._keep, self.pruner._probes):
+            out += [id(h), id(w), id(ph), id(pw), id(s), id(s["exp_avg"]), id(s["exp_avg_sq"]), id(s["state"]), id(k), id(p), id(p.sel), id(p.out), h.h.value]
+        return out, [k.cpu().numpy().copy() for k in self.pruner._keep], list(self.pruner._live)
+
+    def close(self):
+        for h in self.opened + [h for h, _ in self.opt.pairs]:
+            h.close()
+
+
+def same_identity(a, b):
+    return a[0] == b[0] and all(np.array_equal(x, y) for x, y in zip(a[1], b[1])) and a[2] == b[2]
+
+
+@a8_dtypes
+@a8_cases
+def test_fp8_repattern_through_the_optimizer(case, dtype, created):
+    """VbsAdamW.repattern"""
+    key, kname, add, ok = case
+    v = a8_geometry(key)
+    keep = a8_keep(v, kname)
+    host_v, _ = v.repattern(keep=keep, add=list(add))
+    run = A8Train([v], dtype)
+    try:
+        ident = run.identity()
+        del created[:]
+        if ok:
+            new_v, new_h, new_w = run.opt.repattern(0, v, keep=keep, add=list(add))
+            assert run.opt.pairs[0] == (new_h, new_w) and new_w.numel() == host_v.nztot
+            a8_fresh_check(host_v, dtype, new_w, new_h, True)
+        else:
+            with pytest.raises(sa.SpartaError) as err:
+                run.opt.repattern(0, v, keep=keep, add=list(add))
+            refused(err)
+            assert len(created) == 1 and not created[0].h, "the new handle was left open"
+            free0 = free_bytes()
+            with pytest.raises(sa.SpartaError):
+                run.opt.repattern(0, v, keep=keep, add=list(add))
+            assert free_bytes() == free0, "device memory is not back after the refusal"
+            assert same_identity(run.identity(), ident), "the refused call changed the optimizer"
+            run.step()                                                                       # the old handle still trains
+    finally:
+        run.close()
+
+
+@a8_dtypes
+@a8_cases
+def test_fp8_compact_and_grow_move_every_pair_or_none(case, dtype, created):
+    """BlockPruner.compact / .grow on two pairs; the pair of the case is the SECOND: a refusal finds the first one already prepared"""
+    key, kname, add, ok = case
+    first, v = a8_geometry("rows3"), a8_geometry(key)
+    keep0, keep = a8_keep(first, "second"), a8_keep(v, kname)
+    run = A8Train([first, v], dtype)
+    try:
+        if keep is not None:
+            run.pruner.load_state_dict({"keep": [torch.from_numpy(keep0), torch.from_numpy(keep)]})
+            assert [h.live_info()["installed"] for h, _ in run.opt.pairs] == [1, 1]
+            run.step()
+        ident = run.identity()
+        call = (lambda: run.pruner.compact([first, v])) if keep is not None else (lambda: run.pruner.grow(1, v, list(add)))
+        del created[:]
+        if ok:
+            out = call()
+            new_v = out[1] if keep is not None else out
+            host_v, _ = v.repattern(keep=keep, add=list(add))
+            assert np.array_equal(new_v.jab, host_v.jab) and run.opt.pairs[1][1].numel() == host_v.nztot
+            assert len(created) == (2 if keep is not None else 1) and all(d.h for d in created)
+            a8_fresh_check(host_v, dtype, run.opt.pairs[1][1], run.opt.pairs[1][0], True, form=3 if keep is not None else 4)    # (grow hands the live set on)
+            run.vs = ([first.repattern(keep=keep0)[0], host_v] if keep is not None else [first, host_v])
+            run.step()
+        else:
+            with pytest.raises(sa.SpartaError) as err:
+                call()
+            refused(err)
+            assert len(created) == (2 if keep is not None else 1) and not any(d.h for d in created), "a new handle was left open"
+            free0 = free_bytes()
+            with pytest.raises(sa.SpartaError):
+                call()
+            assert free_bytes() == free0, "device memory is not back after the refusal"
+            assert same_identity(run.identity(), ident), "the refused call changed the optimizer or the pruner: compact moves every pair or none"
+            run.step()                                                                       # both old handles still train
+    finally:
+        run.close()
