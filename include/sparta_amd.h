@@ -937,6 +937,10 @@ int sparta_vbs_class_times(sparta_vbs_t* A, float* ms_out);
  * fraction of the 157.3 TFLOP/s fp32 matrix peak: bench.py reports it next to the roofline.  No reference counterpart. */
 int sparta_vbs_clock_mhz(sparta_vbs_t* A, double* mhz_out);
 
+/* Developer aid: the device allocations the library holds right now, process-wide -- how many, and their bytes as asked of hipMalloc.  Every array of a
+ * handle (scratch included) and every prepared B counts; a destroyed handle gives back exactly what it took.  Either pointer may be NULL. */
+int sparta_debug_device_allocs(int64_t* live_count, int64_t* live_bytes);
+
 int sparta_vbs_destroy(sparta_vbs_t* A);
 
 /* plan / roofline introspection. info_out (int64[16]):

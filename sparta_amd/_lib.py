@@ -59,6 +59,7 @@ SYMBOLS = [
     "sparta_vbs_set_forward_a8", "sparta_vbs_a8_info", "sparta_vbs_a8_get", "sparta_a8_quantize_group",
     "sparta_vbs_set_a8_live", "sparta_vbs_a8_live_info",
     "sparta_vbs_repattern_host", "sparta_vbs_move_blocks",
+    "sparta_debug_device_allocs",
 ]
 
 
@@ -183,6 +184,7 @@ def _load():
     L.sparta_vbs_live_forward_lists_get.argtypes = [vp, vp, i32p, C.POINTER(C.c_uint8), vp, i32p, vp]
     L.sparta_vbs_set_forward_a8.argtypes = [vp, C.c_int32, vp]
     L.sparta_vbs_a8_info.argtypes = [vp, i64p, vp]
+    L.sparta_debug_device_allocs.argtypes = [i64p, i64p]
     L.sparta_vbs_set_a8_live.argtypes = [vp, C.c_int32, vp]
     L.sparta_vbs_a8_live_info.argtypes = [vp, i64p, vp]
     L.sparta_vbs_a8_get.argtypes = [vp, C.POINTER(C.c_uint8), i32p, i32p, vp]

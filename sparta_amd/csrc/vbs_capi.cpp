@@ -8,6 +8,7 @@
 // family, no vendor BLAS/SPARSE call, no per-block launch.
 //
 #include <memory>
+#include <optional>
 
 #include <cmath>
 #include "vbs_kernel_common.hpp"
@@ -27,10 +28,9 @@ namespace {
 
 bool force_generic() { const char* e = std::getenv("SPARTA_FORCE_GENERIC"); return e && e[0] == '1'; }
 
-// set for the duration of a product call whose stream is being captured into a graph: anything that allocates, synchronises or times
-// (scratch growth, the first-call autotune, the gathered step lists) then fails with SPARTA_ERR_UNSUPPORTED instead of breaking the
+// CaptureScope sets g_capturing (vbs_device.hpp) for the duration of a call whose stream is being captured into a graph: anything that allocates,
+// synchronises or times (scratch growth, the first-call autotune, the gathered step lists) then fails with SPARTA_ERR_UNSUPPORTED instead of breaking the
 // capture -- run the same call once outside the capture first (same n_cols, layouts and shard_rows), after which the call is launches only
-thread_local bool g_capturing = false;
 struct CaptureScope {
     explicit CaptureScope(hipStream_t st, bool device_ptrs) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -38,135 +38,77 @@ struct CaptureScope {
     }
     ~CaptureScope() { g_capturing = false; }
 };
-int capture_refusal(const char* what, const char* entry = "sparta_vbs_spmm") {
-    return sparta::fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the stream is being captured and this call still has to " + what +
-                                                 " -- run it once outside the capture first");
-}
 
-int ensure_scratch(void** ptr, size_t* have, size_t need) {
-    if (*have >= need) return SPARTA_OK;
-    if (g_capturing) return capture_refusal("allocate scratch memory");
-    if (*ptr) { (void)hipFree(*ptr); *ptr = nullptr; *have = 0; }
-    HIP_TRY(hipMalloc(ptr, need));
-    *have = need;
+// ---- the scaffold of a device entry point, in one place: DeviceGuard, CaptureScope, the refusal of a captured call that asks for dt_ms, then ev0, the
+// launches, hipGetLastError, ev1 + synchronise + elapsed ----
+struct DeviceCall {
+    const char* entry;                          // the name the messages carry
+    int device;                                 // -1: a handle-free entry (no guard)
+    hipStream_t st;
+    bool device_ptrs;                           // false: host operands -- the call synchronises anyway and CaptureScope does not look at the stream
+    float* dt_ms = nullptr;                     // NULL: not timed
+    const char* timed_what = nullptr;           // "the step", "the product", ...: what a captured call is refused to time (NULL: the body refuses capture itself)
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;    // the handle's events; NULL: events made for this call (which synchronises anyway)
+    bool nothing_to_do = false;                 // no launches: the events only
+};
+// what dt_ms measures: launches(st) between the two events.  Staging of host operands and ensure_* calls stay in front of it, copies back behind it.
+template <class Launches>
+int timed_launches(const DeviceCall& c, Launches launches) {
+    DevEvent own0, own1;
+    hipEvent_t e0 = c.ev0, e1 = c.ev1;
+    if (c.dt_ms && !e0) {
+        HIP_TRY(own0.create());
+        HIP_TRY(own1.create());
+        e0 = own0; e1 = own1;
+    }
+    if (c.dt_ms) HIP_TRY(hipEventRecord(e0, c.st));
+    if (!c.nothing_to_do) {
+        launches(c.st);
+        HIP_TRY(hipGetLastError());
+    }
+    if (c.dt_ms) {
+        HIP_TRY(hipEventRecord(e1, c.st));
+        HIP_TRY(hipEventSynchronize(e1));
+        HIP_TRY(hipEventElapsedTime(c.dt_ms, e0, e1));
+    }
     return SPARTA_OK;
 }
+// guard, scope and refusal around body(st): a body that stages, builds lazily or reads back calls timed_launches itself (or launches untimed)
+template <class Body>
+int open_call(const DeviceCall& c, Body body) {
+    std::optional<DeviceGuard> guard;
+    if (c.device >= 0) {
+        guard.emplace(c.device);
+        if (!guard->ok) return sparta::fail(SPARTA_ERR_HIP, std::string(c.entry) + ": hipSetDevice failed");
+    }
+    const CaptureScope capture(c.st, c.device_ptrs);
+    if (g_capturing && c.dt_ms && c.timed_what) return capture_refusal((std::string("time ") + c.timed_what + " (dt_ms != NULL synchronises)").c_str(), c.entry);
+    return body(c.st);
+}
+// an entry that is launches only
+template <class Launches>
+int device_call(const DeviceCall& c, Launches launches) {
+    return open_call(c, [&](hipStream_t) { return timed_launches(c, launches); });
+}
 
+// the refusal of an entry that writes values into a handle made without SPARTA_CREATE_UPDATABLE
+int not_updatable(const char* entry) {
+    return sparta::fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the handle was not made with SPARTA_CREATE_UPDATABLE (sparta_vbs_create_range_ex; handles of "
+                                                                     "sparta_vbs_create_from_csr and sparta_vbs_create_transposed cannot take new values)");
+}
+
+// an environment switch that is on unless set to 0 (SPARTA_SGD_FUSE, SPARTA_ADAM_FUSE: read at every call, no plan depends on them)
+bool env_switch(const char* name) {
+    const char* e = std::getenv(name);
+    return !e || atoi(e) != 0;
+}
+
+// every device array and event of the handle is a member that frees itself, with the handle's device current
 void destroy_impl(sparta_vbs* v) {
     if (!v) return;
     DeviceGuard g(v->device);
-    if (v->d_A) (void)hipFree(v->d_A);
-    if (v->d_jab) (void)hipFree(v->d_jab);
-    for (int c = 0; c < 4; c++)
-        if (v->d_tiles[c]) (void)hipFree(v->d_tiles[c]);
-    if (v->d_brows) (void)hipFree(v->d_brows);
-    for (int ty = 0; ty < 2; ty++) {
-        if (v->d_steps[ty]) (void)hipFree(v->d_steps[ty]);
-        if (v->d_steps_g[ty]) (void)hipFree(v->d_steps_g[ty]);
-        if (v->d_wrange[ty]) (void)hipFree(v->d_wrange[ty]);
-    }
-    if (v->d_a_frag) (void)hipFree(v->d_a_frag);
-    if (v->d_a_pack) (void)hipFree(v->d_a_pack);
-    if (v->d_psteps) (void)hipFree(v->d_psteps);
-    if (v->d_pwrange) (void)hipFree(v->d_pwrange);
-    if (v->d_pack_loc) (void)hipFree(v->d_pack_loc);
-    if (v->d_hub_steps) (void)hipFree(v->d_hub_steps);
-    if (v->d_hub_steps_g) (void)hipFree(v->d_hub_steps_g);
-    if (v->d_hub_tiles) (void)hipFree(v->d_hub_tiles);
-    if (v->d_hub_wrange) (void)hipFree(v->d_hub_wrange);
-    if (v->d_hub_A) (void)hipFree(v->d_hub_A);
-    if (v->d_fix) (void)hipFree(v->d_fix);
-    if (v->d_fix_slots) (void)hipFree(v->d_fix_slots);
-    if (v->d_big_fix) (void)hipFree(v->d_big_fix);
-    if (v->d_ws) (void)hipFree(v->d_ws);
-    if (v->d_btail) (void)hipFree(v->d_btail);
-    if (v->d_tune) (void)hipFree(v->d_tune);
-    if (v->d_B16) (void)hipFree(v->d_B16);
-    if (v->d_Bt) (void)hipFree(v->d_Bt);
-    if (v->d_Ct) (void)hipFree(v->d_Ct);
-    if (v->d_clk) (void)hipFree(v->d_clk);
-    if (v->tev0) (void)hipEventDestroy(v->tev0);
-    if (v->tev1) (void)hipEventDestroy(v->tev1);
-    if (v->d_sp_rowptr) (void)hipFree(v->d_sp_rowptr);
-    if (v->d_sp_col) (void)hipFree(v->d_sp_col);
-    if (v->d_sp_val) (void)hipFree(v->d_sp_val);
-    if (v->d_sp_crow) (void)hipFree(v->d_sp_crow);
-    if (v->d_sp_list) (void)hipFree(v->d_sp_list);
-    if (v->d_sp_segs) (void)hipFree(v->d_sp_segs);
-    if (v->d_sp_stream_begin) (void)hipFree(v->d_sp_stream_begin);
-    if (v->d_sp_long) (void)hipFree(v->d_sp_long);
-    if (v->d_sp_part) (void)hipFree(v->d_sp_part);
-    if (v->d_cr_col) (void)hipFree(v->d_cr_col);
-    if (v->d_cr_val) (void)hipFree(v->d_cr_val);
-    if (v->d_cr_meta) (void)hipFree(v->d_cr_meta);
-    if (v->d_cr_parts) (void)hipFree(v->d_cr_parts);
-    if (v->d_cr_mode) (void)hipFree(v->d_cr_mode);
-    if (v->cr_small.col) (void)hipFree(v->cr_small.col);
-    if (v->cr_small.val) (void)hipFree(v->cr_small.val);
-    if (v->cr_small.meta) (void)hipFree(v->cr_small.meta);
-    if (v->cr_small.dest) (void)hipFree(v->cr_small.dest);
-    if (v->cr_small.longs) (void)hipFree(v->cr_small.longs);
-    if (v->cr_small.parts) (void)hipFree(v->cr_small.parts);
-    if (v->d_cr_dest) (void)hipFree(v->d_cr_dest);
-    if (v->d_cr_longs) (void)hipFree(v->d_cr_longs);
-    for (int ty = 0; ty < kUnionTypes; ty++) {
-        if (v->d_u_rec[ty]) (void)hipFree(v->d_u_rec[ty]);
-        if (v->d_u_ids[ty]) (void)hipFree(v->d_u_ids[ty]);
-        if (v->d_u_a[ty]) (void)hipFree(v->d_u_a[ty]);
-        if (v->d_u_wrange[ty]) (void)hipFree(v->d_u_wrange[ty]);
-        if (v->d_u_tail[ty]) (void)hipFree(v->d_u_tail[ty]);
-    }
-    if (v->d_Brm) (void)hipFree(v->d_Brm);
-    if (v->d_B) (void)hipFree(v->d_B);
-    if (v->d_C) (void)hipFree(v->d_C);
-    if (v->d_sd_items) (void)hipFree(v->d_sd_items);
-    if (v->d_sd_ws) (void)hipFree(v->d_sd_ws);
-    if (v->d_sd_h16) (void)hipFree(v->d_sd_h16);
-    for (int ty = 0; ty < 2; ty++)
-        if (v->d_upd_map[ty]) (void)hipFree(v->d_upd_map[ty]);
-    if (v->d_upd_hub) (void)hipFree(v->d_upd_hub);
-    if (v->d_upd_ws) (void)hipFree(v->d_upd_ws);
-    if (v->d_prune) (void)hipFree(v->d_prune);
-    if (v->d_repat) (void)hipFree(v->d_repat);
-    if (v->d_live_keep) (void)hipFree(v->d_live_keep);
-    if (v->d_live_goff) (void)hipFree(v->d_live_goff);
-    if (v->d_live_groups) (void)hipFree(v->d_live_groups);
-    if (v->d_live_gcount) (void)hipFree(v->d_live_gcount);
-    if (v->d_live_tmap) (void)hipFree(v->d_live_tmap);
-    if (v->d_live_tids) (void)hipFree(v->d_live_tids);
-    if (v->d_live_tcount) (void)hipFree(v->d_live_tcount);
-    if (v->d_live_t_blocks) (void)hipFree(v->d_live_t_blocks);
-    if (v->d_live_t_items) (void)hipFree(v->d_live_t_items);
-    if (v->d_score_keep) (void)hipFree(v->d_score_keep);
-    if (v->d_score_ones) (void)hipFree(v->d_score_ones);
-    if (v->d_score_groups) (void)hipFree(v->d_score_groups);
-    if (v->d_score_gcount) (void)hipFree(v->d_score_gcount);
-    if (v->d_score_soff) (void)hipFree(v->d_score_soff);
-    if (v->d_score_blocks) (void)hipFree(v->d_score_blocks);
-    if (v->d_score_slots) (void)hipFree(v->d_score_slots);
-    if (v->d_live_wmap) (void)hipFree(v->d_live_wmap);
-    if (v->d_live_words) (void)hipFree(v->d_live_words);
-    if (v->d_fwd_steps) (void)hipFree(v->d_fwd_steps);
-    if (v->d_fwd_wrange) (void)hipFree(v->d_fwd_wrange);
-    if (v->d_fwd_seg_last) (void)hipFree(v->d_fwd_seg_last);
-    if (v->d_a8) (void)hipFree(v->d_a8);
-    if (v->d_a8_steps) (void)hipFree(v->d_a8_steps);
-    if (v->d_t_items) (void)hipFree(v->d_t_items);
-    if (v->d_t_blocks) (void)hipFree(v->d_t_blocks);
-    if (v->d_t_A) (void)hipFree(v->d_t_A);
-    if (v->d_t_src) (void)hipFree(v->d_t_src);
-    if (v->d_t_ws) (void)hipFree(v->d_t_ws);
-    if (v->d_t_h16) (void)hipFree(v->d_t_h16);
-    if (v->ev0) (void)hipEventDestroy(v->ev0);
-    if (v->ev1) (void)hipEventDestroy(v->ev1);
-    for (int c = 0; c < 4; c++)
-        for (int e = 0; e < 2; e++)
-            if (v->cev[c][e]) (void)hipEventDestroy(v->cev[c][e]);
     delete v;
 }
-
-
-
 
 // ---- resident-column product (k_colres.hip): A as length-sorted slots, 64 to a slice -----------------------------------------------------------
 // Only for handles whose rows of C are ALL sparse rows (nothing for a tile launch to store first) and small enough that a column of B (and of C, with the
@@ -817,46 +759,37 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
     // A is padded by 128 floats so that no (masked-off) lane ever forms an address past the allocation
     if (!h16) {
         v->a_bytes = (nztot + 128) * (int64_t)sizeof(float);
-        CREATE_TRY(hipMalloc((void**)&v->d_A, (size_t)v->a_bytes));
-        CREATE_TRY(hipMemset(v->d_A, 0, (size_t)v->a_bytes));
-        if (nztot > 0) CREATE_TRY(hipMemcpy(v->d_A, mab + mab_lo, (size_t)nztot * sizeof(float), hipMemcpyHostToDevice));
+        CREATE_TRY(v->d_A.upload(nztot > 0 ? mab + mab_lo : nullptr, (size_t)nztot, 128));
     } else {
         // the look-ahead of the pipeline reads up to 5 slices past the last one (never multiplied): pad
         const std::vector<uint16_t>& a0 = plan.a16_steps[0];
         const std::vector<uint16_t>& a1 = plan.a16_steps[1];
         v->a_bytes = ((int64_t)a0.size() + (int64_t)a1.size() + 8 * 64 * 64) * (int64_t)sizeof(uint16_t);
-        CREATE_TRY(hipMalloc((void**)&v->d_A, (size_t)v->a_bytes));
+        CREATE_TRY(v->d_A.alloc(0, (size_t)v->a_bytes));
         CREATE_TRY(hipMemset(v->d_A, 0, (size_t)v->a_bytes));
         if (!a0.empty()) CREATE_TRY(hipMemcpy(v->d_A, a0.data(), a0.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        if (!a1.empty()) CREATE_TRY(hipMemcpy((uint16_t*)v->d_A + a0.size(), a1.data(), a1.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        if (!a1.empty()) CREATE_TRY(hipMemcpy((uint16_t*)v->d_A.get() + a0.size(), a1.data(), a1.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         v->kp16 = (int)kp;
         v->upd_base[1] = (int64_t)a0.size();
         for (int ty = 0; ty < 2 && updatable; ty++) {
             if (plan.upd_map[ty].empty()) continue;
             for (const UpdSlice& u : plan.upd_map[ty]) v->upd_cover[ty] += (int64_t)(u.rows_lo + u.rows_hi) * kp;
-            CREATE_TRY(hipMalloc((void**)&v->d_upd_map[ty], plan.upd_map[ty].size() * sizeof(UpdSlice)));
-            CREATE_TRY(hipMemcpy(v->d_upd_map[ty], plan.upd_map[ty].data(), plan.upd_map[ty].size() * sizeof(UpdSlice), hipMemcpyHostToDevice));
+            CREATE_TRY(v->d_upd_map[ty].upload(plan.upd_map[ty]));
         }
         if (updatable && !plan.upd_hub.empty()) {
             v->n_upd_hub = (int64_t)plan.upd_hub.size();
-            CREATE_TRY(hipMalloc((void**)&v->d_upd_hub, plan.upd_hub.size() * sizeof(UpdSlice)));
-            CREATE_TRY(hipMemcpy(v->d_upd_hub, plan.upd_hub.data(), plan.upd_hub.size() * sizeof(UpdSlice), hipMemcpyHostToDevice));
+            CREATE_TRY(v->d_upd_hub.upload(plan.upd_hub));
         }
     }
-    CREATE_TRY(hipMalloc((void**)&v->d_jab, jab32.size() * sizeof(int32_t)));
-    CREATE_TRY(hipMemcpy(v->d_jab, jab32.data(), jab32.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    CREATE_TRY(v->d_jab.upload(jab32));
     for (int c = 0; c < 4; c++) {
         v->n_tiles[c] = (int64_t)tiles[c].size();
         v->n_real_tiles[c] = n_real[c];
         if (tiles[c].empty()) continue;
-        CREATE_TRY(hipMalloc((void**)&v->d_tiles[c], tiles[c].size() * sizeof(TileDesc)));
-        CREATE_TRY(hipMemcpy(v->d_tiles[c], tiles[c].data(), tiles[c].size() * sizeof(TileDesc), hipMemcpyHostToDevice));
+        CREATE_TRY(v->d_tiles[c].upload(tiles[c]));
     }
     v->n_brows = (int64_t)brows.size();
-    if (!brows.empty()) {
-        CREATE_TRY(hipMalloc((void**)&v->d_brows, brows.size() * sizeof(BlockRowDesc)));
-        CREATE_TRY(hipMemcpy(v->d_brows, brows.data(), brows.size() * sizeof(BlockRowDesc), hipMemcpyHostToDevice));
-    }
+    if (!brows.empty()) CREATE_TRY(v->d_brows.upload(brows));
     if (!steps[0].empty() || !steps[1].empty() || !fix.empty() || !plan.zero_ranges.empty() || plan.n_hub_steps > 0) {
         v->has_tail = (cols % w) != 0;
         v->n_workers = n_workers; v->n_fix = (int32_t)fix.size(); v->n_split = n_split; v->n_slots = (int32_t)fix_slots.size();
@@ -866,10 +799,7 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
             if (fix[q].n_slots > 2 * kFixGroup) big_fix.push_back((int32_t)q);
         }
         v->n_big_fix = (int32_t)big_fix.size();
-        if (!big_fix.empty()) {
-            CREATE_TRY(hipMalloc((void**)&v->d_big_fix, big_fix.size() * sizeof(int32_t)));
-            CREATE_TRY(hipMemcpy(v->d_big_fix, big_fix.data(), big_fix.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
+        if (!big_fix.empty()) CREATE_TRY(v->d_big_fix.upload(big_fix));
         for (int ty = 0; ty < 2; ty++) {
             std::vector<StepRec>& st = steps[ty];
             v->n_steps[ty] = (int64_t)st.size();
@@ -877,24 +807,21 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
             if (updatable && !h16) for (const StepRec& r : st) v->upd_cover[ty] += (int64_t)(r.mt_flags & 0xffff) * SK_KP;
             // the pipeline prefetches up to 5 steps (and up to two 8-record batches) past a range end: pad with harmless copies
             for (int k = 0; k < 32; k++) { StepRec d = st[(size_t)v->n_steps[ty] - 1]; d.mt_flags = (d.mt_flags & ~(STEP_LAST | STEP_SPLIT)) | STEP_FIRST; st.push_back(d); }
-            CREATE_TRY(hipMalloc((void**)&v->d_steps[ty], st.size() * sizeof(StepRec)));
-            CREATE_TRY(hipMemcpy(v->d_steps[ty], st.data(), st.size() * sizeof(StepRec), hipMemcpyHostToDevice));
+            CREATE_TRY(v->d_steps[ty].upload(st));
             v->h_steps[ty] = st;
             v->n_plan_tiles[ty] = plan.n_plan_tiles[ty];
             v->tiles_row_aligned[ty] = plan.tiles_row_aligned[ty];
             if (ty == 0) v->wide16 = plan.wide16;
-            CREATE_TRY(hipMalloc((void**)&v->d_wrange[ty], wrange[ty].size() * sizeof(int32_t)));
-            CREATE_TRY(hipMemcpy(v->d_wrange[ty], wrange[ty].data(), wrange[ty].size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            CREATE_TRY(v->d_wrange[ty].upload(wrange[ty]));
         }
         if (!plan.a_frag.empty()) {
             // a SECOND copy of the one-tile part of A (4 KB per step whatever the tile height): if the device cannot hold it the handle is still
             // good -- d_a_frag stays null and the launch code runs the LDS-staged kernel on the legacy image (launch_f32_stream)
-            if (hipMalloc((void**)&v->d_a_frag, plan.a_frag.size() * sizeof(float)) == hipSuccess) {
+            if (v->d_a_frag.alloc(plan.a_frag.size()) == hipSuccess) {
                 CREATE_TRY(hipMemcpy(v->d_a_frag, plan.a_frag.data(), plan.a_frag.size() * sizeof(float), hipMemcpyHostToDevice));
                 v->a_bytes += (int64_t)(plan.a_frag.size() * sizeof(float));    // the device image holds the one-tile part of A twice (two layouts)
             } else {
                 (void)hipGetLastError();
-                v->d_a_frag = nullptr;
             }
         }
         if (!plan.a_pack.empty()) {
@@ -903,58 +830,43 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
             std::vector<StepRec>& ps = plan.psteps;
             v->n_psteps = (int64_t)ps.size(); v->pack_slots = plan.pack_slots;
             for (int k = 0; k < 32; k++) { StepRec d = ps[(size_t)v->n_psteps - 1]; d.mt_flags = (d.mt_flags & ~(STEP_LAST | STEP_SPLIT)) | STEP_FIRST; ps.push_back(d); }
-            if (hipMalloc((void**)&v->d_a_pack, plan.a_pack.size() * sizeof(float)) == hipSuccess) {
+            if (v->d_a_pack.alloc(plan.a_pack.size()) == hipSuccess) {
                 CREATE_TRY(hipMemcpy(v->d_a_pack, plan.a_pack.data(), plan.a_pack.size() * sizeof(float), hipMemcpyHostToDevice));
                 v->a_bytes += (int64_t)(plan.a_pack.size() * sizeof(float));
-                CREATE_TRY(hipMalloc((void**)&v->d_psteps, ps.size() * sizeof(StepRec)));
-                CREATE_TRY(hipMemcpy(v->d_psteps, ps.data(), ps.size() * sizeof(StepRec), hipMemcpyHostToDevice));
-                CREATE_TRY(hipMalloc((void**)&v->d_pwrange, plan.pwrange.size() * sizeof(int32_t)));
-                CREATE_TRY(hipMemcpy(v->d_pwrange, plan.pwrange.data(), plan.pwrange.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-                CREATE_TRY(hipMalloc((void**)&v->d_pack_loc, plan.pack_loc.size() * sizeof(PackLoc)));
-                CREATE_TRY(hipMemcpy(v->d_pack_loc, plan.pack_loc.data(), plan.pack_loc.size() * sizeof(PackLoc), hipMemcpyHostToDevice));
+                CREATE_TRY(v->d_psteps.upload(ps));
+                CREATE_TRY(v->d_pwrange.upload(plan.pwrange));
+                CREATE_TRY(v->d_pack_loc.upload(plan.pack_loc));
             } else {
                 (void)hipGetLastError();
-                v->d_a_pack = nullptr; v->n_psteps = 0; v->pack_slots = 0;
+                v->n_psteps = 0; v->pack_slots = 0;
             }
         }
         if (plan.n_hub_steps > 0) {
             v->hub_g = plan.hub_g; v->hub_workers = plan.hub_workers; v->n_hub_steps = plan.n_hub_steps; v->hub_area = plan.hub_area;
             v->hub_union_area = plan.hub_union_area; v->n_hub_tiles = plan.n_hub_tiles; v->n_hub_groups = plan.n_hub_groups;
             v->hub_chunks = plan.hub_chunks; v->hub_segments = plan.hub_segments;
-            CREATE_TRY(hipMalloc((void**)&v->d_hub_steps, plan.hub_steps.size() * sizeof(HubStep)));
-            CREATE_TRY(hipMemcpy(v->d_hub_steps, plan.hub_steps.data(), plan.hub_steps.size() * sizeof(HubStep), hipMemcpyHostToDevice));
-            CREATE_TRY(hipMalloc((void**)&v->d_hub_tiles, plan.hub_tiles.size() * sizeof(HubTile)));
-            CREATE_TRY(hipMemcpy(v->d_hub_tiles, plan.hub_tiles.data(), plan.hub_tiles.size() * sizeof(HubTile), hipMemcpyHostToDevice));
-            CREATE_TRY(hipMalloc((void**)&v->d_hub_wrange, plan.hub_wrange.size() * sizeof(int32_t)));
-            CREATE_TRY(hipMemcpy(v->d_hub_wrange, plan.hub_wrange.data(), plan.hub_wrange.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            CREATE_TRY(v->d_hub_steps.upload(plan.hub_steps));
+            CREATE_TRY(v->d_hub_tiles.upload(plan.hub_tiles));
+            CREATE_TRY(v->d_hub_wrange.upload(plan.hub_wrange));
             const size_t a_elems = plan.hub_a16_elems;
-            CREATE_TRY(hipMalloc((void**)&v->d_hub_A, (a_elems + 64) * sizeof(uint16_t)));
-            if (a_elems > 0) CREATE_TRY(hipMemcpy(v->d_hub_A, plan.hub_a16.get(), a_elems * sizeof(uint16_t), hipMemcpyHostToDevice));
+            CREATE_TRY(v->d_hub_A.upload(plan.hub_a16.get(), a_elems, 64));
             v->a_bytes += (int64_t)(a_elems * sizeof(uint16_t));
             v->exec_area += plan.hub_union_area;
             v->h_hub_steps.swap(plan.hub_steps);
         }
-        if (!fix.empty()) {
-            CREATE_TRY(hipMalloc((void**)&v->d_fix, fix.size() * sizeof(FixRec)));
-            CREATE_TRY(hipMemcpy(v->d_fix, fix.data(), fix.size() * sizeof(FixRec), hipMemcpyHostToDevice));
-        }
-        CREATE_TRY(hipMalloc((void**)&v->d_fix_slots, std::max<size_t>(fix_slots.size(), 1) * sizeof(int32_t)));
+        if (!fix.empty()) CREATE_TRY(v->d_fix.upload(fix));
+        CREATE_TRY(v->d_fix_slots.alloc(std::max<size_t>(fix_slots.size(), 1)));
         if (!fix_slots.empty()) CREATE_TRY(hipMemcpy(v->d_fix_slots, fix_slots.data(), fix_slots.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     for (int ty = 0; ty < kUnionTypes; ty++) {
         if (uplan.n_steps[ty] == 0) continue;
         v->u_workers[ty] = uplan.n_workers[ty]; v->u_steps[ty] = uplan.n_steps[ty]; v->u_tiles[ty] = uplan.n_tiles[ty]; v->u_steps_total += uplan.n_steps[ty];
-        CREATE_TRY(hipMalloc((void**)&v->d_u_rec[ty], uplan.rec[ty].size() * sizeof(UnionRec)));
-        CREATE_TRY(hipMemcpy(v->d_u_rec[ty], uplan.rec[ty].data(), uplan.rec[ty].size() * sizeof(UnionRec), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMalloc((void**)&v->d_u_ids[ty], uplan.ids[ty].size() * sizeof(int32_t)));
-        CREATE_TRY(hipMemcpy(v->d_u_ids[ty], uplan.ids[ty].data(), uplan.ids[ty].size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        CREATE_TRY(v->d_u_rec[ty].upload(uplan.rec[ty]));
+        CREATE_TRY(v->d_u_ids[ty].upload(uplan.ids[ty]));
         const size_t a_bytes_ty = h16 ? uplan.a16[ty].size() * sizeof(uint16_t) : uplan.a[ty].size() * sizeof(float);
-        CREATE_TRY(hipMalloc((void**)&v->d_u_a[ty], a_bytes_ty));
-        CREATE_TRY(hipMemcpy(v->d_u_a[ty], h16 ? (const void*)uplan.a16[ty].data() : (const void*)uplan.a[ty].data(), a_bytes_ty, hipMemcpyHostToDevice));
-        CREATE_TRY(hipMalloc((void**)&v->d_u_wrange[ty], uplan.wrange[ty].size() * sizeof(int32_t)));
-        CREATE_TRY(hipMemcpy(v->d_u_wrange[ty], uplan.wrange[ty].data(), uplan.wrange[ty].size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMalloc(&v->d_u_tail[ty], uplan.tail[ty].size() * sizeof(uint32_t)));
-        CREATE_TRY(hipMemcpy(v->d_u_tail[ty], uplan.tail[ty].data(), uplan.tail[ty].size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        CREATE_TRY(v->d_u_a[ty].upload(h16 ? (const uint8_t*)uplan.a16[ty].data() : (const uint8_t*)uplan.a[ty].data(), a_bytes_ty));
+        CREATE_TRY(v->d_u_wrange[ty].upload(uplan.wrange[ty]));
+        CREATE_TRY(v->d_u_tail[ty].upload(uplan.tail[ty]));
         v->a_bytes += (int64_t)(a_bytes_ty + uplan.ids[ty].size() * sizeof(int32_t) + uplan.tail[ty].size() * sizeof(uint32_t));
         v->exec_area += uplan.n_steps[ty] * 32 * uplan.type_rows[ty];
         v->u_exec_area += uplan.n_steps[ty] * 32 * uplan.type_rows[ty];
@@ -965,57 +877,32 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
     }
     if (!sp_crow.empty()) {
         v->n_sp_rows = (int64_t)sp_crow.size(); v->n_sp_short = n_sp_short; v->n_sp_long = n_sp_long; v->sp_nnz = sp_rowptr.back();
-        CREATE_TRY(hipMalloc((void**)&v->d_sp_rowptr, sp_rowptr.size() * sizeof(int64_t)));
-        CREATE_TRY(hipMemcpy(v->d_sp_rowptr, sp_rowptr.data(), sp_rowptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMalloc((void**)&v->d_sp_col, (sp_col.size() + 64) * sizeof(int32_t)));      // +64: a batch reads up to SP_BATCH entries at once
-        CREATE_TRY(hipMemset(v->d_sp_col, 0, (sp_col.size() + 64) * sizeof(int32_t)));
-        CREATE_TRY(hipMalloc((void**)&v->d_sp_val, (sp_val.size() + 64) * sizeof(float)));
-        CREATE_TRY(hipMemset(v->d_sp_val, 0, (sp_val.size() + 64) * sizeof(float)));
-        if (!sp_col.empty()) {
-            CREATE_TRY(hipMemcpy(v->d_sp_col, sp_col.data(), sp_col.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            CREATE_TRY(hipMemcpy(v->d_sp_val, sp_val.data(), sp_val.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
-        CREATE_TRY(hipMalloc((void**)&v->d_sp_crow, sp_crow.size() * sizeof(int32_t)));
-        CREATE_TRY(hipMemcpy(v->d_sp_crow, sp_crow.data(), sp_crow.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        if (!sp_list.empty()) {
-            CREATE_TRY(hipMalloc((void**)&v->d_sp_list, sp_list.size() * sizeof(int32_t)));
-            CREATE_TRY(hipMemcpy(v->d_sp_list, sp_list.data(), sp_list.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
+        CREATE_TRY(v->d_sp_rowptr.upload(sp_rowptr));
+        CREATE_TRY(v->d_sp_col.upload(sp_col, 64));      // +64: a batch reads up to SP_BATCH entries at once
+        CREATE_TRY(v->d_sp_val.upload(sp_val, 64));
+        CREATE_TRY(v->d_sp_crow.upload(sp_crow));
+        if (!sp_list.empty()) CREATE_TRY(v->d_sp_list.upload(sp_list));
         if (!sp_long.empty()) {
             v->n_sp_segs = (int64_t)sp_segs.size();
-            CREATE_TRY(hipMalloc(&v->d_sp_segs, sp_segs.size() * sizeof(SpSegRec)));
-            CREATE_TRY(hipMemcpy(v->d_sp_segs, sp_segs.data(), sp_segs.size() * sizeof(SpSegRec), hipMemcpyHostToDevice));
+            CREATE_TRY(v->d_sp_segs.upload(sp_segs));
             if (!sp_stream_begin.empty()) {
-                CREATE_TRY(hipMalloc((void**)&v->d_sp_stream_begin, 9 * sizeof(int32_t)));
-                CREATE_TRY(hipMemcpy(v->d_sp_stream_begin, sp_stream_begin.data(), 9 * sizeof(int32_t), hipMemcpyHostToDevice));
+                CREATE_TRY(v->d_sp_stream_begin.upload(sp_stream_begin.data(), 9));
                 for (int x = 0; x < 8; x++) v->sp_max_stream = std::max<int64_t>(v->sp_max_stream, sp_stream_begin[(size_t)x + 1] - sp_stream_begin[(size_t)x]);
             }
-            CREATE_TRY(hipMalloc(&v->d_sp_long, sp_long.size() * sizeof(SpLongRec)));
-            CREATE_TRY(hipMemcpy(v->d_sp_long, sp_long.data(), sp_long.size() * sizeof(SpLongRec), hipMemcpyHostToDevice));
+            CREATE_TRY(v->d_sp_long.upload(sp_long));
         }
     }
     // resident-column image (k_colres.hip): at least half the rows of C are sparse rows (the tile launches, if any, come first on the stream), a column of B fits LDS
     if (!h16 && !sp_crow.empty()) {
         ColresHost H;
         if (build_colres(v->rows, cols, sp_rowptr, sp_col, sp_val, sp_crow, H)) {
-            CREATE_TRY(hipMalloc(&v->d_cr_col, H.col.size() * sizeof(uint16_t)));
-            CREATE_TRY(hipMemcpy(v->d_cr_col, H.col.data(), H.col.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-            if (!H.val.empty()) {
-                CREATE_TRY(hipMalloc(&v->d_cr_val, H.val.size() * sizeof(float)));
-                CREATE_TRY(hipMemcpy(v->d_cr_val, H.val.data(), H.val.size() * sizeof(float), hipMemcpyHostToDevice));
-            }
-            CREATE_TRY(hipMalloc((void**)&v->d_cr_meta, H.meta.size() * sizeof(int32_t)));
-            CREATE_TRY(hipMemcpy(v->d_cr_meta, H.meta.data(), H.meta.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            CREATE_TRY(hipMalloc(&v->d_cr_mode, H.mode.size()));
-            CREATE_TRY(hipMemcpy(v->d_cr_mode, H.mode.data(), H.mode.size(), hipMemcpyHostToDevice));
-            CREATE_TRY(hipMalloc(&v->d_cr_parts, H.parts.size() * sizeof(ColresPartDev)));
-            CREATE_TRY(hipMemcpy(v->d_cr_parts, H.parts.data(), H.parts.size() * sizeof(ColresPartDev), hipMemcpyHostToDevice));
-            CREATE_TRY(hipMalloc((void**)&v->d_cr_dest, H.dest.size() * sizeof(int32_t)));
-            CREATE_TRY(hipMemcpy(v->d_cr_dest, H.dest.data(), H.dest.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            if (!H.longs.empty()) {
-                CREATE_TRY(hipMalloc(&v->d_cr_longs, H.longs.size() * sizeof(ColresLong)));
-                CREATE_TRY(hipMemcpy(v->d_cr_longs, H.longs.data(), H.longs.size() * sizeof(ColresLong), hipMemcpyHostToDevice));
-            }
+            CREATE_TRY(v->d_cr_col.upload(H.col));
+            if (!H.val.empty()) CREATE_TRY(v->d_cr_val.upload(H.val));
+            CREATE_TRY(v->d_cr_meta.upload(H.meta));
+            CREATE_TRY(v->d_cr_mode.upload(H.mode));
+            CREATE_TRY(v->d_cr_parts.upload(H.parts));
+            CREATE_TRY(v->d_cr_dest.upload(H.dest));
+            if (!H.longs.empty()) CREATE_TRY(v->d_cr_longs.upload(H.longs));
             v->cr_slices = H.max_slices; v->cr_long = (int32_t)H.longs.size(); v->cr_plane = H.max_cells; v->cr_lmax = H.lmax;
             v->cr_parts = (int32_t)H.parts.size(); v->cr_ranges = (int32_t)H.krange.size() - 1;
             for (size_t r = 0; r < H.krange.size(); r++) v->cr_krange[r] = H.krange[r];
@@ -1028,22 +915,12 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
                 ColresHost S;
                 if (build_colres(v->rows, cols, sp_rowptr, sp_col, sp_val, sp_crow, S, 4) && S.val.empty() == H.val.empty()) {
                     auto& cs = v->cr_small;
-                    CREATE_TRY(hipMalloc(&cs.col, S.col.size() * sizeof(uint16_t)));
-                    CREATE_TRY(hipMemcpy(cs.col, S.col.data(), S.col.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-                    if (!S.val.empty()) {
-                        CREATE_TRY(hipMalloc(&cs.val, S.val.size() * sizeof(float)));
-                        CREATE_TRY(hipMemcpy(cs.val, S.val.data(), S.val.size() * sizeof(float), hipMemcpyHostToDevice));
-                    }
-                    CREATE_TRY(hipMalloc((void**)&cs.meta, S.meta.size() * sizeof(int32_t)));
-                    CREATE_TRY(hipMemcpy(cs.meta, S.meta.data(), S.meta.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-                    CREATE_TRY(hipMalloc((void**)&cs.dest, S.dest.size() * sizeof(int32_t)));
-                    CREATE_TRY(hipMemcpy(cs.dest, S.dest.data(), S.dest.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-                    if (!S.longs.empty()) {
-                        CREATE_TRY(hipMalloc(&cs.longs, S.longs.size() * sizeof(ColresLong)));
-                        CREATE_TRY(hipMemcpy(cs.longs, S.longs.data(), S.longs.size() * sizeof(ColresLong), hipMemcpyHostToDevice));
-                    }
-                    CREATE_TRY(hipMalloc(&cs.parts, S.parts.size() * sizeof(ColresPartDev)));
-                    CREATE_TRY(hipMemcpy(cs.parts, S.parts.data(), S.parts.size() * sizeof(ColresPartDev), hipMemcpyHostToDevice));
+                    CREATE_TRY(cs.col.upload(S.col));
+                    if (!S.val.empty()) CREATE_TRY(cs.val.upload(S.val));
+                    CREATE_TRY(cs.meta.upload(S.meta));
+                    CREATE_TRY(cs.dest.upload(S.dest));
+                    if (!S.longs.empty()) CREATE_TRY(cs.longs.upload(S.longs));
+                    CREATE_TRY(cs.parts.upload(S.parts));
                     cs.slices = S.max_slices; cs.plane = S.max_cells; cs.n_parts = (int32_t)S.parts.size();
                     v->a_bytes += (int64_t)(S.col.size() * sizeof(uint16_t) + S.val.size() * sizeof(float));
                 }
@@ -1056,31 +933,25 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
         if (int rc = build_spmm_t_index(cols, w, br0, br1, row_part, nzcount, jab, jab_lo, h16, T)) return rc;
         v->n_t_items = (int64_t)T.items.size();
         v->n_t_blocks = (int64_t)T.blocks.size();
-        CREATE_TRY(hipMalloc((void**)&v->d_t_items, T.items.size() * sizeof(SpmmTItem)));
-        CREATE_TRY(hipMemcpy(v->d_t_items, T.items.data(), T.items.size() * sizeof(SpmmTItem), hipMemcpyHostToDevice));
-        if (!T.blocks.empty()) {
-            CREATE_TRY(hipMalloc((void**)&v->d_t_blocks, T.blocks.size() * sizeof(SpmmTBlock)));
-            CREATE_TRY(hipMemcpy(v->d_t_blocks, T.blocks.data(), T.blocks.size() * sizeof(SpmmTBlock), hipMemcpyHostToDevice));
-        }
+        CREATE_TRY(v->d_t_items.upload(T.items));
+        if (!T.blocks.empty()) CREATE_TRY(v->d_t_blocks.upload(T.blocks));
         if (h16 && T.image_elems > 0) {
             std::unique_ptr<uint16_t[]> img(new uint16_t[(size_t)T.image_elems]);
             sparta::parallel_for_dynamic((int64_t)T.src.size(), 64, [&](int64_t lo, int64_t hi, int) {
                 for (int64_t q = lo; q < hi; q++) pack_spmm_t_block(mab + mab_lo + T.src[(size_t)q].src, T.src[(size_t)q].h, w, bf16h, img.get() + T.src[(size_t)q].dst);
             });
-            CREATE_TRY(hipMalloc((void**)&v->d_t_A, (size_t)T.image_elems * sizeof(uint16_t)));
-            CREATE_TRY(hipMemcpy(v->d_t_A, img.get(), (size_t)T.image_elems * sizeof(uint16_t), hipMemcpyHostToDevice));
+            CREATE_TRY(v->d_t_A.upload(img.get(), (size_t)T.image_elems));
             v->a_bytes += T.image_elems * (int64_t)sizeof(uint16_t);
             if (updatable) {
                 v->n_t_src = (int64_t)T.src.size();
-                CREATE_TRY(hipMalloc((void**)&v->d_t_src, T.src.size() * sizeof(SpmmTSrc)));
-                CREATE_TRY(hipMemcpy(v->d_t_src, T.src.data(), T.src.size() * sizeof(SpmmTSrc), hipMemcpyHostToDevice));
+                CREATE_TRY(v->d_t_src.upload(T.src));
             }
         }
     }
-    CREATE_TRY(hipEventCreate(&v->ev0));
-    CREATE_TRY(hipEventCreate(&v->ev1));
-    CREATE_TRY(hipEventCreate(&v->tev0));
-    CREATE_TRY(hipEventCreate(&v->tev1));
+    CREATE_TRY(v->ev0.create());
+    CREATE_TRY(v->ev1.create());
+    CREATE_TRY(v->tev0.create());
+    CREATE_TRY(v->tev1.create());
 #undef CREATE_TRY
     trace.lap("upload");
     *out = hold.release();
@@ -1444,6 +1315,12 @@ int sparta_debug_timeline(sparta_vbs_t* A, long long* out) {
 }
 #endif
 
+int sparta_debug_device_allocs(int64_t* live_count, int64_t* live_bytes) {
+    if (live_count) *live_count = g_dev_live_count.load();
+    if (live_bytes) *live_bytes = g_dev_live_bytes.load();
+    return SPARTA_OK;
+}
+
 int sparta_vbs_clock_mhz(sparta_vbs_t* A, double* mhz_out) {
     using sparta::fail;
     if (!A || !mhz_out) return fail(SPARTA_ERR_INVALID, "sparta_vbs_clock_mhz: NULL argument");
@@ -1499,14 +1376,14 @@ int ensure_gathered_steps(sparta_vbs_t* A, int64_t shard_rows, hipStream_t st) {
         if (A->h_steps[ty].empty()) continue;
         std::vector<StepRec> g = A->h_steps[ty];
         for (StepRec& r : g) { r.pad = (int32_t)(r.b_row / shard_rows); r.b_row = (int32_t)(r.b_row % shard_rows); }
-        if (!A->d_steps_g[ty]) HIP_TRY(hipMalloc((void**)&A->d_steps_g[ty], g.size() * sizeof(StepRec)));
+        if (!A->d_steps_g[ty]) HIP_TRY(A->d_steps_g[ty].alloc(g.size()));
         HIP_TRY(hipMemcpyAsync(A->d_steps_g[ty], g.data(), g.size() * sizeof(StepRec), hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));                       // g goes out of scope
     }
     if (!A->h_hub_steps.empty()) {
         std::vector<HubStep> g = A->h_hub_steps;
         for (HubStep& r : g) if (!(r.flags & STEP_TAIL)) { r.shard = (int32_t)(r.b_row / shard_rows); r.b_row = (int32_t)(r.b_row % shard_rows); }
-        if (!A->d_hub_steps_g) HIP_TRY(hipMalloc((void**)&A->d_hub_steps_g, g.size() * sizeof(HubStep)));
+        if (!A->d_hub_steps_g) HIP_TRY(A->d_hub_steps_g.alloc(g.size()));
         HIP_TRY(hipMemcpyAsync(A->d_hub_steps_g, g.data(), g.size() * sizeof(HubStep), hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
@@ -1522,7 +1399,7 @@ int ensure_legacy_image(sparta_vbs_t* A, hipStream_t st) {
     if (A->d_A || A->dtype != SPARTA_F32) return SPARTA_OK;
     if (g_capturing) return capture_refusal("rebuild the reference-layout image of A");
     const size_t bytes = (size_t)(A->nztot + 128) * sizeof(float);
-    HIP_TRY(hipMalloc((void**)&A->d_A, bytes));
+    HIP_TRY(A->d_A.alloc((size_t)A->nztot + 128));
     HIP_TRY(hipMemsetAsync(A->d_A, 0, bytes, st));
     if (A->n_steps[0] > 0 && A->d_a_pack) launch_f32_legacy_from_pack(st, A->d_steps[0], A->d_pack_loc, A->n_steps[0], A->d_a_pack, A->d_A);
     else if (A->n_steps[0] > 0) launch_f32_legacy_from_frag(st, A->d_steps[0], A->n_steps[0], A->d_a_frag, A->d_A);
@@ -1534,8 +1411,7 @@ void drop_legacy_image(sparta_vbs_t* A) {
     static const bool keep = [] { const char* e = std::getenv("SPARTA_F32_KEEP_LEGACY"); return e && atoi(e) != 0; }();
     if (A->create_flags & SPARTA_CREATE_TRANSPOSE) return;      // sparta_vbs_spmm_t reads the reference-layout image
     if (keep || g_capturing || A->legacy_dropped || !A->d_A || !(A->d_a_frag || A->d_a_pack) || A->dtype != SPARTA_F32 || A->n_steps[1] != 0 || A->n_sp_rows != 0 || A->class_timing) return;
-    (void)hipFree(A->d_A);                               // (synchronises: the autotune's launches that read it are done)
-    A->d_A = nullptr;
+    A->d_A.reset();                                      // (synchronises: the autotune's launches that read it are done)
     A->a_bytes -= (int64_t)((A->nztot + 128) * sizeof(float));
     A->legacy_dropped = true;
 }
@@ -1550,9 +1426,9 @@ int ensure_brm(sparta_vbs_t* A, const void* dB, int64_t ldb, bool b_row_major, i
     const int64_t per16 = 16 / (int64_t)esz;
     if (b_row_major && shard_rows == 0 && (!aligned16 || (ldb % per16 == 0 && ((uintptr_t)dB % 16) == 0))) { A->brm_ready = dB; A->brm_ld = ldb; return SPARTA_OK; }
     if (A->prepared_brm && !b_row_major) { A->brm_ready = A->prepared_brm; A->brm_ld = A->prepared_ld; return SPARTA_OK; }
-    if (g_capturing && A->d_Brm_bytes < (size_t)A->cols * (size_t)((n_cols + per16 - 1) / per16 * per16) * esz) return capture_refusal("allocate the row-major copy of B");
+    if (g_capturing && A->d_Brm.bytes() < (size_t)A->cols * (size_t)((n_cols + per16 - 1) / per16 * per16) * esz) return capture_refusal("allocate the row-major copy of B");
     const int64_t ld = (n_cols + per16 - 1) / per16 * per16;
-    if (int rc = ensure_scratch(&A->d_Brm, &A->d_Brm_bytes, (size_t)A->cols * (size_t)ld * esz)) return rc;
+    if (int rc = A->d_Brm.ensure((size_t)A->cols * (size_t)ld * esz)) return rc;
     if (b_row_major) {                                   // (a row-major B whose rows are not 16-byte aligned: an aligned copy)
         HIP_TRY(hipMemcpy2DAsync(A->d_Brm, (size_t)ld * esz, dB, (size_t)ldb * esz, (size_t)n_cols * esz, (size_t)A->cols, hipMemcpyDeviceToDevice, st));
     } else {
@@ -1580,7 +1456,7 @@ int launch_union_tiles(sparta_vbs_t* A, const void* dB, int64_t ldb, bool b_row_
     up.pad = [] { const char* e = std::getenv("SPARTA_UNION_PROBE"); return e ? atoi(e) : 0; }();      // developer probes (timing only, wrong products; read per call)
     for (int ty = 0; ty < kUnionTypes; ty++) {
         UnionSide& sd = up.side[ty];
-        sd.rec = A->d_u_rec[ty]; sd.ids = A->d_u_ids[ty]; sd.A = A->d_u_a[ty]; sd.worker_range = A->d_u_wrange[ty]; sd.tail = (const uint2*)A->d_u_tail[ty];
+        sd.rec = A->d_u_rec[ty]; sd.ids = A->d_u_ids[ty]; sd.A = A->d_u_a[ty]; sd.worker_range = A->d_u_wrange[ty]; sd.tail = (const uint2*)A->d_u_tail[ty].get();
         sd.n_workers = A->u_steps[ty] > 0 ? A->u_workers[ty] : 0;
         // C is written once and never read back: non-temporal stores where tiles are long (as the stream kernels: vbs_kernel_common.hpp); SPARTA_C_NT=0|1 forces one
         const char* e = std::getenv("SPARTA_C_NT");
@@ -1604,7 +1480,7 @@ int launch_sparse_rows(sparta_vbs_t* A, const void* dB, int64_t ldb, bool b_row_
             int nc_used = nc;
             bool used_small = false;
             ColresParams cp;
-            cp.col4 = (const uint2*)A->d_cr_col; cp.val4 = (const float4*)A->d_cr_val; cp.parts = (const ColresPartDev*)A->d_cr_parts; cp.meta = A->d_cr_meta;
+            cp.col4 = (const uint2*)A->d_cr_col.get(); cp.val4 = (const float4*)A->d_cr_val.get(); cp.parts = A->d_cr_parts; cp.meta = A->d_cr_meta;
             cp.dest = A->d_cr_dest; cp.longs = (const ColresLong*)A->d_cr_longs; cp.mode = (const uint8_t*)A->d_cr_mode;
             cp.B = (const float*)dB; cp.ldb = ldb; cp.C = dC; cp.ldc = ldc;
             for (int r = 0; r <= kColresMaxRanges; r++) cp.krange[r] = A->cr_krange[r];
@@ -1622,7 +1498,7 @@ int launch_sparse_rows(sparta_vbs_t* A, const void* dB, int64_t ldb, bool b_row_
                 for (int c = 1; c <= fit && ncs == 0; c++) if ((int64_t)((n_cols + c - 1) / c) * A->cr_small.n_parts <= 256 && A->cr_small.slices <= colres_max_slices(c)) ncs = c;
                 if (ncs > 0 && !en && !(es && atoi(es) == 0)) {
                     nc_used = ncs; used_small = true;
-                    cp.col4 = (const uint2*)A->cr_small.col; cp.val4 = (const float4*)A->cr_small.val; cp.parts = (const ColresPartDev*)A->cr_small.parts; cp.meta = A->cr_small.meta;
+                    cp.col4 = (const uint2*)A->cr_small.col.get(); cp.val4 = (const float4*)A->cr_small.val.get(); cp.parts = A->cr_small.parts; cp.meta = A->cr_small.meta;
                     cp.dest = A->cr_small.dest; cp.longs = (const ColresLong*)A->cr_small.longs;
                     cp.n_parts = A->cr_small.n_parts;
                     lds_bytes = (size_t)A->cr_plane * (size_t)ncs * sizeof(float);
@@ -1675,7 +1551,7 @@ int launch_sparse_rows(sparta_vbs_t* A, const void* dB, int64_t ldb, bool b_row_
     // the kernels write C themselves: rows of a row-major C, or 16-row pieces of the columns of the reference's column-major C
     q.out = dC; q.ldo = ldc; q.out_is_c = c_row_major ? 1 : 2;
     if (A->n_sp_long > 0)
-        if (int rc = ensure_scratch(&A->d_sp_part, &A->d_sp_part_bytes, (size_t)A->n_sp_segs * (size_t)n_cols * sizeof(float))) return rc;
+        if (int rc = A->d_sp_part.ensure((size_t)A->n_sp_segs * (size_t)n_cols * sizeof(float))) return rc;
     // widest vector the shapes allow: every row start VEC-element aligned, N a multiple of 64 * VEC (no ragged chunk)
     auto aligned = [&](int v) {
         const bool out_ok = q.out_is_c == 2 || (q.ldo % v == 0 && ((uintptr_t)q.out % (4 * v)) == 0);
@@ -1722,9 +1598,9 @@ int spmm16_core(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
     if (ptr_space == SPARTA_PTR_HOST) {
         const size_t b_elems = (size_t)ldb * (size_t)n_cols;
         ldb16 = (A->cols + 7) / 8 * 8;
-        if (int rc = ensure_scratch(&A->d_B, &A->d_B_bytes, b_elems * sizeof(float))) return rc;
-        if (int rc = ensure_scratch(&A->d_B16, &A->d_B16_bytes, (size_t)ldb16 * n_cols * sizeof(uint16_t))) return rc;
-        if (int rc = ensure_scratch(&A->d_C, &A->d_C_bytes, c_elems * sizeof(float))) return rc;
+        if (int rc = A->d_B.ensure(b_elems * sizeof(float))) return rc;
+        if (int rc = A->d_B16.ensure((size_t)ldb16 * n_cols * sizeof(uint16_t))) return rc;
+        if (int rc = A->d_C.ensure(c_elems * sizeof(float))) return rc;
         HIP_TRY(hipMemcpyAsync(A->d_B, B, b_elems * sizeof(float), hipMemcpyHostToDevice, st));
         if (accumulate) HIP_TRY(hipMemcpyAsync(A->d_C, C, c_elems * sizeof(float), hipMemcpyHostToDevice, st));
         else if (c_elems > 0) HIP_TRY(hipMemsetAsync(A->d_C, 0, c_elems * sizeof(float), st));
@@ -1750,7 +1626,7 @@ int spmm16_core(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
     for (int c = 0; c < 4; c++) A->class_ran[c] = false;
     const size_t slab = (size_t)A->n_slots * SK_SLOT_FLOATS;
     if (A->n_split > 0)
-        if (int rc = ensure_scratch(&A->d_ws, &A->d_ws_bytes, slab * n_nt * sizeof(float))) return rc;
+        if (int rc = A->d_ws.ensure(slab * n_nt * sizeof(float))) return rc;
     StreamParams sp;
     sp.A = A->d_A; sp.B = (const float*)dB; sp.C = dC; sp.ws = (float*)A->d_ws;
     sp.ldb = ldb16; sp.ldc = ldc; sp.cols = A->cols; sp.shard_rows = shard_rows; sp.shard_stride = shard_stride;
@@ -1761,7 +1637,7 @@ int spmm16_core(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
     if (A->n_steps[0] + A->n_steps[1] + A->n_hub_steps > 0) {
         if (prof) HIP_TRY(hipEventRecord(A->cev[0][0], st));
         if (A->has_tail && shard_rows == 0) {
-            if (int rc = ensure_scratch(&A->d_btail, &A->d_btail_bytes, (size_t)A->w * n_cols * sizeof(uint16_t))) return rc;
+            if (int rc = A->d_btail.ensure((size_t)A->w * n_cols * sizeof(uint16_t))) return rc;
             const int64_t row0 = ((A->cols - 1) / A->w) * A->w;
             launch_tail_copy_h16(st, dB, ldb16, row0, A->cols, (int)A->w, (int)n_cols, (uint16_t*)A->d_btail);
             sp.B_tail = (const float*)A->d_btail;
@@ -1803,11 +1679,11 @@ int spmm16_core(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
             const bool a8_live_form = a8_form && A->a8_live && A->live_on && A->live_fwd_built && A->live_fwd_ty == ty;
             A->fwd_last_form[ty] = a8_live_form ? 4 : a8_form ? 3 : live_form ? 2 : 1;
             if (a8_live_form) {
-                sp.A = reinterpret_cast<const float*>(A->d_a8); sp.steps = A->d_fwd_steps; sp.worker_range = A->d_fwd_wrange; sp.sub_ranges = 0;
+                sp.A = reinterpret_cast<const float*>(A->d_a8.get()); sp.steps = A->d_fwd_steps; sp.worker_range = A->d_fwd_wrange; sp.sub_ranges = 0;
                 launch_h16_a8_live_stream(A->kp16, ty != 0, bf16, c_stage, wide, grid, st, sp);
                 sp.A = A->d_A;
             } else if (a8_form) {
-                sp.A = reinterpret_cast<const float*>(A->d_a8); sp.steps = A->d_a8_steps; sp.sub_ranges = 0;
+                sp.A = reinterpret_cast<const float*>(A->d_a8.get()); sp.steps = A->d_a8_steps; sp.sub_ranges = 0;
                 launch_h16_a8_stream(A->kp16, ty != 0, bf16, c_stage, wide, grid, st, sp);
                 sp.A = A->d_A;
             } else if (live_form) {
@@ -1905,9 +1781,9 @@ int spmm16_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
     if (ptr_space == SPARTA_PTR_HOST) {                    // stage here (the core's own staging assumes whole slabs)
         const size_t b_elems = (size_t)ldb * (size_t)n_cols;
         ldb16 = (A->cols + 7) / 8 * 8;
-        if (int rc = ensure_scratch(&A->d_B, &A->d_B_bytes, b_elems * sizeof(float))) return rc;
-        if (int rc = ensure_scratch(&A->d_B16, &A->d_B16_bytes, (size_t)ldb16 * n_cols * sizeof(uint16_t))) return rc;
-        if (int rc = ensure_scratch(&A->d_C, &A->d_C_bytes, c_elems * sizeof(float))) return rc;
+        if (int rc = A->d_B.ensure(b_elems * sizeof(float))) return rc;
+        if (int rc = A->d_B16.ensure((size_t)ldb16 * n_cols * sizeof(uint16_t))) return rc;
+        if (int rc = A->d_C.ensure(c_elems * sizeof(float))) return rc;
         HIP_TRY(hipMemcpyAsync(A->d_B, B, b_elems * sizeof(float), hipMemcpyHostToDevice, st));
         if (accumulate) HIP_TRY(hipMemcpyAsync(A->d_C, C, c_elems * sizeof(float), hipMemcpyHostToDevice, st));
         else if (c_elems > 0) HIP_TRY(hipMemsetAsync(A->d_C, 0, c_elems * sizeof(float), st));
@@ -1925,8 +1801,8 @@ int spmm16_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
     const int64_t n_shards = shard_rows > 0 ? A->cols / shard_rows : 1;
     const int64_t ld_t = shard_rows > 0 ? shard_rows : ldb16;                     // rows of a column of the tail slab of B
     const size_t bt_elems = (size_t)ld_t * kTN * (size_t)n_shards;
-    if (int rc = ensure_scratch(&A->d_Bt, &A->d_Bt_bytes, bt_elems * sizeof(uint16_t))) return rc;
-    if (int rc = ensure_scratch(&A->d_Ct, &A->d_Ct_bytes, (size_t)A->rows * kTN * sizeof(float))) return rc;
+    if (int rc = A->d_Bt.ensure(bt_elems * sizeof(uint16_t))) return rc;
+    if (int rc = A->d_Ct.ensure((size_t)A->rows * kTN * sizeof(float))) return rc;
     HIP_TRY(hipMemsetAsync(A->d_Bt, 0, bt_elems * sizeof(uint16_t), st));
     if (shard_rows > 0 && ldb16 == shard_rows)
         HIP_TRY(hipMemcpy2DAsync(A->d_Bt, (size_t)shard_rows * kTN * sizeof(uint16_t), dB + (size_t)n_main * shard_rows, (size_t)shard_stride * sizeof(uint16_t),
@@ -1986,8 +1862,8 @@ int spmm_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int
     const size_t c_elems = (size_t)ldc * (size_t)(c_layout == SPARTA_COL_MAJOR ? n_cols : A->rows);
     if (ptr_space == SPARTA_PTR_HOST) {
         // the reference's back-end contract: host in, host out, dt excludes the copies
-        if (int rc = ensure_scratch(&A->d_B, &A->d_B_bytes, b_elems * sizeof(float))) return rc;
-        if (int rc = ensure_scratch(&A->d_C, &A->d_C_bytes, c_elems * sizeof(float))) return rc;
+        if (int rc = A->d_B.ensure(b_elems * sizeof(float))) return rc;
+        if (int rc = A->d_C.ensure(c_elems * sizeof(float))) return rc;
         HIP_TRY(hipMemcpyAsync(A->d_B, B, b_elems * sizeof(float), hipMemcpyHostToDevice, st));
         if (accumulate) HIP_TRY(hipMemcpyAsync(A->d_C, C, c_elems * sizeof(float), hipMemcpyHostToDevice, st));
         else if (c_elems > 0) HIP_TRY(hipMemsetAsync(A->d_C, 0, c_elems * sizeof(float), st));   // ld padding stays defined
@@ -2027,7 +1903,7 @@ int spmm_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int
         auto run_stream = [&](float* Cout, bool prof) -> int {
             const size_t slab = (size_t)A->n_slots * SK_SLOT_FLOATS;
             if (A->n_split > 0)
-                if (int rc = ensure_scratch(&A->d_ws, &A->d_ws_bytes, slab * n_nt * sizeof(float))) return rc;
+                if (int rc = A->d_ws.ensure(slab * n_nt * sizeof(float))) return rc;
             if (shard_rows > 0)
                 if (int rc = ensure_gathered_steps(A, shard_rows, st)) return rc;
             // the LDS-staged kernels (33..64-row tiles; any tile under a row-major or gathered B) read the reference-layout image; the no-barrier kernel the fragment image
@@ -2043,7 +1919,7 @@ int spmm_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int
             if (A->n_steps[0] + A->n_steps[1] > 0) {
                 if (prof) HIP_TRY(hipEventRecord(A->cev[0][0], st));
                 if (A->has_tail && shard_rows == 0) {
-                    if (int rc = ensure_scratch(&A->d_btail, &A->d_btail_bytes, (size_t)A->w * n_cols * sizeof(float))) return rc;
+                    if (int rc = A->d_btail.ensure((size_t)A->w * n_cols * sizeof(float))) return rc;
                     const int64_t row0 = ((A->cols - 1) / A->w) * A->w;
                     launch_tail_copy(st, dB, ldb, (int)(b_layout == SPARTA_ROW_MAJOR), row0, A->cols, (int)A->w, (int)n_cols, (float*)A->d_btail);
                     sp.B_tail = (const float*)A->d_btail;
@@ -2120,7 +1996,7 @@ int spmm_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int
             if (path == 0 && g_capturing) return capture_refusal("time its two product paths");
             if (path == 0) {
                 // plan-time autotune: both paths write a scratch C (the caller's C must not be accumulated into twice)
-                if (int rc = ensure_scratch(&A->d_tune, &A->d_tune_bytes, c_elems * sizeof(float))) return rc;
+                if (int rc = A->d_tune.ensure(c_elems * sizeof(float))) return rc;
                 float best[3] = {0.0f, 1e30f, 1e30f};
                 for (int cand = 1; cand <= 2; cand++) {
                     for (int rep = 0; rep < 4; rep++) {
@@ -2216,7 +2092,7 @@ struct sparta_b {
     const void* B = nullptr;
     int64_t ldb = 0, shard_rows = 0, shard_stride = 0, cols = 0;
     int32_t n_cols = 0, dtype = 0, device = 0;
-    void* d_Brm = nullptr;                 // row-major copy for the sparse-row kernels and the column-compacted tiles (nullptr: this handle / shape does not need one)
+    DevBuf<uint8_t> d_Brm;                 // row-major copy for the sparse-row kernels and the column-compacted tiles (nullptr: this handle / shape does not need one)
     int64_t ld_brm = 0;                    // its row stride in elements (n_cols rounded up to 16 bytes)
 };
 
@@ -2235,7 +2111,9 @@ int sparta_vbs_prepare_b(sparta_vbs_t* A, const void* B, int64_t ldb, int64_t sh
         return fail(SPARTA_ERR_INVALID, "sparta_vbs_prepare_b: bad gathered layout");
     if (g_capturing) return capture_refusal("prepare a copy of B");
     DeviceGuard guard(A->device);
-    sparta_b* p = new (std::nothrow) sparta_b;
+    // owned by `hold` until it is handed to the caller (the guard above outlives it: the copy is freed with the handle's device current)
+    std::unique_ptr<sparta_b> hold(new (std::nothrow) sparta_b);
+    sparta_b* p = hold.get();
     if (!p) return fail(SPARTA_ERR_ALLOC, "sparta_vbs_prepare_b: out of host memory");
     p->B = B; p->ldb = shard_rows ? shard_ld : ldb; p->shard_rows = shard_rows; p->shard_stride = shard_stride; p->cols = A->cols;
     p->n_cols = n_cols; p->dtype = A->dtype; p->device = A->device;
@@ -2247,14 +2125,14 @@ int sparta_vbs_prepare_b(sparta_vbs_t* A, const void* B, int64_t ldb, int64_t sh
     if (needs_copy) {
         hipStream_t st = (hipStream_t)stream;
         const int64_t n_wg = ((A->cols + 63) / 64) * (int64_t)((n_cols + 63) / 64);
-        if (n_wg > INT32_MAX) { delete p; return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_prepare_b: B too large for the transpose grid"); }
+        if (n_wg > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_prepare_b: B too large for the transpose grid");
         const int64_t per16 = 16 / (int64_t)esz;
         p->ld_brm = (n_cols + per16 - 1) / per16 * per16;
-        if (hipMalloc(&p->d_Brm, (size_t)A->cols * (size_t)p->ld_brm * esz) != hipSuccess) { delete p; return fail(SPARTA_ERR_ALLOC, "sparta_vbs_prepare_b: out of device memory"); }
+        if (p->d_Brm.alloc((size_t)A->cols * (size_t)p->ld_brm * esz) != hipSuccess) return fail(SPARTA_ERR_ALLOC, "sparta_vbs_prepare_b: out of device memory");
         launch_b_to_row_major(A->dtype != SPARTA_F32, (unsigned)n_wg, st, B, p->ldb, shard_rows, shard_stride, A->cols, (int)n_cols, p->d_Brm, p->ld_brm);
-        if (hipGetLastError() != hipSuccess) { (void)hipFree(p->d_Brm); delete p; return fail(SPARTA_ERR_HIP, "sparta_vbs_prepare_b: launch failed"); }
+        if (hipGetLastError() != hipSuccess) return fail(SPARTA_ERR_HIP, "sparta_vbs_prepare_b: launch failed");
     }
-    *out = p;
+    *out = hold.release();
     return SPARTA_OK;
     SPARTA_GUARD_END("sparta_vbs_prepare_b")
 }
@@ -2277,7 +2155,6 @@ int sparta_vbs_spmm_prepared(sparta_vbs_t* A, const sparta_b_t* Bp, void* C, int
 int sparta_b_destroy(sparta_b_t* Bp) {
     if (!Bp) return SPARTA_OK;
     DeviceGuard guard(Bp->device);
-    if (Bp->d_Brm) (void)hipFree(Bp->d_Brm);
     delete Bp;
     return SPARTA_OK;
 }
@@ -2288,10 +2165,10 @@ int sparta_vbs_set_class_timing(sparta_vbs_t* A, int32_t enable) {
     DeviceGuard guard(A->device);
     if (enable && !A->cev[0][0]) {
         for (int c = 0; c < 4; c++)
-            for (int e = 0; e < 2; e++) HIP_TRY(hipEventCreate(&A->cev[c][e]));
+            for (int e = 0; e < 2; e++) HIP_TRY(A->cev[c][e].create());
     }
     if (enable && !A->d_clk) {
-        HIP_TRY(hipMalloc((void**)&A->d_clk, (16 + 4 * 64 * 8 + 2048) * sizeof(long long)));
+        HIP_TRY(A->d_clk.alloc(16 + 4 * 64 * 8 + 2048));
         HIP_TRY(hipMemset(A->d_clk, 0, (16 + 4 * 64 * 8 + 2048) * sizeof(long long)));
     }
     A->class_timing = enable != 0;
@@ -2348,10 +2225,7 @@ int ensure_sddmm_items(sparta_vbs_t* A) {
                 items.push_back(SddmmItem{(int32_t)ib, r0, (int32_t)g0, (int32_t)std::min<int64_t>(kSdGroups, n_groups - g0)});
     }
     if ((int64_t)items.size() > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_sddmm: more than 2^31 - 1 work items");
-    if (!items.empty()) {
-        HIP_TRY(hipMalloc((void**)&A->d_sd_items, items.size() * sizeof(SddmmItem)));
-        HIP_TRY(hipMemcpy(A->d_sd_items, items.data(), items.size() * sizeof(SddmmItem), hipMemcpyHostToDevice));
-    }
+    if (!items.empty()) HIP_TRY(A->d_sd_items.upload(items));
     A->n_sd_items = (int64_t)items.size();
     return SPARTA_OK;
 }
@@ -2369,63 +2243,57 @@ int sddmm_impl(sparta_vbs_t* A, const void* X, int64_t ldx, const void* Y, int64
     if (A->ext_sparse)
         return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_sddmm: the handle does not hold the dense blocks of every block-row (made by sparta_vbs_create_from_csr)");
 
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, "sparta_vbs_sddmm: hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, ptr_space == SPARTA_PTR_DEVICE);
-    if (g_capturing && dt_ms) return capture_refusal("time the product (dt_ms != NULL synchronises)", "sparta_vbs_sddmm");
-    if (int rc = ensure_sddmm_items(A)) return rc;
+    const DeviceCall call{"sparta_vbs_sddmm", A->device, (hipStream_t)stream, ptr_space == SPARTA_PTR_DEVICE, dt_ms, "the product", A->ev0, A->ev1};
+    return open_call(call, [&](hipStream_t st) -> int {
+        if (int rc = ensure_sddmm_items(A)) return rc;
 
-    const void* dX = X;
-    const void* dY = Y;
-    float* dG = G;
-    int64_t kx = ldx, ky = ldy;
-    const size_t x_elems = (size_t)ldx * (size_t)(k - 1) + (size_t)A->rows, y_elems = (size_t)ldy * (size_t)(k - 1) + (size_t)A->cols;
-    const size_t g_elems = (size_t)A->nztot;
-    if (ptr_space == SPARTA_PTR_HOST) {
-        // host in, host out: X, Y, G staged in one device buffer; 16-bit handles round X, Y on the device
-        if (int rc = ensure_scratch(&A->d_sd_ws, &A->d_sd_ws_bytes, (x_elems + y_elems + g_elems) * sizeof(float))) return rc;
-        float* ws = (float*)A->d_sd_ws;
-        HIP_TRY(hipMemcpyAsync(ws, X, x_elems * sizeof(float), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(ws + x_elems, Y, y_elems * sizeof(float), hipMemcpyHostToDevice, st));
-        if (accumulate && g_elems > 0) HIP_TRY(hipMemcpyAsync(ws + x_elems + y_elems, G, g_elems * sizeof(float), hipMemcpyHostToDevice, st));
-        dX = ws; dY = ws + x_elems; dG = ws + x_elems + y_elems;
-        if (h16) {
-            kx = (A->rows + 7) / 8 * 8; ky = (A->cols + 7) / 8 * 8;       // (multiples of 8: the 16-byte loads of k_sddmm.hip)
-            const size_t hx = (size_t)kx * (size_t)k, hy = (size_t)ky * (size_t)k;
-            if (int rc = ensure_scratch(&A->d_sd_h16, &A->d_sd_h16_bytes, (hx + hy) * sizeof(uint16_t))) return rc;
-            uint16_t* hw = (uint16_t*)A->d_sd_h16;
-            launch_convert_h16(A->dtype == SPARTA_BF16, st, ws, ldx, A->rows, k, hw, kx);
-            launch_convert_h16(A->dtype == SPARTA_BF16, st, ws + x_elems, ldy, A->cols, k, hw + hx, ky);
-            HIP_TRY(hipGetLastError());
-            dX = hw; dY = hw + hx;
+        const void* dX = X;
+        const void* dY = Y;
+        float* dG = G;
+        int64_t kx = ldx, ky = ldy;
+        const size_t x_elems = (size_t)ldx * (size_t)(k - 1) + (size_t)A->rows, y_elems = (size_t)ldy * (size_t)(k - 1) + (size_t)A->cols;
+        const size_t g_elems = (size_t)A->nztot;
+        if (ptr_space == SPARTA_PTR_HOST) {
+            // host in, host out: X, Y, G staged in one device buffer; 16-bit handles round X, Y on the device
+            if (int rc = A->d_sd_ws.ensure((x_elems + y_elems + g_elems) * sizeof(float))) return rc;
+            float* ws = (float*)A->d_sd_ws;
+            HIP_TRY(hipMemcpyAsync(ws, X, x_elems * sizeof(float), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ws + x_elems, Y, y_elems * sizeof(float), hipMemcpyHostToDevice, st));
+            if (accumulate && g_elems > 0) HIP_TRY(hipMemcpyAsync(ws + x_elems + y_elems, G, g_elems * sizeof(float), hipMemcpyHostToDevice, st));
+            dX = ws; dY = ws + x_elems; dG = ws + x_elems + y_elems;
+            if (h16) {
+                kx = (A->rows + 7) / 8 * 8; ky = (A->cols + 7) / 8 * 8;       // (multiples of 8: the 16-byte loads of k_sddmm.hip)
+                const size_t hx = (size_t)kx * (size_t)k, hy = (size_t)ky * (size_t)k;
+                if (int rc = A->d_sd_h16.ensure((hx + hy) * sizeof(uint16_t))) return rc;
+                uint16_t* hw = (uint16_t*)A->d_sd_h16;
+                launch_convert_h16(A->dtype == SPARTA_BF16, st, ws, ldx, A->rows, k, hw, kx);
+                launch_convert_h16(A->dtype == SPARTA_BF16, st, ws + x_elems, ldy, A->cols, k, hw + hx, ky);
+                HIP_TRY(hipGetLastError());
+                dX = hw; dY = hw + hx;
+            }
         }
-    }
-    SddmmParams p;
-    p.brows = A->d_brows; p.jab = A->d_jab; p.items = A->d_sd_items;
-    p.X = dX; p.Y = dY; p.G = dG;
-    p.ldx = kx; p.ldy = ky; p.cols = A->cols;
-    p.k = k; p.w = (int32_t)A->w; p.accumulate = accumulate != 0; p.pad = 0;
-    if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
-    if (A->live_on) {
-        // a live set is installed: the dead blocks get their zeros (accumulate = 0) from the mask kernel and the snapshot, in front; the live kernel walks the
-        // compacted group lists over the same grid (an item past its block-row's live groups returns at once), so nothing here depends on a count read back
-        if (!p.accumulate && A->n_prune > 0 && A->nztot > 0) launch_mask_blocks(st, A->d_prune, A->n_prune, A->d_live_keep, dG, nullptr, nullptr, nullptr);
-        launch_sddmm_live(A->dtype, (unsigned)A->n_sd_items, st, p, SddmmLive{A->d_live_groups, A->d_live_goff, A->d_live_gcount, A->d_live_keep});
-    } else {
-        launch_sddmm(A->dtype, (unsigned)A->n_sd_items, st, p);
-    }
-    HIP_TRY(hipGetLastError());
-    if (dt_ms) {
-        HIP_TRY(hipEventRecord(A->ev1, st));
-        HIP_TRY(hipEventSynchronize(A->ev1));
-        HIP_TRY(hipEventElapsedTime(dt_ms, A->ev0, A->ev1));
-    }
-    if (ptr_space == SPARTA_PTR_HOST) {
-        if (g_elems > 0) HIP_TRY(hipMemcpyAsync(G, dG, g_elems * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return SPARTA_OK;
+        SddmmParams p;
+        p.brows = A->d_brows; p.jab = A->d_jab; p.items = A->d_sd_items;
+        p.X = dX; p.Y = dY; p.G = dG;
+        p.ldx = kx; p.ldy = ky; p.cols = A->cols;
+        p.k = k; p.w = (int32_t)A->w; p.accumulate = accumulate != 0; p.pad = 0;
+        const int trc = timed_launches(call, [&](hipStream_t) {
+            if (A->live_on) {
+                // a live set is installed: the dead blocks get their zeros (accumulate = 0) from the mask kernel and the snapshot, in front; the live kernel walks the
+                // compacted group lists over the same grid (an item past its block-row's live groups returns at once), so nothing here depends on a count read back
+                if (!p.accumulate && A->n_prune > 0 && A->nztot > 0) launch_mask_blocks(st, A->d_prune, A->n_prune, A->d_live_keep, dG, nullptr, nullptr, nullptr);
+                launch_sddmm_live(A->dtype, (unsigned)A->n_sd_items, st, p, SddmmLive{A->d_live_groups, A->d_live_goff, A->d_live_gcount, A->d_live_keep});
+            } else {
+                launch_sddmm(A->dtype, (unsigned)A->n_sd_items, st, p);
+            }
+        });
+        if (trc) return trc;
+        if (ptr_space == SPARTA_PTR_HOST) {
+            if (g_elems > 0) HIP_TRY(hipMemcpyAsync(G, dG, g_elems * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        return SPARTA_OK;
+    });
 }
 
 }  // namespace
@@ -2475,7 +2343,7 @@ int launch_images_from(sparta_vbs_t* A, hipStream_t st, const float* src) {
         const bool bf16 = A->dtype == SPARTA_BF16;
         for (int ty = 0; ty < 2; ty++)
             if (A->n_steps[ty] > 0) {
-                launch_update_h16(bf16, false, ty ? 64 : 32, A->kp16, st, A->d_upd_map[ty], A->n_steps[ty], src, (uint16_t*)A->d_A + A->upd_base[ty]);
+                launch_update_h16(bf16, false, ty ? 64 : 32, A->kp16, st, A->d_upd_map[ty], A->n_steps[ty], src, (uint16_t*)A->d_A.get() + A->upd_base[ty]);
                 launches++;
             }
         if (A->n_upd_hub > 0) { launch_update_h16(bf16, true, 64, 64, st, A->d_upd_hub, A->n_upd_hub, src, A->d_hub_A); launches++; }
@@ -2489,33 +2357,19 @@ int set_values_impl(sparta_vbs_t* A, const float* mab, int32_t ptr_space, void* 
     if (!A) return fail(SPARTA_ERR_INVALID, "sparta_vbs_set_values: NULL handle");
     if (!mab && A->nztot > 0) return fail(SPARTA_ERR_INVALID, "sparta_vbs_set_values: mab is NULL");
     if (ptr_space != SPARTA_PTR_HOST && ptr_space != SPARTA_PTR_DEVICE) return fail(SPARTA_ERR_INVALID, "sparta_vbs_set_values: bad ptr_space");
-    if (!(A->create_flags & SPARTA_CREATE_UPDATABLE))
-        return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_set_values: the handle was not made with SPARTA_CREATE_UPDATABLE (sparta_vbs_create_range_ex; handles of "
-                                            "sparta_vbs_create_from_csr and sparta_vbs_create_transposed cannot take new values)");
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, "sparta_vbs_set_values: hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, ptr_space == SPARTA_PTR_DEVICE);
-    if (g_capturing && dt_ms) return capture_refusal("time the update (dt_ms != NULL synchronises)", "sparta_vbs_set_values");
-    const float* src = mab;
-    if (ptr_space == SPARTA_PTR_HOST && A->nztot > 0) {
-        if (int rc = ensure_scratch(&A->d_upd_ws, &A->d_upd_ws_bytes, (size_t)A->nztot * sizeof(float))) return rc;
-        HIP_TRY(hipMemcpyAsync(A->d_upd_ws, mab, (size_t)A->nztot * sizeof(float), hipMemcpyHostToDevice, st));
-        src = (const float*)A->d_upd_ws;
-    }
-    if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
-    if (A->nztot > 0) {
-        (void)launch_images_from(A, st, src);
-        a8_requantize(A, st, src);
-        HIP_TRY(hipGetLastError());
-    }
-    if (dt_ms) {
-        HIP_TRY(hipEventRecord(A->ev1, st));
-        HIP_TRY(hipEventSynchronize(A->ev1));
-        HIP_TRY(hipEventElapsedTime(dt_ms, A->ev0, A->ev1));
-    }
-    if (ptr_space == SPARTA_PTR_HOST) HIP_TRY(hipStreamSynchronize(st));          // (the caller's array is free again when the call returns)
-    return SPARTA_OK;
+    if (!(A->create_flags & SPARTA_CREATE_UPDATABLE)) return not_updatable("sparta_vbs_set_values");
+    const DeviceCall call{"sparta_vbs_set_values", A->device, (hipStream_t)stream, ptr_space == SPARTA_PTR_DEVICE, dt_ms, "the update", A->ev0, A->ev1, A->nztot <= 0};
+    return open_call(call, [&](hipStream_t st) -> int {
+        const float* src = mab;
+        if (ptr_space == SPARTA_PTR_HOST && A->nztot > 0) {
+            if (int rc = A->d_upd_ws.ensure((size_t)A->nztot * sizeof(float))) return rc;
+            HIP_TRY(hipMemcpyAsync(A->d_upd_ws, mab, (size_t)A->nztot * sizeof(float), hipMemcpyHostToDevice, st));
+            src = (const float*)A->d_upd_ws;
+        }
+        if (int rc = timed_launches(call, [&](hipStream_t) { (void)launch_images_from(A, st, src); a8_requantize(A, st, src); })) return rc;
+        if (ptr_space == SPARTA_PTR_HOST) HIP_TRY(hipStreamSynchronize(st));          // (the caller's array is free again when the call returns)
+        return SPARTA_OK;
+    });
 }
 
 }  // namespace
@@ -2546,15 +2400,10 @@ int sgd_fused_image(const sparta_vbs_t* A) {
 // Whether a step asks for the image kernel (sgd_fused_image then says whether the handle has one).  By default every step does: on the headline handle the
 // image kernel measured faster than the elementwise kernel + the set_values launches, and than the same update as torch ops + set_values, with and without
 // momentum, fp32 and f16.  SPARTA_SGD_FUSE=0 asks for the two-pass form on every step, 1 is the default spelled out.  Read at every
-// call (no plan depends on it): scripts/sgd_step_record.py and the tests drive both forms of one handle in one process.
+// call through env_switch (no plan depends on it): scripts/sgd_step_record.py and the tests drive both forms of one handle in one process.
 // Live steps (sparta_vbs_set_live_steps): the switch counts only while a live set is installed; read when a step is called or captured.  The image kernels'
 // words exist then: the enabling call built them, and every set_live_blocks since rewrote them behind the snapshot.
 bool live_steps_active(const sparta_vbs_t* A) { return A->live_on && A->live_steps && A->live_steps_built; }
-
-bool sgd_fuse_wanted() {
-    const char* e = std::getenv("SPARTA_SGD_FUSE");
-    return !e || atoi(e) != 0;
-}
 
 // entry: the name the messages carry.  R: the control record of sparta_vbs_sgd_step_ctl, or NULL (the step as it always was)
 int sgd_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G, float* M, const sparta_sgd_cfg* cfg, const void* R, void* stream, float* dt_ms) {
@@ -2562,23 +2411,16 @@ int sgd_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G, 
     if (!A) return fail(SPARTA_ERR_INVALID, ": NULL handle");
     if (A->nztot > 0 && (!W || !G || !cfg)) return fail(SPARTA_ERR_INVALID, ": W, G or cfg is NULL");
     if (cfg && cfg->momentum != 0.0f && !M) return fail(SPARTA_ERR_INVALID, ": M is NULL with momentum != 0");
-    if (!(A->create_flags & SPARTA_CREATE_UPDATABLE))
-        return fail(SPARTA_ERR_UNSUPPORTED, ": the handle was not made with SPARTA_CREATE_UPDATABLE (sparta_vbs_create_range_ex; handles of "
-                                            "sparta_vbs_create_from_csr and sparta_vbs_create_transposed cannot take new values)");
+    if (!(A->create_flags & SPARTA_CREATE_UPDATABLE)) return not_updatable(entry);
     if ((uintptr_t)R % 8 != 0) return fail(SPARTA_ERR_INVALID, ": the control record R must be 8-byte aligned");
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, ": hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, true);
-    if (g_capturing && dt_ms) return capture_refusal("time the step (dt_ms != NULL synchronises)", entry);
-    if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
     int launches = 0;
     int fused = -1;
     bool live = false;
-    if (A->nztot > 0) {
+    const DeviceCall call{entry, A->device, (hipStream_t)stream, true, dt_ms, "the step", A->ev0, A->ev1, A->nztot <= 0};
+    const int rc = device_call(call, [&](hipStream_t st) {
         const SgdCfg c{cfg->lr, cfg->momentum, cfg->weight_decay, cfg->grad_scale};
         const uint32_t* ctl = (const uint32_t*)R;
-        if (sgd_fuse_wanted()) fused = sgd_fused_image(A);
+        if (env_switch("SPARTA_SGD_FUSE")) fused = sgd_fused_image(A);
         live = live_steps_active(A);
         if (fused >= 0 && A->dtype == SPARTA_F32) {
             if (live) launch_sgd_f32_frag_live(st, A->d_steps[0], A->n_steps[0], W, G, M, c, ctl, A->d_a_frag, A->d_A, A->d_live_words);
@@ -2586,7 +2428,7 @@ int sgd_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G, 
             launches = 1;
         } else if (fused >= 0) {
             const bool bf16 = A->dtype == SPARTA_BF16;
-            uint16_t* dst = (uint16_t*)A->d_A + A->upd_base[fused];
+            uint16_t* dst = (uint16_t*)A->d_A.get() + A->upd_base[fused];
             if (live) launch_sgd_h16_live(bf16, fused ? 64 : 32, A->kp16, st, A->d_upd_map[fused], A->n_steps[fused], W, G, M, c, ctl, dst, A->d_live_words);
             else launch_sgd_h16(bf16, fused ? 64 : 32, A->kp16, st, A->d_upd_map[fused], A->n_steps[fused], W, G, M, c, ctl, dst);
             launches = 1;
@@ -2597,16 +2439,11 @@ int sgd_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G, 
             launches = 1 + launch_images_from(A, st, W);
         }
         a8_requantize(A, st, W);                  // (a step the control record skipped left W as it was: the image comes out as it stood)
-        HIP_TRY(hipGetLastError());
-    }
+    });
+    if (rc) return rc;
     A->step_last_live = live ? 1 : 0;
     A->step_last_fused = fused >= 0 ? 1 : 0;
     A->step_last_launches = launches;
-    if (dt_ms) {
-        HIP_TRY(hipEventRecord(A->ev1, st));
-        HIP_TRY(hipEventSynchronize(A->ev1));
-        HIP_TRY(hipEventElapsedTime(dt_ms, A->ev0, A->ev1));
-    }
     return SPARTA_OK;
 }
 
@@ -2630,12 +2467,7 @@ namespace {
 
 // Whether a step asks for the image kernel (sgd_fused_image says whether the handle has one): the default is the form that measured faster on the headline
 // handle, DESIGN.md section 3.8.  SPARTA_ADAM_FUSE=0 asks for the two-pass form on every step, 1 for the image kernel wherever the handle has one.  Read at
-// every call, as SPARTA_SGD_FUSE is.
-bool adam_fuse_wanted() {
-    const char* e = std::getenv("SPARTA_ADAM_FUSE");
-    return !e || atoi(e) != 0;
-}
-
+// every call through env_switch, as SPARTA_SGD_FUSE is.
 int adam_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G, float* M, float* V, void* S, const sparta_adam_cfg* cfg, const void* R, void* stream,
                    float* dt_ms) {
     const auto fail = [entry](int code, const char* what) { return sparta::fail(code, std::string(entry) + what); };
@@ -2647,26 +2479,19 @@ int adam_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G,
         if (!(cfg->eps > 0.0f)) return fail(SPARTA_ERR_INVALID, ": eps must be > 0");
         if (cfg->reserved != 0) return fail(SPARTA_ERR_INVALID, ": cfg->reserved must be 0");
     }
-    if (!(A->create_flags & SPARTA_CREATE_UPDATABLE))
-        return fail(SPARTA_ERR_UNSUPPORTED, ": the handle was not made with SPARTA_CREATE_UPDATABLE (sparta_vbs_create_range_ex; handles of "
-                                            "sparta_vbs_create_from_csr and sparta_vbs_create_transposed cannot take new values)");
+    if (!(A->create_flags & SPARTA_CREATE_UPDATABLE)) return not_updatable(entry);
     if ((uintptr_t)R % 8 != 0) return fail(SPARTA_ERR_INVALID, ": the control record R must be 8-byte aligned");
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, ": hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, true);
-    if (g_capturing && dt_ms) return capture_refusal("time the step (dt_ms != NULL synchronises)", entry);
-    if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
     int launches = 0;
     int fused = -1;
     bool live = false;
-    if (A->nztot > 0) {
+    const DeviceCall call{entry, A->device, (hipStream_t)stream, true, dt_ms, "the step", A->ev0, A->ev1, A->nztot <= 0};
+    const int rc = device_call(call, [&](hipStream_t st) {
         // the three derived constants, each operation rounded once to fp32 (volatile: no contraction, no wider intermediate)
         volatile float omb1 = 1.0f - cfg->beta1, omb2 = 1.0f - cfg->beta2, lr_wd = cfg->lr * cfg->weight_decay;
         volatile float dk = 1.0f - lr_wd;
         const AdamArgs a{W, G, M, V, (float*)S,
                          AdamCfg{cfg->lr, cfg->beta1, cfg->beta2, cfg->eps, cfg->weight_decay, cfg->grad_scale, omb1, omb2, dk, cfg->decoupled != 0 ? 1 : 0}, (const uint32_t*)R};
-        if (adam_fuse_wanted()) fused = sgd_fused_image(A);
+        if (env_switch("SPARTA_ADAM_FUSE")) fused = sgd_fused_image(A);
         live = live_steps_active(A);
         launch_adam_tick(st, a);
         launches = 1;
@@ -2676,7 +2501,7 @@ int adam_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G,
             launches++;
         } else if (fused >= 0) {
             const bool bf16 = A->dtype == SPARTA_BF16;
-            uint16_t* dst = (uint16_t*)A->d_A + A->upd_base[fused];
+            uint16_t* dst = (uint16_t*)A->d_A.get() + A->upd_base[fused];
             if (live) launch_adam_h16_live(bf16, fused ? 64 : 32, A->kp16, st, A->d_upd_map[fused], A->n_steps[fused], a, dst, A->d_live_words);
             else launch_adam_h16(bf16, fused ? 64 : 32, A->kp16, st, A->d_upd_map[fused], A->n_steps[fused], a, dst);
             launches++;
@@ -2687,16 +2512,11 @@ int adam_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G,
             launches += 1 + launch_images_from(A, st, W);
         }
         a8_requantize(A, st, W);                  // (as in sgd_step_impl)
-        HIP_TRY(hipGetLastError());
-    }
+    });
+    if (rc) return rc;
     A->step_last_live = live ? 1 : 0;
     A->step_last_fused = fused >= 0 ? 1 : 0;
     A->step_last_launches = launches;
-    if (dt_ms) {
-        HIP_TRY(hipEventRecord(A->ev1, st));
-        HIP_TRY(hipEventSynchronize(A->ev1));
-        HIP_TRY(hipEventElapsedTime(dt_ms, A->ev0, A->ev1));
-    }
     return SPARTA_OK;
 }
 
@@ -2728,25 +2548,9 @@ extern "C" int sparta_grad_stats(const float* G, int64_t n, void* R, int32_t acc
     if (n < 0) return fail(SPARTA_ERR_INVALID, "sparta_grad_stats: n < 0");
     if (n > 0 && !G) return fail(SPARTA_ERR_INVALID, "sparta_grad_stats: G is NULL with n > 0");
     if ((uintptr_t)G % 4 != 0) return fail(SPARTA_ERR_INVALID, "sparta_grad_stats: G must be 4-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, true);
-    if (g_capturing && dt_ms) return capture_refusal("time the reduction (dt_ms != NULL synchronises)", "sparta_grad_stats");
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (dt_ms) {                                // handle-free: the events live for this call (which synchronises anyway)
-        HIP_TRY(hipEventCreate(&ev[0]));
-        if (hipEventCreate(&ev[1]) != hipSuccess) { (void)hipEventDestroy(ev[0]); return fail(SPARTA_ERR_HIP, "sparta_grad_stats: hipEventCreate failed"); }
-        (void)hipEventRecord(ev[0], st);
-    }
-    launch_grad_stats(st, G, n, R, accumulate != 0);
-    hipError_t err = hipGetLastError();
-    if (dt_ms) {
-        if (err == hipSuccess) err = hipEventRecord(ev[1], st);
-        if (err == hipSuccess) err = hipEventSynchronize(ev[1]);
-        if (err == hipSuccess) err = hipEventElapsedTime(dt_ms, ev[0], ev[1]);
-        (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
-    }
-    if (err != hipSuccess) return fail(SPARTA_ERR_HIP, std::string("sparta_grad_stats: ") + hipGetErrorString(err));
-    return SPARTA_OK;
+    // handle-free: no guard, and the events of a timed call live for that call
+    return device_call(DeviceCall{"sparta_grad_stats", -1, (hipStream_t)stream, true, dt_ms, "the reduction"},
+                       [&](hipStream_t st) { launch_grad_stats(st, G, n, R, accumulate != 0); });
     SPARTA_GUARD_END("sparta_grad_stats")
 }
 
@@ -2761,9 +2565,8 @@ extern "C" int sparta_grad_ctl_finish(void* R, const sparta_grad_ctl_cfg* cfg, v
         return fail(SPARTA_ERR_INVALID, "sparta_grad_ctl_finish: growth_factor must be >= 1 and backoff_factor in (0, 1]");
     for (int i = 0; i < 4; i++)
         if (cfg->reserved[i] != 0) return fail(SPARTA_ERR_INVALID, "sparta_grad_ctl_finish: cfg->reserved must be 0");
-    launch_grad_ctl_finish((hipStream_t)stream, R, cfg->max_norm, cfg->growth_factor, cfg->backoff_factor, cfg->growth_interval);
-    HIP_TRY(hipGetLastError());
-    return SPARTA_OK;
+    return device_call(DeviceCall{"sparta_grad_ctl_finish", -1, (hipStream_t)stream, true},
+                       [&](hipStream_t st) { launch_grad_ctl_finish(st, R, cfg->max_norm, cfg->growth_factor, cfg->backoff_factor, cfg->growth_interval); });
     SPARTA_GUARD_END("sparta_grad_ctl_finish")
 }
 
@@ -2828,29 +2631,7 @@ int64_t ep_scratch_bytes(int64_t rows, int64_t n_cols) {
 // the launches of one entry between two events of this call (handle-free, as sparta_grad_stats)
 template <class Launch>
 int ep_call(const char* entry, bool nothing_to_do, void* stream, float* dt_ms, Launch launch) {
-    using sparta::fail;
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, true);
-    if (g_capturing && dt_ms) return capture_refusal("time the kernels (dt_ms != NULL synchronises)", entry);
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (dt_ms) {
-        HIP_TRY(hipEventCreate(&ev[0]));
-        if (hipEventCreate(&ev[1]) != hipSuccess) { (void)hipEventDestroy(ev[0]); return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipEventCreate failed"); }
-        (void)hipEventRecord(ev[0], st);
-    }
-    hipError_t err = hipSuccess;
-    if (!nothing_to_do) {
-        launch(st);
-        err = hipGetLastError();
-    }
-    if (dt_ms) {
-        if (err == hipSuccess) err = hipEventRecord(ev[1], st);
-        if (err == hipSuccess) err = hipEventSynchronize(ev[1]);
-        if (err == hipSuccess) err = hipEventElapsedTime(dt_ms, ev[0], ev[1]);
-        (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
-    }
-    if (err != hipSuccess) return fail(SPARTA_ERR_HIP, std::string(entry) + ": " + hipGetErrorString(err));
-    return SPARTA_OK;
+    return device_call(DeviceCall{entry, -1, (hipStream_t)stream, true, dt_ms, "the kernels", nullptr, nullptr, nothing_to_do}, launch);
 }
 
 }  // namespace
@@ -2952,35 +2733,20 @@ int ensure_prune_table(sparta_vbs_t* A, const char* entry) {
         if (table[(size_t)(4 * q + 2)] > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": a block of 2^31 or more elements");
         rec[(size_t)q] = PruneBlock{table[(size_t)(4 * q)], (int32_t)table[(size_t)(4 * q + 1)], (int32_t)table[(size_t)(4 * q + 2)]};
     }
-    if (nb > 0) {
-        HIP_TRY(hipMalloc((void**)&A->d_prune, rec.size() * sizeof(PruneBlock)));
-        HIP_TRY(hipMemcpy(A->d_prune, rec.data(), rec.size() * sizeof(PruneBlock), hipMemcpyHostToDevice));
-    }
+    if (nb > 0) HIP_TRY(A->d_prune.upload(rec));
     A->n_prune = nb;
     return SPARTA_OK;
 }
 
+// the launches of one entry between the handle's events, behind the block table (built at the first call that has something to do)
 template <class Launch>
 int prune_call(sparta_vbs_t* A, const char* entry, bool nothing_to_do, void* stream, float* dt_ms, Launch launch) {
-    using sparta::fail;
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, true);
-    if (g_capturing && dt_ms) return capture_refusal("time the kernel (dt_ms != NULL synchronises)", entry);
-    if (!nothing_to_do)
-        if (int rc = ensure_prune_table(A, entry)) return rc;
-    if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
-    if (!nothing_to_do) {
-        launch(st);
-        HIP_TRY(hipGetLastError());
-    }
-    if (dt_ms) {
-        HIP_TRY(hipEventRecord(A->ev1, st));
-        HIP_TRY(hipEventSynchronize(A->ev1));
-        HIP_TRY(hipEventElapsedTime(dt_ms, A->ev0, A->ev1));
-    }
-    return SPARTA_OK;
+    const DeviceCall call{entry, A->device, (hipStream_t)stream, true, dt_ms, "the kernel", A->ev0, A->ev1, nothing_to_do};
+    return open_call(call, [&](hipStream_t) -> int {
+        if (!nothing_to_do)
+            if (int rc = ensure_prune_table(A, entry)) return rc;
+        return timed_launches(call, launch);
+    });
 }
 
 }  // namespace
@@ -3170,39 +2936,28 @@ extern "C" int sparta_vbs_move_blocks(sparta_vbs_t* dst, const sparta_vbs_t* src
             if (r > q && D[r] && overlap((uintptr_t)D[q], d_bytes, (uintptr_t)D[r], d_bytes)) return fail(SPARTA_ERR_INVALID, std::string(me) + ": two destination tensors overlap");
         }
     }
-    DeviceGuard guard(dst->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(me) + ": hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, true);
-    if (g_capturing) return capture_refusal("build and upload the records of the move (it synchronises)", me);
-    std::vector<int64_t> td, ts;
-    if (int rc = host_block_table(dst, me, td)) return rc;
-    if (int rc = host_block_table(src, me, ts)) return rc;
-    std::vector<MoveBlock> rec((size_t)nb);
-    for (int64_t b = 0; b < nb; b++) {
-        const int64_t n_all = td[(size_t)(4 * b + 2)];
-        if (n_all > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, std::string(me) + ": a block of 2^31 or more elements");
-        const int64_t m = map[b];
-        if (m >= 0 && ts[(size_t)(4 * m + 2)] != n_all) return fail(SPARTA_ERR_INVALID, std::string(me) + ": a mapped block differs in size (n_all) from its source block");
-        rec[(size_t)b] = MoveBlock{m >= 0 ? ts[(size_t)(4 * m)] : 0, td[(size_t)(4 * b)], (int32_t)n_all, m >= 0 ? 1 : 0};
-    }
     const bool nothing_to_do = nb == 0 || dst->nztot == 0 || !any;
-    if (!nothing_to_do) {
-        HIP_TRY(hipStreamSynchronize(st));                                // (the kernel of an earlier call may still read the records)
-        if (int rc = ensure_scratch(&dst->d_repat, &dst->d_repat_bytes, rec.size() * sizeof(MoveBlock))) return rc;
-        HIP_TRY(hipMemcpy(dst->d_repat, rec.data(), rec.size() * sizeof(MoveBlock), hipMemcpyHostToDevice));
-    }
-    if (dt_ms) HIP_TRY(hipEventRecord(dst->ev0, st));
-    if (!nothing_to_do) {
-        launch_move_blocks(st, (const MoveBlock*)dst->d_repat, nb, S, D);
-        HIP_TRY(hipGetLastError());
-    }
-    if (dt_ms) {
-        HIP_TRY(hipEventRecord(dst->ev1, st));
-        HIP_TRY(hipEventSynchronize(dst->ev1));
-        HIP_TRY(hipEventElapsedTime(dt_ms, dst->ev0, dst->ev1));
-    }
-    return SPARTA_OK;
+    const DeviceCall call{me, dst->device, (hipStream_t)stream, true, dt_ms, nullptr, dst->ev0, dst->ev1, nothing_to_do};
+    return open_call(call, [&](hipStream_t st) -> int {
+        if (g_capturing) return capture_refusal("build and upload the records of the move (it synchronises)", me);
+        std::vector<int64_t> td, ts;
+        if (int rc = host_block_table(dst, me, td)) return rc;
+        if (int rc = host_block_table(src, me, ts)) return rc;
+        std::vector<MoveBlock> rec((size_t)nb);
+        for (int64_t b = 0; b < nb; b++) {
+            const int64_t n_all = td[(size_t)(4 * b + 2)];
+            if (n_all > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, std::string(me) + ": a block of 2^31 or more elements");
+            const int64_t m = map[b];
+            if (m >= 0 && ts[(size_t)(4 * m + 2)] != n_all) return fail(SPARTA_ERR_INVALID, std::string(me) + ": a mapped block differs in size (n_all) from its source block");
+            rec[(size_t)b] = MoveBlock{m >= 0 ? ts[(size_t)(4 * m)] : 0, td[(size_t)(4 * b)], (int32_t)n_all, m >= 0 ? 1 : 0};
+        }
+        if (!nothing_to_do) {
+            HIP_TRY(hipStreamSynchronize(st));                                // (the kernel of an earlier call may still read the records)
+            if (int rc = dst->d_repat.ensure(rec.size() * sizeof(MoveBlock))) return rc;
+            HIP_TRY(hipMemcpy(dst->d_repat, rec.data(), rec.size() * sizeof(MoveBlock), hipMemcpyHostToDevice));
+        }
+        return timed_launches(call, [&](hipStream_t) { launch_move_blocks(st, (const MoveBlock*)dst->d_repat, nb, S, D); });
+    });
     SPARTA_GUARD_END("sparta_vbs_move_blocks")
 }
 
@@ -3226,15 +2981,11 @@ int ensure_live_arrays(sparta_vbs_t* A, const char* entry) {
     for (int64_t ib = 0; ib < A->block_rows; ib++)
         if (A->h_row_part[(size_t)ib + 1] > A->h_row_part[(size_t)ib]) goff.push_back((int32_t)M.goff[(size_t)ib]);
     if ((int64_t)goff.size() != A->n_brows || M.first_block.back() != nb) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": the live-set maps disagree with the handle's block-rows");
-    auto alloc = [](void** ptr, size_t bytes) {
-        if (*ptr) { (void)hipFree(*ptr); *ptr = nullptr; }
-        return hipMalloc(ptr, std::max<size_t>(bytes, 16));
-    };
     A->live_n_groups = M.goff.back();
-    HIP_TRY(alloc((void**)&A->d_live_keep, (size_t)nb));
-    HIP_TRY(alloc((void**)&A->d_live_goff, goff.size() * sizeof(int32_t)));
-    HIP_TRY(alloc((void**)&A->d_live_groups, (size_t)A->live_n_groups * sizeof(int32_t)));
-    HIP_TRY(alloc((void**)&A->d_live_gcount, goff.size() * sizeof(int32_t)));
+    HIP_TRY(A->d_live_keep.alloc((size_t)nb, 16));
+    HIP_TRY(A->d_live_goff.alloc(goff.size(), 16));
+    HIP_TRY(A->d_live_groups.alloc((size_t)A->live_n_groups, 16));
+    HIP_TRY(A->d_live_gcount.alloc(goff.size(), 16));
     if (!goff.empty()) HIP_TRY(hipMemcpy(A->d_live_goff, goff.data(), goff.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     A->live_n_tlist = 0;
     A->live_block_cols = (int64_t)M.tptr.size() - 1;
@@ -3243,11 +2994,11 @@ int ensure_live_arrays(sparta_vbs_t* A, const char* entry) {
         if (A->live_block_cols * panels != A->n_t_items || (int64_t)M.tmap.size() != A->n_t_blocks)
             return fail(SPARTA_ERR_INVALID, std::string(entry) + ": the live-set maps disagree with the handle's block-column index");
         A->live_n_tlist = (int64_t)M.tmap.size();
-        HIP_TRY(alloc((void**)&A->d_live_tmap, M.tmap.size() * sizeof(int32_t)));
-        HIP_TRY(alloc((void**)&A->d_live_tids, M.tmap.size() * sizeof(int32_t)));
-        HIP_TRY(alloc((void**)&A->d_live_t_blocks, M.tmap.size() * sizeof(SpmmTBlock)));
-        HIP_TRY(alloc((void**)&A->d_live_tcount, (size_t)A->live_block_cols * sizeof(int32_t)));
-        HIP_TRY(alloc((void**)&A->d_live_t_items, (size_t)A->n_t_items * sizeof(SpmmTItem)));
+        HIP_TRY(A->d_live_tmap.alloc(M.tmap.size(), 16));
+        HIP_TRY(A->d_live_tids.alloc(M.tmap.size(), 16));
+        HIP_TRY(A->d_live_t_blocks.alloc(M.tmap.size(), 16));
+        HIP_TRY(A->d_live_tcount.alloc((size_t)A->live_block_cols, 16));
+        HIP_TRY(A->d_live_t_items.alloc((size_t)A->n_t_items, 16));
         if (!M.tmap.empty()) HIP_TRY(hipMemcpy(A->d_live_tmap, M.tmap.data(), M.tmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     A->live_built = true;
@@ -3287,8 +3038,8 @@ int ensure_live_word_map(sparta_vbs_t* A, const char* entry) {
         std::vector<int32_t> wmap(first.size());
         if (int rc = build_live_word_map(off.data(), nb, A->nztot, first.data(), ld.data(), (int64_t)first.size(), span, wmap.data())) return rc;
         A->live_n_words = (int64_t)wmap.size();
-        HIP_TRY(hipMalloc((void**)&A->d_live_wmap, std::max<size_t>(wmap.size() * sizeof(int32_t), 16)));
-        HIP_TRY(hipMalloc((void**)&A->d_live_words, std::max<size_t>(wmap.size() * sizeof(uint32_t), 16)));
+        HIP_TRY(A->d_live_wmap.alloc(wmap.size(), 16));
+        HIP_TRY(A->d_live_words.alloc(wmap.size(), 16));
         if (!wmap.empty()) HIP_TRY(hipMemcpy(A->d_live_wmap, wmap.data(), wmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     A->live_words_built = true;
@@ -3329,11 +3080,9 @@ int ensure_live_forward_arrays(sparta_vbs_t* A, const char* entry) {
                 return fail(SPARTA_ERR_INVALID, std::string(entry) + ": a worker range of the plan lies outside its step records");
         std::vector<int32_t> seg_last((size_t)n);
         live_forward_segments(hs.data(), n, ranges.data(), n_ranges, seg_last.data());
-        HIP_TRY(hipMalloc((void**)&A->d_fwd_steps, hs.size() * sizeof(StepRec)));
-        HIP_TRY(hipMalloc((void**)&A->d_fwd_wrange, ranges.size() * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void**)&A->d_fwd_seg_last, std::max<size_t>(seg_last.size() * sizeof(int32_t), 16)));
-        HIP_TRY(hipMemcpy(A->d_fwd_steps, hs.data(), hs.size() * sizeof(StepRec), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(A->d_fwd_wrange, ranges.data(), ranges.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(A->d_fwd_steps.upload(hs));
+        HIP_TRY(A->d_fwd_wrange.upload(ranges));
+        HIP_TRY(A->d_fwd_seg_last.alloc(seg_last.size(), 16));
         HIP_TRY(hipMemcpy(A->d_fwd_seg_last, seg_last.data(), seg_last.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         A->fwd_n_ranges = n_ranges; A->fwd_n_alloc = (int64_t)hs.size();
         A->live_fwd_ty = ty;
@@ -3362,17 +3111,15 @@ extern "C" int sparta_vbs_set_live_steps(sparta_vbs_t* A, int32_t enable, void* 
         A->live_steps = false;
         return SPARTA_OK;
     }
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, true);
-    if (int rc = ensure_live_step_arrays(A, entry)) return rc;
-    if (A->live_on && A->live_n_words > 0) {     // a set is installed already: the words follow from its snapshot
-        launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
-        HIP_TRY(hipGetLastError());
-    }
-    A->live_steps = true;
-    return SPARTA_OK;
+    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+        if (int rc = ensure_live_step_arrays(A, entry)) return rc;
+        if (A->live_on && A->live_n_words > 0) {     // a set is installed already: the words follow from its snapshot
+            launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
+            HIP_TRY(hipGetLastError());
+        }
+        A->live_steps = true;
+        return SPARTA_OK;
+    });
     SPARTA_GUARD_END("sparta_vbs_set_live_steps")
 }
 
@@ -3385,24 +3132,22 @@ extern "C" int sparta_vbs_set_live_blocks(sparta_vbs_t* A, const uint8_t* keep, 
         A->live_on = false;
         return SPARTA_OK;
     }
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, true);
-    if (int rc = ensure_live_arrays(A, entry)) return rc;
-    launch_live_sddmm(st, A->d_brows, A->n_brows, (int)A->w, keep, A->nblocks, A->d_live_keep, A->d_live_goff, A->d_live_groups, A->d_live_gcount);
-    if (A->create_flags & SPARTA_CREATE_TRANSPOSE)
-        launch_live_spmm_t(st, A->d_t_items, A->d_t_blocks, A->d_live_tmap, A->live_block_cols, (int)((A->w + 31) / 32), keep, A->d_live_t_items, A->d_live_t_blocks,
-                           A->d_live_tids, A->d_live_tcount);
-    // live steps: the words of the image kernel behind the snapshot, in stream order (written whether or not the switch is on right now, once they exist)
-    if (A->live_words_built && A->live_n_words > 0) launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
-    // live forward: the compacted records of the stream image behind the words (likewise written once they exist, whatever the switch says right now)
-    launch_live_forward_lists(A, st);
-    // the fp8 image with a live-block set: the compaction rewrote every position from the plain records, the exponent words go back in behind it
-    a8_live_place_scales(A, st);
-    HIP_TRY(hipGetLastError());
-    A->live_on = true;
-    return SPARTA_OK;
+    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+        if (int rc = ensure_live_arrays(A, entry)) return rc;
+        launch_live_sddmm(st, A->d_brows, A->n_brows, (int)A->w, keep, A->nblocks, A->d_live_keep, A->d_live_goff, A->d_live_groups, A->d_live_gcount);
+        if (A->create_flags & SPARTA_CREATE_TRANSPOSE)
+            launch_live_spmm_t(st, A->d_t_items, A->d_t_blocks, A->d_live_tmap, A->live_block_cols, (int)((A->w + 31) / 32), keep, A->d_live_t_items, A->d_live_t_blocks,
+                               A->d_live_tids, A->d_live_tcount);
+        // live steps: the words of the image kernel behind the snapshot, in stream order (written whether or not the switch is on right now, once they exist)
+        if (A->live_words_built && A->live_n_words > 0) launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
+        // live forward: the compacted records of the stream image behind the words (likewise written once they exist, whatever the switch says right now)
+        launch_live_forward_lists(A, st);
+        // the fp8 image with a live-block set: the compaction rewrote every position from the plain records, the exponent words go back in behind it
+        a8_live_place_scales(A, st);
+        HIP_TRY(hipGetLastError());
+        A->live_on = true;
+        return SPARTA_OK;
+    });
     SPARTA_GUARD_END("sparta_vbs_set_live_blocks")
 }
 
@@ -3428,17 +3173,13 @@ int ensure_score_arrays(sparta_vbs_t* A, const char* entry) {
         slots += tiles * nq;
     }
     if ((int64_t)soff.size() != A->n_brows || q != nb) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": the score maps disagree with the handle's block-rows");
-    auto alloc = [](void** ptr, size_t bytes) {
-        if (*ptr) { (void)hipFree(*ptr); *ptr = nullptr; }
-        return hipMalloc(ptr, std::max<size_t>(bytes, 16));
-    };
-    HIP_TRY(alloc((void**)&A->d_score_keep, (size_t)nb));
-    HIP_TRY(alloc((void**)&A->d_score_ones, (size_t)nb));
-    HIP_TRY(alloc((void**)&A->d_score_groups, (size_t)A->live_n_groups * sizeof(int32_t)));
-    HIP_TRY(alloc((void**)&A->d_score_gcount, soff.size() * sizeof(int32_t)));
-    HIP_TRY(alloc((void**)&A->d_score_soff, soff.size() * sizeof(int64_t)));
-    HIP_TRY(alloc((void**)&A->d_score_blocks, rec.size() * sizeof(ScoreBlock)));
-    HIP_TRY(alloc((void**)&A->d_score_slots, (size_t)slots * sizeof(double)));
+    HIP_TRY(A->d_score_keep.alloc((size_t)nb, 16));
+    HIP_TRY(A->d_score_ones.alloc((size_t)nb, 16));
+    HIP_TRY(A->d_score_groups.alloc((size_t)A->live_n_groups, 16));
+    HIP_TRY(A->d_score_gcount.alloc(soff.size(), 16));
+    HIP_TRY(A->d_score_soff.alloc(soff.size(), 16));
+    HIP_TRY(A->d_score_blocks.alloc(rec.size(), 16));
+    HIP_TRY(A->d_score_slots.alloc((size_t)slots, 16));
     if (nb > 0) {
         HIP_TRY(hipMemset(A->d_score_ones, 1, (size_t)nb));
         HIP_TRY(hipMemcpy(A->d_score_blocks, rec.data(), rec.size() * sizeof(ScoreBlock), hipMemcpyHostToDevice));
@@ -3467,32 +3208,24 @@ extern "C" int sparta_vbs_sddmm_block_ssq(sparta_vbs_t* A, const void* X, int64_
     if (A->dtype != SPARTA_F32 && ((ldx | ldy) & 1)) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": 16-bit handles need even ldx, ldy");
     if (A->nblocks == 0) return SPARTA_OK;
 
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, true);
-    if (g_capturing && dt_ms) return capture_refusal("time the product (dt_ms != NULL synchronises)", entry);
-    if (int rc = ensure_score_arrays(A, entry)) return rc;
+    const DeviceCall call{entry, A->device, (hipStream_t)stream, true, dt_ms, "the product", A->ev0, A->ev1};
+    return open_call(call, [&](hipStream_t st) -> int {
+        if (int rc = ensure_score_arrays(A, entry)) return rc;
 
-    SddmmParams p;
-    p.brows = A->d_brows; p.jab = A->d_jab; p.items = A->d_sd_items;
-    p.X = X; p.Y = Y; p.G = nullptr;
-    p.ldx = ldx; p.ldy = ldy; p.cols = A->cols;
-    p.k = k; p.w = (int32_t)A->w; p.accumulate = 0; p.pad = 0;
-    if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
-    // the lists of sel, by the kernel of the live set into the score call's own arrays: the live set of the handle, installed or not, is neither read nor written
-    launch_live_sddmm(st, A->d_brows, A->n_brows, (int)A->w, sel ? sel : A->d_score_ones, A->nblocks, A->d_score_keep, A->d_live_goff, A->d_score_groups,
-                      A->d_score_gcount);
-    launch_sddmm_score(A->dtype, (unsigned)A->n_sd_items, st, p, SddmmLive{A->d_score_groups, A->d_live_goff, A->d_score_gcount, A->d_score_keep},
-                       SddmmScore{A->d_score_slots, A->d_score_soff});
-    launch_sddmm_score_finish(st, A->d_score_blocks, A->nblocks, (int)A->w, A->d_score_keep, A->d_score_slots, ssq_out);
-    HIP_TRY(hipGetLastError());
-    if (dt_ms) {
-        HIP_TRY(hipEventRecord(A->ev1, st));
-        HIP_TRY(hipEventSynchronize(A->ev1));
-        HIP_TRY(hipEventElapsedTime(dt_ms, A->ev0, A->ev1));
-    }
-    return SPARTA_OK;
+        SddmmParams p;
+        p.brows = A->d_brows; p.jab = A->d_jab; p.items = A->d_sd_items;
+        p.X = X; p.Y = Y; p.G = nullptr;
+        p.ldx = ldx; p.ldy = ldy; p.cols = A->cols;
+        p.k = k; p.w = (int32_t)A->w; p.accumulate = 0; p.pad = 0;
+        return timed_launches(call, [&](hipStream_t) {
+            // the lists of sel, by the kernel of the live set into the score call's own arrays: the live set of the handle, installed or not, is neither read nor written
+            launch_live_sddmm(st, A->d_brows, A->n_brows, (int)A->w, sel ? sel : A->d_score_ones, A->nblocks, A->d_score_keep, A->d_live_goff, A->d_score_groups,
+                              A->d_score_gcount);
+            launch_sddmm_score(A->dtype, (unsigned)A->n_sd_items, st, p, SddmmLive{A->d_score_groups, A->d_live_goff, A->d_score_gcount, A->d_score_keep},
+                               SddmmScore{A->d_score_slots, A->d_score_soff});
+            launch_sddmm_score_finish(st, A->d_score_blocks, A->nblocks, (int)A->w, A->d_score_keep, A->d_score_slots, ssq_out);
+        });
+    });
     SPARTA_GUARD_END("sparta_vbs_sddmm_block_ssq")
 }
 
@@ -3509,18 +3242,16 @@ extern "C" int sparta_vbs_set_live_forward(sparta_vbs_t* A, int32_t enable, void
     }
     if (A->a8_on)
         return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the fp8 weight image is on (sparta_vbs_set_forward_a8) and the two do not combine -- switch it off first");
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, true);
-    if (int rc = ensure_live_forward_arrays(A, entry)) return rc;
-    if (A->live_on && A->live_fwd_ty >= 0) {     // a set is installed already: words and lists follow from its snapshot
-        launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
-        launch_live_forward_lists(A, st);
-        HIP_TRY(hipGetLastError());
-    }
-    A->live_fwd = true;
-    return SPARTA_OK;
+    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+        if (int rc = ensure_live_forward_arrays(A, entry)) return rc;
+        if (A->live_on && A->live_fwd_ty >= 0) {     // a set is installed already: words and lists follow from its snapshot
+            launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
+            launch_live_forward_lists(A, st);
+            HIP_TRY(hipGetLastError());
+        }
+        A->live_fwd = true;
+        return SPARTA_OK;
+    });
     SPARTA_GUARD_END("sparta_vbs_set_live_forward")
 }
 
@@ -3540,16 +3271,14 @@ extern "C" int sparta_vbs_live_forward_info(sparta_vbs_t* A, int64_t* info_out, 
     info_out[6] = A->n_split;
     info_out[7] = A->live_fwd_built && ty >= 0 ? A->fwd_n_ranges : 0;
     if (!A->live_on || !A->live_fwd_built || ty < 0) return SPARTA_OK;
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, true);
-    if (g_capturing) return capture_refusal("read the live ranges back (synchronises)", entry);
-    HIP_TRY(hipStreamSynchronize(st));
-    std::vector<int32_t> ranges((size_t)A->fwd_n_ranges * 2);
-    if (!ranges.empty()) HIP_TRY(hipMemcpy(ranges.data(), A->d_fwd_wrange, ranges.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (int64_t r = 0; r < A->fwd_n_ranges; r++) info_out[5] += std::max(0, ranges[(size_t)(2 * r + 1)] - ranges[(size_t)(2 * r)]);
-    return SPARTA_OK;
+    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+        if (g_capturing) return capture_refusal("read the live ranges back (synchronises)", entry);
+        HIP_TRY(hipStreamSynchronize(st));
+        std::vector<int32_t> ranges((size_t)A->fwd_n_ranges * 2);
+        if (!ranges.empty()) HIP_TRY(hipMemcpy(ranges.data(), A->d_fwd_wrange, ranges.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int64_t r = 0; r < A->fwd_n_ranges; r++) info_out[5] += std::max(0, ranges[(size_t)(2 * r + 1)] - ranges[(size_t)(2 * r)]);
+        return SPARTA_OK;
+    });
     SPARTA_GUARD_END("sparta_vbs_live_forward_info")
 }
 
@@ -3561,24 +3290,22 @@ extern "C" int sparta_vbs_live_forward_lists_get(sparta_vbs_t* A, void* steps_pl
     if (int rc = prune_handle_check(A, entry)) return rc;
     if (!A->live_on) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": no live set is installed");
     if (!A->live_fwd_built || A->live_fwd_ty < 0) return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the handle has no live forward lists");
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, true);
-    if (g_capturing) return capture_refusal("read the live forward lists back (synchronises)", entry);
-    HIP_TRY(hipStreamSynchronize(st));
-    const int ty = A->live_fwd_ty;
-    const size_t n = (size_t)A->n_steps[ty], nr = (size_t)A->fwd_n_ranges;
-    if (steps_plain && n > 0) HIP_TRY(hipMemcpy(steps_plain, A->d_steps[ty], n * sizeof(StepRec), hipMemcpyDeviceToHost));
-    if (steps_live && n > 0) HIP_TRY(hipMemcpy(steps_live, A->d_fwd_steps, n * sizeof(StepRec), hipMemcpyDeviceToHost));
-    if (ranges_plain && nr > 0) HIP_TRY(hipMemcpy(ranges_plain, A->d_wrange[ty], nr * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (ranges_live && nr > 0) HIP_TRY(hipMemcpy(ranges_live, A->d_fwd_wrange, nr * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (live_bits && n > 0) {
-        std::vector<uint32_t> words(2 * n);
-        HIP_TRY(hipMemcpy(words.data(), A->d_live_words, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < words.size(); i++) live_bits[i] = words[i] != 0u ? 1 : 0;
-    }
-    return SPARTA_OK;
+    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+        if (g_capturing) return capture_refusal("read the live forward lists back (synchronises)", entry);
+        HIP_TRY(hipStreamSynchronize(st));
+        const int ty = A->live_fwd_ty;
+        const size_t n = (size_t)A->n_steps[ty], nr = (size_t)A->fwd_n_ranges;
+        if (steps_plain && n > 0) HIP_TRY(hipMemcpy(steps_plain, A->d_steps[ty], n * sizeof(StepRec), hipMemcpyDeviceToHost));
+        if (steps_live && n > 0) HIP_TRY(hipMemcpy(steps_live, A->d_fwd_steps, n * sizeof(StepRec), hipMemcpyDeviceToHost));
+        if (ranges_plain && nr > 0) HIP_TRY(hipMemcpy(ranges_plain, A->d_wrange[ty], nr * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (ranges_live && nr > 0) HIP_TRY(hipMemcpy(ranges_live, A->d_fwd_wrange, nr * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (live_bits && n > 0) {
+            std::vector<uint32_t> words(2 * n);
+            HIP_TRY(hipMemcpy(words.data(), A->d_live_words, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < words.size(); i++) live_bits[i] = words[i] != 0u ? 1 : 0;
+        }
+        return SPARTA_OK;
+    });
     SPARTA_GUARD_END("sparta_vbs_live_forward_lists_get")
 }
 
@@ -3602,10 +3329,9 @@ int ensure_a8_arrays(sparta_vbs_t* A, const char* entry) {
         if (hs[(size_t)q].a_off != A->upd_base[ty] + q * slice)
             return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the slices of the stream image are not in step order");
     A->a8_bytes = A->a_bytes / (int64_t)sizeof(uint16_t);      // one byte per element of the 16-bit image, its padding included
-    HIP_TRY(hipMalloc((void**)&A->d_a8, (size_t)A->a8_bytes));
+    HIP_TRY(A->d_a8.alloc((size_t)A->a8_bytes));
     HIP_TRY(hipMemset(A->d_a8, 0, (size_t)A->a8_bytes));
-    HIP_TRY(hipMalloc((void**)&A->d_a8_steps, hs.size() * sizeof(StepRec)));
-    HIP_TRY(hipMemcpy(A->d_a8_steps, hs.data(), hs.size() * sizeof(StepRec), hipMemcpyHostToDevice));
+    HIP_TRY(A->d_a8_steps.upload(hs));
     A->a8_n_groups = n * (ty ? 2 : 1);
     A->a8_ty = ty;
     A->a8_built = true;
@@ -3629,14 +3355,12 @@ extern "C" int sparta_vbs_set_forward_a8(sparta_vbs_t* A, int32_t enable, void* 
         return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": needs a 16-bit handle made with SPARTA_CREATE_UPDATABLE (sparta_vbs_create_range_ex)");
     if (A->live_fwd)
         return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": live forward is on (sparta_vbs_set_live_forward) and the two do not combine -- switch it off first");
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, true);
-    if (int rc = ensure_a8_arrays(A, entry)) return rc;
-    if (!A->a8_on) A->a8_valid = false;          // invalid until the next write of values
-    A->a8_on = true;
-    return SPARTA_OK;
+    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+        if (int rc = ensure_a8_arrays(A, entry)) return rc;
+        if (!A->a8_on) A->a8_valid = false;          // invalid until the next write of values
+        A->a8_on = true;
+        return SPARTA_OK;
+    });
     SPARTA_GUARD_END("sparta_vbs_set_forward_a8")
 }
 
@@ -3672,21 +3396,19 @@ extern "C" int sparta_vbs_set_a8_live(sparta_vbs_t* A, int32_t enable, void* str
     if (!A->a8_on || !A->a8_built || A->a8_ty < 0)
         return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the fp8 weight image is off -- switch it on first (sparta_vbs_set_forward_a8)");
     if (int rc = prune_handle_check(A, entry)) return rc;
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, true);
-    if (int rc = ensure_live_forward_arrays(A, entry)) return rc;      // the word map, seg_last and the compacted arrays of live forward: the same ones
-    if (A->live_fwd_ty != A->a8_ty)
-        return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the stream image that has the fp8 image has no live forward lists");
-    A->a8_live = true;
-    if (A->live_on) {                            // a set is installed already: words, lists and scales follow from its snapshot
-        launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
-        launch_live_forward_lists(A, st);
-        a8_live_place_scales(A, st);
-        HIP_TRY(hipGetLastError());
-    }
-    return SPARTA_OK;
+    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+        if (int rc = ensure_live_forward_arrays(A, entry)) return rc;      // the word map, seg_last and the compacted arrays of live forward: the same ones
+        if (A->live_fwd_ty != A->a8_ty)
+            return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the stream image that has the fp8 image has no live forward lists");
+        A->a8_live = true;
+        if (A->live_on) {                            // a set is installed already: words, lists and scales follow from its snapshot
+            launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
+            launch_live_forward_lists(A, st);
+            a8_live_place_scales(A, st);
+            HIP_TRY(hipGetLastError());
+        }
+        return SPARTA_OK;
+    });
     SPARTA_GUARD_END("sparta_vbs_set_a8_live")
 }
 
@@ -3704,16 +3426,14 @@ extern "C" int sparta_vbs_a8_live_info(sparta_vbs_t* A, int64_t* info_out, void*
     info_out[3] = ty >= 0 ? A->n_steps[ty] : 0;
     info_out[5] = A->a8_live_launches;
     if (!A->live_on || !lists) return SPARTA_OK;
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, true);
-    if (g_capturing) return capture_refusal("read the live ranges back (synchronises)", entry);
-    HIP_TRY(hipStreamSynchronize(st));
-    std::vector<int32_t> ranges((size_t)A->fwd_n_ranges * 2);
-    if (!ranges.empty()) HIP_TRY(hipMemcpy(ranges.data(), A->d_fwd_wrange, ranges.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (int64_t r = 0; r < A->fwd_n_ranges; r++) info_out[4] += std::max(0, ranges[(size_t)(2 * r + 1)] - ranges[(size_t)(2 * r)]);
-    return SPARTA_OK;
+    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+        if (g_capturing) return capture_refusal("read the live ranges back (synchronises)", entry);
+        HIP_TRY(hipStreamSynchronize(st));
+        std::vector<int32_t> ranges((size_t)A->fwd_n_ranges * 2);
+        if (!ranges.empty()) HIP_TRY(hipMemcpy(ranges.data(), A->d_fwd_wrange, ranges.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int64_t r = 0; r < A->fwd_n_ranges; r++) info_out[4] += std::max(0, ranges[(size_t)(2 * r + 1)] - ranges[(size_t)(2 * r)]);
+        return SPARTA_OK;
+    });
     SPARTA_GUARD_END("sparta_vbs_a8_live_info")
 }
 
@@ -3723,41 +3443,39 @@ extern "C" int sparta_vbs_a8_get(sparta_vbs_t* A, uint8_t* codes, int32_t* exps,
     const char* entry = "sparta_vbs_a8_get";
     if (!A) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": NULL handle");
     if (!A->a8_built || A->a8_ty < 0) return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the handle has no fp8 image (sparta_vbs_set_forward_a8 was never on)");
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, true);
-    if (g_capturing) return capture_refusal("read the fp8 image back (synchronises)", entry);
-    HIP_TRY(hipStreamSynchronize(st));
-    const int ty = A->a8_ty, tms = ty ? 64 : 32, kp = A->kp16;
-    const int64_t n = A->n_steps[ty], slice = (int64_t)tms * kp;
-    std::vector<UpdSlice> map((size_t)n);
-    std::vector<StepRec> recs((size_t)n);
-    std::vector<uint8_t> img((size_t)(n * slice));
-    if (n > 0) {
-        HIP_TRY(hipMemcpy(map.data(), A->d_upd_map[ty], map.size() * sizeof(UpdSlice), hipMemcpyDeviceToHost));
-        if (exps) HIP_TRY(hipMemcpy(recs.data(), A->d_a8_steps, recs.size() * sizeof(StepRec), hipMemcpyDeviceToHost));
-        if (codes) HIP_TRY(hipMemcpy(img.data(), A->d_a8 + A->upd_base[ty], img.size(), hipMemcpyDeviceToHost));
-    }
-    for (int64_t s = 0; s < n; s++) {
-        const UpdSlice& u = map[(size_t)s];
-        const uint32_t word = (uint32_t)recs[(size_t)s].pad;
-        for (int rr = 0; rr < tms; rr++) {
-            int64_t at0 = -1, ld = 0;                           // (the rows vbs_a8quant_kernel reads, see k_h16_a8.hip)
-            if (rr < u.rows_lo) { at0 = u.off_lo + rr; ld = u.h_lo; }
-            else if (rr >= 32 && rr - 32 < u.rows_hi) { at0 = u.off_hi + (rr - 32); ld = u.h_hi; }
-            if (at0 < 0) continue;
-            const int hf = rr >> 5;
-            for (int k = 0; k < kp; k++) {
-                const int64_t i = at0 + (int64_t)k * ld;
-                if (i < 0 || i >= A->nztot) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": the slice map points outside the stored elements");
-                if (codes) codes[i] = img[(size_t)(s * slice + ((int64_t)(k / 8) * tms + rr) * 8 + (k & 7))];
-                if (exps) exps[i] = (int32_t)((word >> (16 * hf)) & 0xffffu) - 127;
-                if (group) group[i] = (int32_t)(s * (tms / 32) + hf);
+    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+        if (g_capturing) return capture_refusal("read the fp8 image back (synchronises)", entry);
+        HIP_TRY(hipStreamSynchronize(st));
+        const int ty = A->a8_ty, tms = ty ? 64 : 32, kp = A->kp16;
+        const int64_t n = A->n_steps[ty], slice = (int64_t)tms * kp;
+        std::vector<UpdSlice> map((size_t)n);
+        std::vector<StepRec> recs((size_t)n);
+        std::vector<uint8_t> img((size_t)(n * slice));
+        if (n > 0) {
+            HIP_TRY(hipMemcpy(map.data(), A->d_upd_map[ty], map.size() * sizeof(UpdSlice), hipMemcpyDeviceToHost));
+            if (exps) HIP_TRY(hipMemcpy(recs.data(), A->d_a8_steps, recs.size() * sizeof(StepRec), hipMemcpyDeviceToHost));
+            if (codes) HIP_TRY(hipMemcpy(img.data(), A->d_a8 + A->upd_base[ty], img.size(), hipMemcpyDeviceToHost));
+        }
+        for (int64_t s = 0; s < n; s++) {
+            const UpdSlice& u = map[(size_t)s];
+            const uint32_t word = (uint32_t)recs[(size_t)s].pad;
+            for (int rr = 0; rr < tms; rr++) {
+                int64_t at0 = -1, ld = 0;                           // (the rows vbs_a8quant_kernel reads, see k_h16_a8.hip)
+                if (rr < u.rows_lo) { at0 = u.off_lo + rr; ld = u.h_lo; }
+                else if (rr >= 32 && rr - 32 < u.rows_hi) { at0 = u.off_hi + (rr - 32); ld = u.h_hi; }
+                if (at0 < 0) continue;
+                const int hf = rr >> 5;
+                for (int k = 0; k < kp; k++) {
+                    const int64_t i = at0 + (int64_t)k * ld;
+                    if (i < 0 || i >= A->nztot) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": the slice map points outside the stored elements");
+                    if (codes) codes[i] = img[(size_t)(s * slice + ((int64_t)(k / 8) * tms + rr) * 8 + (k & 7))];
+                    if (exps) exps[i] = (int32_t)((word >> (16 * hf)) & 0xffffu) - 127;
+                    if (group) group[i] = (int32_t)(s * (tms / 32) + hf);
+                }
             }
         }
-    }
-    return SPARTA_OK;
+        return SPARTA_OK;
+    });
     SPARTA_GUARD_END("sparta_vbs_a8_get")
 }
 
@@ -3807,21 +3525,21 @@ namespace {
 
 // the device state of an installed live set on the host (synchronises `st`)
 struct LiveDownload { std::vector<uint8_t> keep; std::vector<int32_t> groups, gcount, tids, tcount; };
-int live_download(sparta_vbs_t* A, const char* entry, hipStream_t st, LiveDownload& D) {
-    using sparta::fail;
-    const CaptureScope capture(st, true);
-    if (g_capturing) return capture_refusal("read the live set back (synchronises)", entry);
-    HIP_TRY(hipStreamSynchronize(st));
-    auto get = [](auto& vec, const void* src, int64_t n) {
-        vec.resize((size_t)n);
-        return n > 0 ? hipMemcpy(vec.data(), src, (size_t)n * sizeof(vec[0]), hipMemcpyDeviceToHost) : hipSuccess;
-    };
-    HIP_TRY(get(D.keep, A->d_live_keep, A->nblocks));
-    HIP_TRY(get(D.groups, A->d_live_groups, A->live_n_groups));
-    HIP_TRY(get(D.gcount, A->d_live_gcount, A->n_brows));
-    HIP_TRY(get(D.tids, A->d_live_tids, A->live_n_tlist));
-    HIP_TRY(get(D.tcount, A->d_live_tcount, (A->create_flags & SPARTA_CREATE_TRANSPOSE) ? A->live_block_cols : 0));
-    return SPARTA_OK;
+int live_download(sparta_vbs_t* A, const char* entry, void* stream, LiveDownload& D) {
+    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+        if (g_capturing) return capture_refusal("read the live set back (synchronises)", entry);
+        HIP_TRY(hipStreamSynchronize(st));
+        auto get = [](auto& vec, const void* src, int64_t n) {
+            vec.resize((size_t)n);
+            return n > 0 ? hipMemcpy(vec.data(), src, (size_t)n * sizeof(vec[0]), hipMemcpyDeviceToHost) : hipSuccess;
+        };
+        HIP_TRY(get(D.keep, A->d_live_keep, A->nblocks));
+        HIP_TRY(get(D.groups, A->d_live_groups, A->live_n_groups));
+        HIP_TRY(get(D.gcount, A->d_live_gcount, A->n_brows));
+        HIP_TRY(get(D.tids, A->d_live_tids, A->live_n_tlist));
+        HIP_TRY(get(D.tcount, A->d_live_tcount, (A->create_flags & SPARTA_CREATE_TRANSPOSE) ? A->live_block_cols : 0));
+        return SPARTA_OK;
+    });
 }
 
 }  // namespace
@@ -3836,10 +3554,8 @@ extern "C" int sparta_vbs_live_info(sparta_vbs_t* A, int64_t* info_out, void* st
     info_out[1] = A->nblocks;
     info_out[7] = A->live_steps ? 1 : 0;
     if (!A->live_on) return SPARTA_OK;
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
     LiveDownload D;
-    if (int rc = live_download(A, entry, (hipStream_t)stream, D)) return rc;
+    if (int rc = live_download(A, entry, stream, D)) return rc;
     info_out[0] = 1;
     for (uint8_t k : D.keep) info_out[2] += k != 0;
     info_out[3] = A->live_n_groups;
@@ -3856,10 +3572,8 @@ extern "C" int sparta_vbs_live_lists_get(sparta_vbs_t* A, int32_t* sd_groups, in
     const char* entry = "sparta_vbs_live_lists_get";
     if (int rc = prune_handle_check(A, entry)) return rc;
     if (!A->live_on) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": no live set is installed");
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, std::string(entry) + ": hipSetDevice failed");
     LiveDownload D;
-    if (int rc = live_download(A, entry, (hipStream_t)stream, D)) return rc;
+    if (int rc = live_download(A, entry, stream, D)) return rc;
     if (sd_groups && !D.groups.empty()) std::memcpy(sd_groups, D.groups.data(), D.groups.size() * sizeof(int32_t));
     if (sd_count) {                              // per block-row of the handle; the device keeps the block-rows of height > 0 only
         size_t at = 0;
@@ -3915,51 +3629,41 @@ int spmm_t_impl(sparta_vbs_t* A, const void* X, int64_t ldx, int32_t n_cols, flo
     const bool h16 = A->dtype != SPARTA_F32;
     if (h16 && ptr_space == SPARTA_PTR_DEVICE && (ldx & 1)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_spmm_t: 16-bit handles need an even ldx");
 
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, "sparta_vbs_spmm_t: hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, ptr_space == SPARTA_PTR_DEVICE);
-    if (g_capturing && dt_ms) return capture_refusal("time the product (dt_ms != NULL synchronises)", "sparta_vbs_spmm_t");
-
-    const void* dX = X;
-    float* dC = Ct;
-    int64_t kx = ldx;
-    const size_t x_elems = (size_t)ldx * (size_t)(n_cols - 1) + (size_t)A->rows, c_elems = (size_t)ldo * (size_t)(n_cols - 1) + (size_t)A->cols;
-    if (ptr_space == SPARTA_PTR_HOST) {
-        // host in, host out: X and Ct staged in one device buffer (Ct whole, so that its padding rows come back as they went); 16-bit handles round X on the device
-        if (int rc = ensure_scratch(&A->d_t_ws, &A->d_t_ws_bytes, (x_elems + c_elems) * sizeof(float))) return rc;
-        float* ws = (float*)A->d_t_ws;
-        HIP_TRY(hipMemcpyAsync(ws, X, x_elems * sizeof(float), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(ws + x_elems, Ct, c_elems * sizeof(float), hipMemcpyHostToDevice, st));
-        dX = ws; dC = ws + x_elems;
-        if (h16) {
-            kx = (A->rows + 7) / 8 * 8;
-            if (int rc = ensure_scratch(&A->d_t_h16, &A->d_t_h16_bytes, (size_t)kx * (size_t)n_cols * sizeof(uint16_t))) return rc;
-            launch_convert_h16(A->dtype == SPARTA_BF16, st, ws, ldx, A->rows, n_cols, (uint16_t*)A->d_t_h16, kx);
-            HIP_TRY(hipGetLastError());
-            dX = A->d_t_h16;
+    const DeviceCall call{"sparta_vbs_spmm_t", A->device, (hipStream_t)stream, ptr_space == SPARTA_PTR_DEVICE, dt_ms, "the product", A->ev0, A->ev1};
+    return open_call(call, [&](hipStream_t st) -> int {
+        const void* dX = X;
+        float* dC = Ct;
+        int64_t kx = ldx;
+        const size_t x_elems = (size_t)ldx * (size_t)(n_cols - 1) + (size_t)A->rows, c_elems = (size_t)ldo * (size_t)(n_cols - 1) + (size_t)A->cols;
+        if (ptr_space == SPARTA_PTR_HOST) {
+            // host in, host out: X and Ct staged in one device buffer (Ct whole, so that its padding rows come back as they went); 16-bit handles round X on the device
+            if (int rc = A->d_t_ws.ensure((x_elems + c_elems) * sizeof(float))) return rc;
+            float* ws = (float*)A->d_t_ws;
+            HIP_TRY(hipMemcpyAsync(ws, X, x_elems * sizeof(float), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ws + x_elems, Ct, c_elems * sizeof(float), hipMemcpyHostToDevice, st));
+            dX = ws; dC = ws + x_elems;
+            if (h16) {
+                kx = (A->rows + 7) / 8 * 8;
+                if (int rc = A->d_t_h16.ensure((size_t)kx * (size_t)n_cols * sizeof(uint16_t))) return rc;
+                launch_convert_h16(A->dtype == SPARTA_BF16, st, ws, ldx, A->rows, n_cols, (uint16_t*)A->d_t_h16, kx);
+                HIP_TRY(hipGetLastError());
+                dX = A->d_t_h16;
+            }
         }
-    }
-    SpmmTParams p;
-    p.items = A->d_t_items; p.blocks = A->d_t_blocks;
-    if (A->live_on) { p.items = A->d_live_t_items; p.blocks = A->d_live_t_blocks; }      // the same kernels on the compacted lists (an empty list writes the zeros)
-    p.A = h16 ? (const void*)A->d_t_A : (const void*)A->d_A;
-    p.X = dX; p.Ct = dC;
-    p.ldx = kx; p.ldo = ldo; p.cols = A->cols;
-    p.n_cols = n_cols; p.w = (int32_t)A->w; p.accumulate = accumulate != 0; p.pad = 0;
-    if (dt_ms) HIP_TRY(hipEventRecord(A->ev0, st));
-    launch_spmm_t(A->dtype, (unsigned)A->n_t_items, st, p);
-    HIP_TRY(hipGetLastError());
-    if (dt_ms) {
-        HIP_TRY(hipEventRecord(A->ev1, st));
-        HIP_TRY(hipEventSynchronize(A->ev1));
-        HIP_TRY(hipEventElapsedTime(dt_ms, A->ev0, A->ev1));
-    }
-    if (ptr_space == SPARTA_PTR_HOST) {
-        HIP_TRY(hipMemcpyAsync(Ct, dC, c_elems * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return SPARTA_OK;
+        SpmmTParams p;
+        p.items = A->d_t_items; p.blocks = A->d_t_blocks;
+        if (A->live_on) { p.items = A->d_live_t_items; p.blocks = A->d_live_t_blocks; }      // the same kernels on the compacted lists (an empty list writes the zeros)
+        p.A = h16 ? (const void*)A->d_t_A : (const void*)A->d_A;
+        p.X = dX; p.Ct = dC;
+        p.ldx = kx; p.ldo = ldo; p.cols = A->cols;
+        p.n_cols = n_cols; p.w = (int32_t)A->w; p.accumulate = accumulate != 0; p.pad = 0;
+        if (int rc = timed_launches(call, [&](hipStream_t) { launch_spmm_t(A->dtype, (unsigned)A->n_t_items, st, p); })) return rc;
+        if (ptr_space == SPARTA_PTR_HOST) {
+            HIP_TRY(hipMemcpyAsync(Ct, dC, c_elems * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        return SPARTA_OK;
+    });
 }
 
 }  // namespace

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -377,118 +378,190 @@ struct DeviceGuard {
     }
 };
 
+// ---- the single owners of device memory and events: nothing else in the library spells hipMalloc / hipFree / hipEventCreate / hipEventDestroy --------
+// Owners free in their destructors: destroy one with its device current (DeviceGuard).  DevBuf keeps the two process-wide counters that
+// sparta_debug_device_allocs reads: allocations held right now, and their bytes as asked of hipMalloc.
+inline std::atomic<int64_t> g_dev_live_count{0}, g_dev_live_bytes{0};
+
+// one allocation of T (uint8_t: a byte buffer).  Converts to T* so that launches and `if (A->d_x)` read as with a raw pointer; a reinterpreting site says .get()
+template <class T>
+struct DevBuf {
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr; o.bytes_ = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p_ = o.p_; bytes_ = o.bytes_; o.p_ = nullptr; o.bytes_ = 0; } return *this; }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { reset(); }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    size_t bytes() const { return bytes_; }
+    void reset() {
+        if (p_) { (void)hipFree(p_); g_dev_live_count--; g_dev_live_bytes -= (int64_t)bytes_; }
+        p_ = nullptr; bytes_ = 0;
+    }
+    // frees what it held first: a builder that failed half-way and is called again leaks nothing
+    hipError_t alloc(size_t n_elems, size_t min_bytes = 0) {
+        reset();
+        const size_t b = std::max(n_elems * sizeof(T), min_bytes);
+        const hipError_t e = hipMalloc((void**)&p_, b);
+        if (e != hipSuccess) p_ = nullptr;
+        if (p_) { bytes_ = b; g_dev_live_count++; g_dev_live_bytes += (int64_t)b; }      // (an empty allocation holds nothing)
+        return e;
+    }
+    // n elements of src behind a fresh allocation of n + pad_elems, the padding zeroed: one size for the allocation and the copy
+    hipError_t upload(const T* src, size_t n, size_t pad_elems = 0) {
+        hipError_t e = alloc(n + pad_elems);
+        if (e == hipSuccess && pad_elems > 0) e = hipMemset(p_ + n, 0, pad_elems * sizeof(T));
+        if (e == hipSuccess && n > 0) e = hipMemcpy(p_, src, n * sizeof(T), hipMemcpyHostToDevice);
+        return e;
+    }
+    hipError_t upload(const std::vector<T>& v, size_t pad_elems = 0) { return upload(v.data(), v.size(), pad_elems); }
+private:
+    T* p_ = nullptr;
+    size_t bytes_ = 0;
+};
+
+// set for the duration of a call whose stream is being captured into a graph (CaptureScope, vbs_capi.cpp): what allocates, synchronises or times then
+// fails with SPARTA_ERR_UNSUPPORTED instead of breaking the capture
+inline thread_local bool g_capturing = false;
+inline int capture_refusal(const char* what, const char* entry = "sparta_vbs_spmm") {
+    return sparta::fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the stream is being captured and this call still has to " + what +
+                                                 " -- run it once outside the capture first");
+}
+
+// grow-only scratch of a handle: ensure(need) keeps what is large enough, otherwise frees and allocates `need` bytes (never under capture).  Converts to
+// any pointer type, as the void* it replaces was cast at every use.
+struct DevScratch {
+    size_t bytes() const { return buf_.bytes(); }
+    void* get() const { return buf_.get(); }
+    template <class U> operator U*() const { return (U*)buf_.get(); }
+    explicit operator bool() const { return buf_.get() != nullptr; }
+    int ensure(size_t need) {
+        if (buf_.bytes() >= need) return SPARTA_OK;
+        if (g_capturing) return capture_refusal("allocate scratch memory");
+        HIP_TRY(buf_.alloc(need));
+        return SPARTA_OK;
+    }
+private:
+    DevBuf<uint8_t> buf_;
+};
+
+struct DevEvent {
+    DevEvent() = default;
+    DevEvent(const DevEvent&) = delete;
+    DevEvent& operator=(const DevEvent&) = delete;
+    ~DevEvent() { if (ev_) (void)hipEventDestroy(ev_); }
+    hipError_t create() { return ev_ ? hipSuccess : hipEventCreate(&ev_); }
+    operator hipEvent_t() const { return ev_; }
+private:
+    hipEvent_t ev_ = nullptr;
+};
+
 }  // namespace sparta_dev
 
 struct sparta_vbs {
     int device = 0, dtype = SPARTA_F32;
     int64_t rows = 0, cols = 0, block_rows = 0, w = 0, nblocks = 0, nztot = 0;
-    float* d_A = nullptr;                    // fp32: the reference's mab; 16-bit handles: packed slices (see sparta_vbs_create)
+    sparta_dev::DevBuf<float> d_A;                    // fp32: the reference's mab; 16-bit handles: packed slices (see sparta_vbs_create)
     int kp16 = 0;                            // 16-bit handles: k depth of a step (32 or 64)
-    int32_t* d_jab = nullptr;
-    sparta_dev::TileDesc* d_tiles[4] = {nullptr, nullptr, nullptr, nullptr};   // classes 16, 32, 64, 128
+    sparta_dev::DevBuf<int32_t> d_jab;
+    sparta_dev::DevBuf<sparta_dev::TileDesc> d_tiles[4];   // classes 16, 32, 64, 128
     int64_t n_tiles[4] = {0, 0, 0, 0};       // launch entries (real tiles + padding)
     int64_t n_real_tiles[4] = {0, 0, 0, 0};
-    sparta_dev::BlockRowDesc* d_brows = nullptr;
+    sparta_dev::DevBuf<sparta_dev::BlockRowDesc> d_brows;
     int64_t n_brows = 0;
     int64_t exec_area = 0;
     int64_t a_bytes = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t cev[4][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
+    sparta_dev::DevEvent ev0, ev1;
+    sparta_dev::DevEvent cev[4][2];
     bool class_timing = false;
     bool class_ran[4] = {false, false, false, false};
     // stream plan (w % 32 == 0): see vbs_spmm_f32_stream_kernel
-    sparta_dev::StepRec* d_steps[2] = {nullptr, nullptr};      // per tile type: [0] <= 32 rows, [1] 33..64 rows
+    sparta_dev::DevBuf<sparta_dev::StepRec> d_steps[2];      // per tile type: [0] <= 32 rows, [1] 33..64 rows
     std::vector<sparta_dev::StepRec> h_steps[2];               // host copies (padded), source of the gathered-B variants
-    sparta_dev::StepRec* d_steps_g[2] = {nullptr, nullptr};    // step lists for sparta_vbs_spmm_gathered with shard_rows == g_shard_rows
+    sparta_dev::DevBuf<sparta_dev::StepRec> d_steps_g[2];    // step lists for sparta_vbs_spmm_gathered with shard_rows == g_shard_rows
     int64_t g_shard_rows = 0;
-    int32_t* d_wrange[2] = {nullptr, nullptr};
-    sparta_dev::FixRec* d_fix = nullptr;
+    sparta_dev::DevBuf<int32_t> d_wrange[2];
+    sparta_dev::DevBuf<sparta_dev::FixRec> d_fix;
     std::vector<std::pair<int64_t, int64_t>> zero_ranges;   // long runs of rows without blocks (local C rows), see vbs_zero_rows_kernel
-    int32_t* d_fix_slots = nullptr;
+    sparta_dev::DevBuf<int32_t> d_fix_slots;
     int64_t n_steps[2] = {0, 0};
     int32_t n_workers = 0, n_fix = 0, n_split = 0, n_slots = 0;
     int32_t max_tile_slots = 0;            // most partial images of one split tile
-    int32_t* d_big_fix = nullptr;          // fix records with more than 2 * kFixGroup images (group stage)
+    sparta_dev::DevBuf<int32_t> d_big_fix;          // fix records with more than 2 * kFixGroup images (group stage)
     int32_t n_big_fix = 0;
-    void* d_ws = nullptr;
-    size_t d_ws_bytes = 0;
+    sparta_dev::DevScratch d_ws;
     int64_t n_plan_tiles[2] = {0, 0};             // see StreamPlanHost
     bool tiles_row_aligned[2] = {true, true};
     bool wide16 = false;                      // the 16-bit one-tile plan holds two sub-worker ranges per workgroup (vbs_spmm_h16_direct_kernel, WC = 64)
-    float* d_a_frag = nullptr;                    // A of the one-tile plan in fragment order (k_f32_direct.hip) or nullptr
-    float* d_a_pack = nullptr;                    // packed handles (k_f32_packed.hip): A per PACKED step, instead of d_a_frag
-    sparta_dev::StepRec* d_psteps = nullptr;      // ... the packed steps, their worker ranges, and where every block of d_steps[0] sits in d_a_pack
-    int32_t* d_pwrange = nullptr;
-    sparta_dev::PackLoc* d_pack_loc = nullptr;
+    sparta_dev::DevBuf<float> d_a_frag;                    // A of the one-tile plan in fragment order (k_f32_direct.hip) or nullptr
+    sparta_dev::DevBuf<float> d_a_pack;                    // packed handles (k_f32_packed.hip): A per PACKED step, instead of d_a_frag
+    sparta_dev::DevBuf<sparta_dev::StepRec> d_psteps;      // ... the packed steps, their worker ranges, and where every block of d_steps[0] sits in d_a_pack
+    sparta_dev::DevBuf<int32_t> d_pwrange;
+    sparta_dev::DevBuf<sparta_dev::PackLoc> d_pack_loc;
     int64_t n_psteps = 0, pack_slots = 0;
     bool legacy_dropped = false;                  // fp32: the reference-layout image d_A was freed once the fragment image had won (rebuilt on demand, then kept)
     // hub plan (16-bit handles of 64-wide blocks; vbs_plan.cpp, k_hub16.hip)
-    sparta_dev::HubStep* d_hub_steps = nullptr;
-    sparta_dev::HubStep* d_hub_steps_g = nullptr; // step list for sparta_vbs_spmm_gathered with shard_rows == g_shard_rows
+    sparta_dev::DevBuf<sparta_dev::HubStep> d_hub_steps;
+    sparta_dev::DevBuf<sparta_dev::HubStep> d_hub_steps_g; // step list for sparta_vbs_spmm_gathered with shard_rows == g_shard_rows
     std::vector<sparta_dev::HubStep> h_hub_steps; // host copy (padded), source of the gathered variant
-    sparta_dev::HubTile* d_hub_tiles = nullptr;
-    int32_t* d_hub_wrange = nullptr;
-    uint16_t* d_hub_A = nullptr;
+    sparta_dev::DevBuf<sparta_dev::HubTile> d_hub_tiles;
+    sparta_dev::DevBuf<int32_t> d_hub_wrange;
+    sparta_dev::DevBuf<uint16_t> d_hub_A;
     int hub_g = 0, hub_workers = 0;
     int64_t n_hub_steps = 0, hub_area = 0, hub_union_area = 0, n_hub_tiles = 0, n_hub_groups = 0, hub_chunks = 0, hub_segments = 0;
     bool has_tail = false;                 // cols % w != 0: the stream path needs B_tail
-    void* d_btail = nullptr;
-    size_t d_btail_bytes = 0;
+    sparta_dev::DevScratch d_btail;
     int last_path = 0;                     // 1: stream kernel, 2: per-class branch-free kernels, 3: per-class generic kernels
     std::vector<std::pair<int64_t, int>> tuned;   // (n_cols/layout key) -> measured best path
     float tune_ms[2] = {0.0f, 0.0f};
-    void* d_tune = nullptr;
-    size_t d_tune_bytes = 0;
-    void* d_B16 = nullptr;                 // 16-bit handles, host-pointer calls: B converted on the device
-    size_t d_B16_bytes = 0;
-    void* d_Bt = nullptr;                  // 16-bit handles, n_cols % 128 != 0: the last n_cols % 128 columns of B, zero-padded to a 128-column slab
-    size_t d_Bt_bytes = 0;
-    void* d_Ct = nullptr;                  // ... and the 128-column slab of C they produce (column-major, ld = rows), merged into C afterwards
-    size_t d_Ct_bytes = 0;
-    long long* d_clk = nullptr;           // clock probe: [4 launches][4] = {s_memtime, s_memrealtime} at entry, at exit
-    hipEvent_t tev0 = nullptr, tev1 = nullptr;
+    sparta_dev::DevScratch d_tune;
+    sparta_dev::DevScratch d_B16;                 // 16-bit handles, host-pointer calls: B converted on the device
+    sparta_dev::DevScratch d_Bt;                  // 16-bit handles, n_cols % 128 != 0: the last n_cols % 128 columns of B, zero-padded to a 128-column slab
+    sparta_dev::DevScratch d_Ct;                  // ... and the 128-column slab of C they produce (column-major, ld = rows), merged into C afterwards
+    sparta_dev::DevBuf<long long> d_clk;           // clock probe: [4 launches][4] = {s_memtime, s_memrealtime} at entry, at exit
+    sparta_dev::DevEvent tev0, tev1;
     // sparse-row path (fp32 handles): the block-rows taken out of the MFMA plans, as rows of (column, value)
     int64_t n_sp_rows = 0, n_sp_short = 0, n_sp_long = 0, sp_nnz = 0;
     bool ext_sparse = false;               // created from CSR: the sparse rows have no dense image (no exact-order kernel for them)
-    int64_t* d_sp_rowptr = nullptr;
-    int32_t* d_sp_col = nullptr;
-    float* d_sp_val = nullptr;
-    int32_t* d_sp_crow = nullptr;
-    int32_t* d_sp_list = nullptr;          // the short rows (one wave each)
-    void* d_sp_segs = nullptr;             // SpSegRec[n_sp_segs]: segments of the long rows
-    void* d_sp_long = nullptr;             // SpLongRec[n_sp_long]
+    sparta_dev::DevBuf<int64_t> d_sp_rowptr;
+    sparta_dev::DevBuf<int32_t> d_sp_col;
+    sparta_dev::DevBuf<float> d_sp_val;
+    sparta_dev::DevBuf<int32_t> d_sp_crow;
+    sparta_dev::DevBuf<int32_t> d_sp_list;          // the short rows (one wave each)
+    sparta_dev::DevBuf<sparta_dev::SpSegRec> d_sp_segs;             // SpSegRec[n_sp_segs]: segments of the long rows
+    sparta_dev::DevBuf<sparta_dev::SpLongRec> d_sp_long;             // SpLongRec[n_sp_long]
     int64_t n_sp_segs = 0;
-    int32_t* d_sp_stream_begin = nullptr;  // XCD-affine order of the segments: eight streams, [9] offsets into d_sp_segs (nullptr: one list, window-major)
+    sparta_dev::DevBuf<int32_t> d_sp_stream_begin;  // XCD-affine order of the segments: eight streams, [9] offsets into d_sp_segs (nullptr: one list, window-major)
     int64_t sp_max_stream = 0;
-    void* d_sp_part = nullptr;             // partial rows of the segments
-    size_t d_sp_part_bytes = 0;
+    sparta_dev::DevScratch d_sp_part;             // partial rows of the segments
     // resident-column product (k_colres.hip): fp32 handles whose rows are ALL sparse rows and whose columns of B fit LDS
-    void* d_cr_col = nullptr;               // 16-bit columns
-    void* d_cr_val = nullptr;               // values (nullptr: unit image)
-    int32_t* d_cr_meta = nullptr;          // woff[17], wslice[17], bnd[n_slices]
-    int32_t* d_cr_dest = nullptr;
-    void* d_cr_longs = nullptr;
+    sparta_dev::DevBuf<uint16_t> d_cr_col;               // 16-bit columns
+    sparta_dev::DevBuf<float> d_cr_val;               // values (nullptr: unit image)
+    sparta_dev::DevBuf<int32_t> d_cr_meta;          // woff[17], wslice[17], bnd[n_slices]
+    sparta_dev::DevBuf<int32_t> d_cr_dest;
+    sparta_dev::DevBuf<sparta_dev::ColresLong> d_cr_longs;
     int32_t cr_slices = 0, cr_long = 0, cr_plane = 0, cr_lmax = 0;       // slices of the part with most; rows cut into chunks; cells of the largest staging image / range of B; longest slot
     int32_t cr_parts = 0, cr_ranges = 0, cr_span = 0;
     int32_t cr_krange[sparta_dev::kColresMaxRanges + 1] = {0, 0, 0, 0, 0};
-    void* d_cr_parts = nullptr;
-    void* d_cr_mode = nullptr;
+    sparta_dev::DevBuf<sparta_dev::ColresPartDev> d_cr_parts;
+    sparta_dev::DevBuf<uint8_t> d_cr_mode;
     bool cr_unit = false;                  // every value 1.0f: no value array
     // ... and the same matrix once more in FOUR parts of the rows of C, for products of few column sets (N <= 128 with two columns per workgroup): 4 x the workgroups, each with a
     // quarter of the stream of A -- with fewer workgroups than CUs one workgroup's stream IS the product's time
     struct ColresSmall {
-        void* col = nullptr; void* val = nullptr; int32_t* meta = nullptr; int32_t* dest = nullptr; void* longs = nullptr; void* parts = nullptr;
+        sparta_dev::DevBuf<uint16_t> col; sparta_dev::DevBuf<float> val; sparta_dev::DevBuf<int32_t> meta, dest; sparta_dev::DevBuf<sparta_dev::ColresLong> longs; sparta_dev::DevBuf<sparta_dev::ColresPartDev> parts;
         int32_t slices = 0, plane = 0, n_parts = 0;
     } cr_small;
     bool last_colres_small = false;        // the last product on this path used the four-part image
     int64_t cr_entries = 0;                // stored entries, padding included
     int last_colres_nc = 0;                // columns per workgroup of the last product on this path (0: the product took another path)
     // column-compacted tiles (fp32 handles made from a CSR: vbs_build.cpp mode 3): per tile type [0] <= 32 rows, [1] 33..64 rows
-    sparta_dev::UnionRec* d_u_rec[sparta_dev::kUnionTypes] = {nullptr, nullptr, nullptr, nullptr};
-    int32_t* d_u_ids[sparta_dev::kUnionTypes] = {nullptr, nullptr, nullptr, nullptr};
-    void* d_u_a[sparta_dev::kUnionTypes] = {nullptr, nullptr, nullptr, nullptr};
-    int32_t* d_u_wrange[sparta_dev::kUnionTypes] = {nullptr, nullptr, nullptr, nullptr};
-    void* d_u_tail[sparta_dev::kUnionTypes] = {nullptr, nullptr, nullptr, nullptr};
+    sparta_dev::DevBuf<sparta_dev::UnionRec> d_u_rec[sparta_dev::kUnionTypes];
+    sparta_dev::DevBuf<int32_t> d_u_ids[sparta_dev::kUnionTypes];
+    sparta_dev::DevBuf<uint8_t> d_u_a[sparta_dev::kUnionTypes];
+    sparta_dev::DevBuf<int32_t> d_u_wrange[sparta_dev::kUnionTypes];
+    sparta_dev::DevBuf<uint32_t> d_u_tail[sparta_dev::kUnionTypes];
     int32_t u_workers[sparta_dev::kUnionTypes] = {0, 0, 0, 0};
     int64_t u_steps[sparta_dev::kUnionTypes] = {0, 0, 0, 0}, u_tiles[sparta_dev::kUnionTypes] = {0, 0, 0, 0};   // per tile type of the DEVICE plan
     int64_t u_tiles_h[2] = {0, 0}, u_steps_h[2] = {0, 0}, u_steps_total = 0;   // tiles / steps of tiles of <= 32 / 33..64 rows; all steps
@@ -497,74 +570,65 @@ struct sparta_vbs {
     int64_t u_exec_area = 0;                        // elements the kernel multiplies: steps x 32 x rows of the tile's type
     const void* brm_ready = nullptr;       // the row-major B of the product in flight (set by the first launch that needs it, cleared when the product returns)
     int64_t brm_ld = 0;
-    void* d_Brm = nullptr;                 // row-major copy of a column-major / gathered B
-    size_t d_Brm_bytes = 0;
+    sparta_dev::DevScratch d_Brm;                 // row-major copy of a column-major / gathered B
     const void* prepared_brm = nullptr;    // set for the duration of a sparta_vbs_spmm_prepared call: the caller's row-major copy, made once
     int64_t prepared_ld = 0;               // ... and its row stride (the n_cols it was prepared for: a 16-bit call with n_cols % 128 != 0 is cut into sub-calls)
-    void* d_B = nullptr;
-    size_t d_B_bytes = 0;
-    void* d_C = nullptr;
-    size_t d_C_bytes = 0;
+    sparta_dev::DevScratch d_B;
+    sparta_dev::DevScratch d_C;
     // SDDMM (sparta_vbs_sddmm): the work list, built at the first call; host-pointer calls stage X, Y, G (and 16-bit X, Y) in scratch
-    sparta_dev::SddmmItem* d_sd_items = nullptr;
+    sparta_dev::DevBuf<sparta_dev::SddmmItem> d_sd_items;
     int64_t n_sd_items = -1;               // -1: not built yet
-    void* d_sd_ws = nullptr;
-    size_t d_sd_ws_bytes = 0;
-    void* d_sd_h16 = nullptr;
-    size_t d_sd_h16_bytes = 0;
+    sparta_dev::DevScratch d_sd_ws;
+    sparta_dev::DevScratch d_sd_h16;
     // sparta_vbs_set_values (SPARTA_CREATE_UPDATABLE handles only): the source of every 16-bit slice, in image order; host-pointer calls stage mab in scratch
     int32_t create_flags = 0;
-    sparta_dev::UpdSlice* d_upd_map[2] = {nullptr, nullptr};   // per tile type: one record per step (= slice) of d_A
+    sparta_dev::DevBuf<sparta_dev::UpdSlice> d_upd_map[2];   // per tile type: one record per step (= slice) of d_A
     int64_t upd_base[2] = {0, 0};                              // element offset of the type's first slice in d_A
-    sparta_dev::UpdSlice* d_upd_hub = nullptr;                 // one record per 64 x 64 slice of d_hub_A
+    sparta_dev::DevBuf<sparta_dev::UpdSlice> d_upd_hub;                 // one record per 64 x 64 slice of d_hub_A
     int64_t n_upd_hub = 0;
-    void* d_upd_ws = nullptr;
-    size_t d_upd_ws_bytes = 0;
+    sparta_dev::DevScratch d_upd_ws;
     // sparta_vbs_sgd_step: stored elements the slices of each stream image hold (set at creation from the plan: an image that holds nztot of them, the only
     // non-empty one, holds each exactly once and its kernel may own the arithmetic); what the last step of either optimizer did (sparta_vbs_step_info)
     int64_t upd_cover[2] = {0, 0};
     int32_t step_last_fused = -1, step_last_launches = 0;
     // sparta_vbs_spmm_t (SPARTA_CREATE_TRANSPOSE handles only): the block-column index, the 16-bit image, the sources of its blocks; host-pointer calls stage X, Ct
-    sparta_dev::SpmmTItem* d_t_items = nullptr;
-    sparta_dev::SpmmTBlock* d_t_blocks = nullptr;
+    sparta_dev::DevBuf<sparta_dev::SpmmTItem> d_t_items;
+    sparta_dev::DevBuf<sparta_dev::SpmmTBlock> d_t_blocks;
     int64_t n_t_items = 0, n_t_blocks = 0;
-    uint16_t* d_t_A = nullptr;                                 // 16-bit handles: [ceil(h / 8)][w][8] per block, blocks in mab order
-    sparta_dev::SpmmTSrc* d_t_src = nullptr;                   // 16-bit handles with both flags: one record per block (set_values)
+    sparta_dev::DevBuf<uint16_t> d_t_A;                                 // 16-bit handles: [ceil(h / 8)][w][8] per block, blocks in mab order
+    sparta_dev::DevBuf<sparta_dev::SpmmTSrc> d_t_src;                   // 16-bit handles with both flags: one record per block (set_values)
     int64_t n_t_src = 0;
-    void* d_t_ws = nullptr;
-    size_t d_t_ws_bytes = 0;
-    void* d_t_h16 = nullptr;
-    size_t d_t_h16_bytes = 0;
+    sparta_dev::DevScratch d_t_ws;
+    sparta_dev::DevScratch d_t_h16;
     // block pruning (sparta_vbs_block_ssq / sparta_vbs_mask_blocks; handles made from VBS arrays only): the block-rows' heights and block counts, kept from
     // creation, and the block table, built from them and the handle's jab and uploaded at the first call
     bool from_vbs_arrays = false;
     std::vector<int64_t> h_row_part, h_nzcount;                // [block_rows + 1] (from 0), [block_rows]
-    sparta_dev::PruneBlock* d_prune = nullptr;
+    sparta_dev::DevBuf<sparta_dev::PruneBlock> d_prune;
     int64_t n_prune = -1;                                      // -1: not built yet
     // repattern (sparta_vbs_move_blocks with this handle as the destination): the records of the last call, grown when needed
-    void* d_repat = nullptr;
-    size_t d_repat_bytes = 0;
+    sparta_dev::DevScratch d_repat;
     // the live-block set (sparta_vbs_set_live_blocks): whether one is installed is host state; the helper arrays (pattern only) are built at the first call,
     // the snapshot and the compacted lists are written by the launches of every call (k_live.hip)
     bool live_on = false, live_built = false;
-    uint8_t* d_live_keep = nullptr;                            // [nblocks] the snapshot (0 / 1)
-    int32_t* d_live_goff = nullptr;                            // [n_brows] first position of the block-row's slice of d_live_groups
-    int32_t* d_live_groups = nullptr;                          // [live_n_groups]
-    int32_t* d_live_gcount = nullptr;                          // [n_brows]
+    sparta_dev::DevBuf<uint8_t> d_live_keep;                            // [nblocks] the snapshot (0 / 1)
+    sparta_dev::DevBuf<int32_t> d_live_goff;                            // [n_brows] first position of the block-row's slice of d_live_groups
+    sparta_dev::DevBuf<int32_t> d_live_groups;                          // [live_n_groups]
+    sparta_dev::DevBuf<int32_t> d_live_gcount;                          // [n_brows]
     int64_t live_n_groups = 0;
-    int32_t* d_live_tmap = nullptr;                            // [live_n_tlist] list position of d_t_blocks -> block number
-    int32_t* d_live_tids = nullptr;                            // [live_n_tlist] the live block numbers of every block column, compacted (-1 behind them)
-    int32_t* d_live_tcount = nullptr;                          // [block columns]
-    sparta_dev::SpmmTBlock* d_live_t_blocks = nullptr;         // d_t_blocks, every block column's live records first
-    sparta_dev::SpmmTItem* d_live_t_items = nullptr;           // d_t_items with l1 = l0 + live count
+    sparta_dev::DevBuf<int32_t> d_live_tmap;                            // [live_n_tlist] list position of d_t_blocks -> block number
+    sparta_dev::DevBuf<int32_t> d_live_tids;                            // [live_n_tlist] the live block numbers of every block column, compacted (-1 behind them)
+    sparta_dev::DevBuf<int32_t> d_live_tcount;                          // [block columns]
+    sparta_dev::DevBuf<sparta_dev::SpmmTBlock> d_live_t_blocks;         // d_t_blocks, every block column's live records first
+    sparta_dev::DevBuf<sparta_dev::SpmmTItem> d_live_t_items;           // d_t_items with l1 = l0 + live count
     int64_t live_n_tlist = 0, live_block_cols = 0;
     // live steps (sparta_vbs_set_live_steps): the switch is host state and acts only while a live set is installed.  Handles with a fused image hold one
     // word per step (fp32) / two per slice (16-bit) for its kernel: the map word -> block number is pattern only (built at the first enabling call), the words
     // are written from the snapshot by one launch of k_live.hip.  The two-pass form needs nothing of its own: it walks d_prune with d_live_keep.
     bool live_steps = false, live_steps_built = false;
     bool live_words_built = false;                             // the word map and the words exist (live steps or live forward asked for them)
-    int32_t* d_live_wmap = nullptr;                            // [live_n_words]
-    uint32_t* d_live_words = nullptr;                          // [live_n_words]
+    sparta_dev::DevBuf<int32_t> d_live_wmap;                            // [live_n_words]
+    sparta_dev::DevBuf<uint32_t> d_live_words;                          // [live_n_words]
     int64_t live_n_words = 0;
     int32_t step_last_live = 0;                                // the last step skipped dead blocks (sparta_vbs_step_info word 2)
     // live forward (sparta_vbs_set_live_forward): the switch is host state and acts only while a live set is installed.  Handles that have the word map
@@ -572,9 +636,9 @@ struct sparta_vbs {
     // words behind every set_live_blocks, and the live kernels of k_h16_live.hip walk them.  The plain arrays are never written.
     bool live_fwd = false, live_fwd_built = false;
     int live_fwd_ty = -1;                                      // the stream image that has the live form, -1: none (the plain kernels run under the switch)
-    sparta_dev::StepRec* d_fwd_steps = nullptr;                // [n_steps[ty] + padding] d_steps[ty], every range's kept steps first
-    int32_t* d_fwd_wrange = nullptr;                           // the live ranges, as d_wrange[ty]
-    int32_t* d_fwd_seg_last = nullptr;                         // [n_steps[ty]] last record of every step's segment (pattern only)
+    sparta_dev::DevBuf<sparta_dev::StepRec> d_fwd_steps;                // [n_steps[ty] + padding] d_steps[ty], every range's kept steps first
+    sparta_dev::DevBuf<int32_t> d_fwd_wrange;                           // the live ranges, as d_wrange[ty]
+    sparta_dev::DevBuf<int32_t> d_fwd_seg_last;                         // [n_steps[ty]] last record of every step's segment (pattern only)
     int64_t fwd_n_ranges = 0, fwd_n_alloc = 0;
     int32_t fwd_last_form[2] = {0, 0};                         // per stream image: the form the last 16-bit product ran (0 none yet, 1 plain, 2 live, 3 a8, 4 a8 live)
     // the fp8 weight image (sparta_vbs_set_forward_a8): the switch is host state.  The first enabling call allocates the e4m3 image of the one stream image (the
@@ -582,8 +646,8 @@ struct sparta_vbs {
     // biased exponents of the slice's two groups.  vbs_a8quant_kernel rewrites both behind every write of values while the switch is on.
     bool a8_on = false, a8_built = false, a8_valid = false;
     int a8_ty = -1;                                            // the stream image that has the a8 form
-    uint8_t* d_a8 = nullptr;                                   // [a8_bytes]
-    sparta_dev::StepRec* d_a8_steps = nullptr;                 // [n_steps[a8_ty] + padding]
+    sparta_dev::DevBuf<uint8_t> d_a8;                                   // [a8_bytes]
+    sparta_dev::DevBuf<sparta_dev::StepRec> d_a8_steps;                 // [n_steps[a8_ty] + padding]
     int64_t a8_bytes = 0, a8_n_groups = 0, a8_launches = 0;
     // the fp8 image with a live-block set (sparta_vbs_set_a8_live): host state; acts while a8 is on and valid and a live set is installed.  The product then walks
     // the compacted records of live forward (d_fwd_steps, d_fwd_wrange: live_fwd is off by the refusals, so they have no other reader) on d_a8, and
@@ -593,13 +657,13 @@ struct sparta_vbs {
     // block scores of the SDDMM (sparta_vbs_sddmm_block_ssq): a second snapshot / group list / count, written from `sel` by every call (goff is d_live_goff:
     // pattern only), the all-ones selection that stands in for sel == NULL, and the pattern-only slot offsets, finish records and the fp64 slots themselves
     bool score_built = false;
-    uint8_t* d_score_keep = nullptr;                           // [nblocks] the snapshot of sel
-    uint8_t* d_score_ones = nullptr;                           // [nblocks] 1
-    int32_t* d_score_groups = nullptr;                         // [live_n_groups]
-    int32_t* d_score_gcount = nullptr;                         // [n_brows]
-    int64_t* d_score_soff = nullptr;                           // [n_brows] first slot of the block-row
-    sparta_dev::ScoreBlock* d_score_blocks = nullptr;          // [nblocks]
-    double* d_score_slots = nullptr;                           // [sum over block-rows of ceil(h / 32) * nb * w]
+    sparta_dev::DevBuf<uint8_t> d_score_keep;                           // [nblocks] the snapshot of sel
+    sparta_dev::DevBuf<uint8_t> d_score_ones;                           // [nblocks] 1
+    sparta_dev::DevBuf<int32_t> d_score_groups;                         // [live_n_groups]
+    sparta_dev::DevBuf<int32_t> d_score_gcount;                         // [n_brows]
+    sparta_dev::DevBuf<int64_t> d_score_soff;                           // [n_brows] first slot of the block-row
+    sparta_dev::DevBuf<sparta_dev::ScoreBlock> d_score_blocks;          // [nblocks]
+    sparta_dev::DevBuf<double> d_score_slots;                           // [sum over block-rows of ceil(h / 32) * nb * w]
 };
 
 namespace sparta_dev {
