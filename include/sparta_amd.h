@@ -321,6 +321,13 @@ int sparta_vbs_plan_stats(int64_t rows, int64_t cols, const int64_t* rowptr, con
  * times its two product paths once; every later call of the shape is kernel launches only and can be captured into a hipGraph.  A call
  * that would have to allocate or time while its stream is being captured returns SPARTA_ERR_UNSUPPORTED (and leaves the capture
  * intact): run it once outside the capture first.
+ * A CAPTURED GRAPH STAYS VALID FOR AS LONG AS THE HANDLE LIVES: a graph captured from any call on a handle replays with the result of the eager call
+ * it was captured from, whatever other calls (other n_cols, leading dimensions, layouts, slab heights, SPARTA_PTR_HOST calls) are made on the handle
+ * between replays, on the same stream.  The cost: once a call on the handle has been captured, scratch that a later, larger shape outgrows is kept
+ * until sparta_vbs_destroy instead of being freed (each retired buffer is smaller than its successor, so at most as much again as the largest);
+ * every slab height of a gathered B keeps step lists of its own (captured or not); and an fp32 handle that would drop its reference-layout image of
+ * A once the no-barrier kernel carries its products keeps both images.  sparta_debug_device_allocs counts all of it; a handle that is never captured
+ * frees and reallocates as before.
  *
  * WHAT AN OUTPUT ELEMENT DEPENDS ON (non-finite operands included: Inf and NaN are ordinary data, and 0 * Inf is NaN, so "multiplied by a zero"
  * is not "not read"; tests/test_poison_gpu.py).

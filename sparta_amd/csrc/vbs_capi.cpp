@@ -30,20 +30,28 @@ bool force_generic() { const char* e = std::getenv("SPARTA_FORCE_GENERIC"); retu
 
 // CaptureScope sets g_capturing (vbs_device.hpp) for the duration of a call whose stream is being captured into a graph: anything that allocates,
 // synchronises or times (scratch growth, the first-call autotune, the gathered step lists) then fails with SPARTA_ERR_UNSUPPORTED instead of breaking the
-// capture -- run the same call once outside the capture first (same n_cols, layouts and shard_rows), after which the call is launches only
+// capture -- run the same call once outside the capture first (same n_cols, layouts and shard_rows), after which the call is launches only.
+// done(rc) is the way out of a call on a handle: a call that ran under capture and returns SPARTA_OK marks the handle as captured, after which its scratch
+// is retired instead of freed when it grows (Retired, vbs_device.hpp) -- the graph holds the addresses this call launched with.
 struct CaptureScope {
-    explicit CaptureScope(hipStream_t st, bool device_ptrs) {
+    explicit CaptureScope(hipStream_t st, bool device_ptrs, sparta_vbs* handle = nullptr) : handle_(handle) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         g_capturing = device_ptrs && hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
     }
     ~CaptureScope() { g_capturing = false; }
+    int done(int rc) const {
+        if (g_capturing && rc == SPARTA_OK && handle_) handle_->retired.captured = true;
+        return rc;
+    }
+private:
+    sparta_vbs* handle_;
 };
 
 // ---- the scaffold of a device entry point, in one place: DeviceGuard, CaptureScope, the refusal of a captured call that asks for dt_ms, then ev0, the
 // launches, hipGetLastError, ev1 + synchronise + elapsed ----
 struct DeviceCall {
     const char* entry;                          // the name the messages carry
-    int device;                                 // -1: a handle-free entry (no guard)
+    sparta_vbs* handle;                         // the handle whose device is made current and that a captured call marks; NULL: a handle-free entry (no guard)
     hipStream_t st;
     bool device_ptrs;                           // false: host operands -- the call synchronises anyway and CaptureScope does not look at the stream
     float* dt_ms = nullptr;                     // NULL: not timed
@@ -77,13 +85,13 @@ int timed_launches(const DeviceCall& c, Launches launches) {
 template <class Body>
 int open_call(const DeviceCall& c, Body body) {
     std::optional<DeviceGuard> guard;
-    if (c.device >= 0) {
-        guard.emplace(c.device);
+    if (c.handle) {
+        guard.emplace(c.handle->device);
         if (!guard->ok) return sparta::fail(SPARTA_ERR_HIP, std::string(c.entry) + ": hipSetDevice failed");
     }
-    const CaptureScope capture(c.st, c.device_ptrs);
+    const CaptureScope capture(c.st, c.device_ptrs, c.handle);
     if (g_capturing && c.dt_ms && c.timed_what) return capture_refusal((std::string("time ") + c.timed_what + " (dt_ms != NULL synchronises)").c_str(), c.entry);
-    return body(c.st);
+    return capture.done(body(c.st));
 }
 // an entry that is launches only
 template <class Launches>
@@ -1368,26 +1376,32 @@ void launch_zero_ranges(sparta_vbs_t* A, float* C, int64_t ldc, bool c_row_major
     }
 }
 
-// step lists for a gathered B (slab index + row inside the slab), rebuilt when the slab height changes
+// step lists for a gathered B (slab index + row inside the slab): built once per slab height and kept (sparta_vbs::gathered).  A list is never rewritten:
+// a graph captured at one height holds its address and must go on reading that height's steps.
 int ensure_gathered_steps(sparta_vbs_t* A, int64_t shard_rows, hipStream_t st) {
-    if (A->g_shard_rows == shard_rows) return SPARTA_OK;
+    if (A->g_cur >= 0 && A->gathered[(size_t)A->g_cur].shard_rows == shard_rows) return SPARTA_OK;
+    for (size_t i = 0; i < A->gathered.size(); i++)
+        if (A->gathered[i].shard_rows == shard_rows) { A->g_cur = (int)i; return SPARTA_OK; }
     if (g_capturing) return capture_refusal("build the step lists of this slab height");
+    sparta_vbs::GatheredSteps gs;                                // (joins the cache only when complete: a failed upload leaves no half-built set behind)
+    gs.shard_rows = shard_rows;
     for (int ty = 0; ty < 2; ty++) {
         if (A->h_steps[ty].empty()) continue;
         std::vector<StepRec> g = A->h_steps[ty];
         for (StepRec& r : g) { r.pad = (int32_t)(r.b_row / shard_rows); r.b_row = (int32_t)(r.b_row % shard_rows); }
-        if (!A->d_steps_g[ty]) HIP_TRY(A->d_steps_g[ty].alloc(g.size()));
-        HIP_TRY(hipMemcpyAsync(A->d_steps_g[ty], g.data(), g.size() * sizeof(StepRec), hipMemcpyHostToDevice, st));
+        HIP_TRY(gs.steps[ty].alloc(g.size()));
+        HIP_TRY(hipMemcpyAsync(gs.steps[ty], g.data(), g.size() * sizeof(StepRec), hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));                       // g goes out of scope
     }
     if (!A->h_hub_steps.empty()) {
         std::vector<HubStep> g = A->h_hub_steps;
         for (HubStep& r : g) if (!(r.flags & STEP_TAIL)) { r.shard = (int32_t)(r.b_row / shard_rows); r.b_row = (int32_t)(r.b_row % shard_rows); }
-        if (!A->d_hub_steps_g) HIP_TRY(A->d_hub_steps_g.alloc(g.size()));
-        HIP_TRY(hipMemcpyAsync(A->d_hub_steps_g, g.data(), g.size() * sizeof(HubStep), hipMemcpyHostToDevice, st));
+        HIP_TRY(gs.hub.alloc(g.size()));
+        HIP_TRY(hipMemcpyAsync(gs.hub, g.data(), g.size() * sizeof(HubStep), hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    A->g_shard_rows = shard_rows;
+    A->gathered.push_back(std::move(gs));
+    A->g_cur = (int)A->gathered.size() - 1;
     return SPARTA_OK;
 }
 
@@ -1410,6 +1424,7 @@ int ensure_legacy_image(sparta_vbs_t* A, hipStream_t st) {
 void drop_legacy_image(sparta_vbs_t* A) {
     static const bool keep = [] { const char* e = std::getenv("SPARTA_F32_KEEP_LEGACY"); return e && atoi(e) != 0; }();
     if (A->create_flags & SPARTA_CREATE_TRANSPOSE) return;      // sparta_vbs_spmm_t reads the reference-layout image
+    if (A->retired.captured) return;                            // a captured graph may read it (a row-major or gathered B, the per-class kernels): the handle keeps both images
     if (keep || g_capturing || A->legacy_dropped || !A->d_A || !(A->d_a_frag || A->d_a_pack) || A->dtype != SPARTA_F32 || A->n_steps[1] != 0 || A->n_sp_rows != 0 || A->class_timing) return;
     A->d_A.reset();                                      // (synchronises: the autotune's launches that read it are done)
     A->a_bytes -= (int64_t)((A->nztot + 128) * sizeof(float));
@@ -1428,7 +1443,7 @@ int ensure_brm(sparta_vbs_t* A, const void* dB, int64_t ldb, bool b_row_major, i
     if (A->prepared_brm && !b_row_major) { A->brm_ready = A->prepared_brm; A->brm_ld = A->prepared_ld; return SPARTA_OK; }
     if (g_capturing && A->d_Brm.bytes() < (size_t)A->cols * (size_t)((n_cols + per16 - 1) / per16 * per16) * esz) return capture_refusal("allocate the row-major copy of B");
     const int64_t ld = (n_cols + per16 - 1) / per16 * per16;
-    if (int rc = A->d_Brm.ensure((size_t)A->cols * (size_t)ld * esz)) return rc;
+    if (int rc = A->d_Brm.ensure((size_t)A->cols * (size_t)ld * esz, A->retired)) return rc;
     if (b_row_major) {                                   // (a row-major B whose rows are not 16-byte aligned: an aligned copy)
         HIP_TRY(hipMemcpy2DAsync(A->d_Brm, (size_t)ld * esz, dB, (size_t)ldb * esz, (size_t)n_cols * esz, (size_t)A->cols, hipMemcpyDeviceToDevice, st));
     } else {
@@ -1551,7 +1566,7 @@ int launch_sparse_rows(sparta_vbs_t* A, const void* dB, int64_t ldb, bool b_row_
     // the kernels write C themselves: rows of a row-major C, or 16-row pieces of the columns of the reference's column-major C
     q.out = dC; q.ldo = ldc; q.out_is_c = c_row_major ? 1 : 2;
     if (A->n_sp_long > 0)
-        if (int rc = A->d_sp_part.ensure((size_t)A->n_sp_segs * (size_t)n_cols * sizeof(float))) return rc;
+        if (int rc = A->d_sp_part.ensure((size_t)A->n_sp_segs * (size_t)n_cols * sizeof(float), A->retired)) return rc;
     // widest vector the shapes allow: every row start VEC-element aligned, N a multiple of 64 * VEC (no ragged chunk)
     auto aligned = [&](int v) {
         const bool out_ok = q.out_is_c == 2 || (q.ldo % v == 0 && ((uintptr_t)q.out % (4 * v)) == 0);
@@ -1598,9 +1613,9 @@ int spmm16_core(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
     if (ptr_space == SPARTA_PTR_HOST) {
         const size_t b_elems = (size_t)ldb * (size_t)n_cols;
         ldb16 = (A->cols + 7) / 8 * 8;
-        if (int rc = A->d_B.ensure(b_elems * sizeof(float))) return rc;
-        if (int rc = A->d_B16.ensure((size_t)ldb16 * n_cols * sizeof(uint16_t))) return rc;
-        if (int rc = A->d_C.ensure(c_elems * sizeof(float))) return rc;
+        if (int rc = A->d_B.ensure(b_elems * sizeof(float), A->retired)) return rc;
+        if (int rc = A->d_B16.ensure((size_t)ldb16 * n_cols * sizeof(uint16_t), A->retired)) return rc;
+        if (int rc = A->d_C.ensure(c_elems * sizeof(float), A->retired)) return rc;
         HIP_TRY(hipMemcpyAsync(A->d_B, B, b_elems * sizeof(float), hipMemcpyHostToDevice, st));
         if (accumulate) HIP_TRY(hipMemcpyAsync(A->d_C, C, c_elems * sizeof(float), hipMemcpyHostToDevice, st));
         else if (c_elems > 0) HIP_TRY(hipMemsetAsync(A->d_C, 0, c_elems * sizeof(float), st));
@@ -1626,7 +1641,7 @@ int spmm16_core(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
     for (int c = 0; c < 4; c++) A->class_ran[c] = false;
     const size_t slab = (size_t)A->n_slots * SK_SLOT_FLOATS;
     if (A->n_split > 0)
-        if (int rc = A->d_ws.ensure(slab * n_nt * sizeof(float))) return rc;
+        if (int rc = A->d_ws.ensure(slab * n_nt * sizeof(float), A->retired)) return rc;
     StreamParams sp;
     sp.A = A->d_A; sp.B = (const float*)dB; sp.C = dC; sp.ws = (float*)A->d_ws;
     sp.ldb = ldb16; sp.ldc = ldc; sp.cols = A->cols; sp.shard_rows = shard_rows; sp.shard_stride = shard_stride;
@@ -1637,7 +1652,7 @@ int spmm16_core(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
     if (A->n_steps[0] + A->n_steps[1] + A->n_hub_steps > 0) {
         if (prof) HIP_TRY(hipEventRecord(A->cev[0][0], st));
         if (A->has_tail && shard_rows == 0) {
-            if (int rc = A->d_btail.ensure((size_t)A->w * n_cols * sizeof(uint16_t))) return rc;
+            if (int rc = A->d_btail.ensure((size_t)A->w * n_cols * sizeof(uint16_t), A->retired)) return rc;
             const int64_t row0 = ((A->cols - 1) / A->w) * A->w;
             launch_tail_copy_h16(st, dB, ldb16, row0, A->cols, (int)A->w, (int)n_cols, (uint16_t*)A->d_btail);
             sp.B_tail = (const float*)A->d_btail;
@@ -1652,7 +1667,7 @@ int spmm16_core(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
         const bool fwd_a8 = A->a8_on && A->a8_valid && A->a8_built && A->a8_ty >= 0 && shard_rows == 0;
         for (int ty = 1; ty >= 0; ty--) {
             if (A->n_steps[ty] == 0) continue;
-            sp.steps = shard_rows > 0 ? A->d_steps_g[ty] : A->d_steps[ty]; sp.worker_range = A->d_wrange[ty]; sp.c_nt = c_store_nt(A, ty, sp.C, sp.ldc, sp.c_row_major != 0);
+            sp.steps = shard_rows > 0 ? A->gathered[(size_t)A->g_cur].steps[ty] : A->d_steps[ty]; sp.worker_range = A->d_wrange[ty]; sp.c_nt = c_store_nt(A, ty, sp.C, sp.ldc, sp.c_row_major != 0);
             sp.clk = (prof && ty == probe_ty) ? A->d_clk : nullptr;
             const bool gth = shard_rows > 0;
             // tiles of <= 32 rows of arbitrary height + column-major C: finished tiles wait in the LDS ring for whole aligned blocks (CRing)
@@ -1704,7 +1719,7 @@ int spmm16_core(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
         // the hub plan: group tiles of 2 / 4 long 64-row tiles through the GEMM-shaped kernel (k_hub16.hip), 256-column slabs (the last one may be a half slab)
         if (A->n_hub_steps > 0) {
             HubParams hp;
-            hp.steps = shard_rows > 0 ? A->d_hub_steps_g : A->d_hub_steps; hp.worker_range = A->d_hub_wrange; hp.tiles = A->d_hub_tiles; hp.A = A->d_hub_A;
+            hp.steps = shard_rows > 0 ? A->gathered[(size_t)A->g_cur].hub : A->d_hub_steps; hp.worker_range = A->d_hub_wrange; hp.tiles = A->d_hub_tiles; hp.A = A->d_hub_A;
             hp.B = dB; hp.B_tail = (const uint16_t*)sp.B_tail; hp.C = dC; hp.ws = (float*)A->d_ws;
             hp.ldb = ldb16; hp.ldc = ldc; hp.shard_stride = shard_stride; hp.ws_slab_stride = (int64_t)slab;
             hp.accumulate = accumulate != 0; hp.c_row_major = c_layout == SPARTA_ROW_MAJOR; hp.c_nt = 1; hp.w = (int32_t)A->w;
@@ -1781,9 +1796,9 @@ int spmm16_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
     if (ptr_space == SPARTA_PTR_HOST) {                    // stage here (the core's own staging assumes whole slabs)
         const size_t b_elems = (size_t)ldb * (size_t)n_cols;
         ldb16 = (A->cols + 7) / 8 * 8;
-        if (int rc = A->d_B.ensure(b_elems * sizeof(float))) return rc;
-        if (int rc = A->d_B16.ensure((size_t)ldb16 * n_cols * sizeof(uint16_t))) return rc;
-        if (int rc = A->d_C.ensure(c_elems * sizeof(float))) return rc;
+        if (int rc = A->d_B.ensure(b_elems * sizeof(float), A->retired)) return rc;
+        if (int rc = A->d_B16.ensure((size_t)ldb16 * n_cols * sizeof(uint16_t), A->retired)) return rc;
+        if (int rc = A->d_C.ensure(c_elems * sizeof(float), A->retired)) return rc;
         HIP_TRY(hipMemcpyAsync(A->d_B, B, b_elems * sizeof(float), hipMemcpyHostToDevice, st));
         if (accumulate) HIP_TRY(hipMemcpyAsync(A->d_C, C, c_elems * sizeof(float), hipMemcpyHostToDevice, st));
         else if (c_elems > 0) HIP_TRY(hipMemsetAsync(A->d_C, 0, c_elems * sizeof(float), st));
@@ -1801,8 +1816,8 @@ int spmm16_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
     const int64_t n_shards = shard_rows > 0 ? A->cols / shard_rows : 1;
     const int64_t ld_t = shard_rows > 0 ? shard_rows : ldb16;                     // rows of a column of the tail slab of B
     const size_t bt_elems = (size_t)ld_t * kTN * (size_t)n_shards;
-    if (int rc = A->d_Bt.ensure(bt_elems * sizeof(uint16_t))) return rc;
-    if (int rc = A->d_Ct.ensure((size_t)A->rows * kTN * sizeof(float))) return rc;
+    if (int rc = A->d_Bt.ensure(bt_elems * sizeof(uint16_t), A->retired)) return rc;
+    if (int rc = A->d_Ct.ensure((size_t)A->rows * kTN * sizeof(float), A->retired)) return rc;
     HIP_TRY(hipMemsetAsync(A->d_Bt, 0, bt_elems * sizeof(uint16_t), st));
     if (shard_rows > 0 && ldb16 == shard_rows)
         HIP_TRY(hipMemcpy2DAsync(A->d_Bt, (size_t)shard_rows * kTN * sizeof(uint16_t), dB + (size_t)n_main * shard_rows, (size_t)shard_stride * sizeof(uint16_t),
@@ -1834,6 +1849,11 @@ int spmm16_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, i
     return SPARTA_OK;
 }
 
+// (the product itself: below, inside this guard and capture scope)
+int spmm_run(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int64_t shard_rows, int64_t shard_stride, int32_t n_cols,
+             void* C, int64_t ldc, int32_t c_layout, int32_t accumulate, int32_t ptr_space, hipStream_t st, int32_t algo,
+             float* dt_ms);
+
 int spmm_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int64_t shard_rows, int64_t shard_stride, int32_t n_cols,
               void* C, int64_t ldc, int32_t c_layout, int32_t accumulate, int32_t ptr_space, void* stream, int32_t algo,
               float* dt_ms) {
@@ -1851,8 +1871,16 @@ int spmm_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int
     DeviceGuard guard(A->device);
     if (!guard.ok) return fail(SPARTA_ERR_HIP, "sparta_vbs_spmm: hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, ptr_space == SPARTA_PTR_DEVICE);
+    const CaptureScope capture(st, ptr_space == SPARTA_PTR_DEVICE, A);
     if (g_capturing && dt_ms) return capture_refusal("time the product (dt_ms != NULL synchronises)");
+    return capture.done(spmm_run(A, B, ldb, b_layout, shard_rows, shard_stride, n_cols, C, ldc, c_layout, accumulate, ptr_space, st, algo, dt_ms));
+}
+
+// the product of a checked call, inside spmm_impl's guard and capture scope
+int spmm_run(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int64_t shard_rows, int64_t shard_stride, int32_t n_cols,
+             void* C, int64_t ldc, int32_t c_layout, int32_t accumulate, int32_t ptr_space, hipStream_t st, int32_t algo,
+             float* dt_ms) {
+    using sparta::fail;
     if (A->dtype != SPARTA_F32)
         return spmm16_impl(A, B, ldb, b_layout, shard_rows, shard_stride, n_cols, C, ldc, c_layout, accumulate, ptr_space, st, algo, dt_ms);
 
@@ -1862,8 +1890,8 @@ int spmm_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int
     const size_t c_elems = (size_t)ldc * (size_t)(c_layout == SPARTA_COL_MAJOR ? n_cols : A->rows);
     if (ptr_space == SPARTA_PTR_HOST) {
         // the reference's back-end contract: host in, host out, dt excludes the copies
-        if (int rc = A->d_B.ensure(b_elems * sizeof(float))) return rc;
-        if (int rc = A->d_C.ensure(c_elems * sizeof(float))) return rc;
+        if (int rc = A->d_B.ensure(b_elems * sizeof(float), A->retired)) return rc;
+        if (int rc = A->d_C.ensure(c_elems * sizeof(float), A->retired)) return rc;
         HIP_TRY(hipMemcpyAsync(A->d_B, B, b_elems * sizeof(float), hipMemcpyHostToDevice, st));
         if (accumulate) HIP_TRY(hipMemcpyAsync(A->d_C, C, c_elems * sizeof(float), hipMemcpyHostToDevice, st));
         else if (c_elems > 0) HIP_TRY(hipMemsetAsync(A->d_C, 0, c_elems * sizeof(float), st));   // ld padding stays defined
@@ -1903,7 +1931,7 @@ int spmm_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int
         auto run_stream = [&](float* Cout, bool prof) -> int {
             const size_t slab = (size_t)A->n_slots * SK_SLOT_FLOATS;
             if (A->n_split > 0)
-                if (int rc = A->d_ws.ensure(slab * n_nt * sizeof(float))) return rc;
+                if (int rc = A->d_ws.ensure(slab * n_nt * sizeof(float), A->retired)) return rc;
             if (shard_rows > 0)
                 if (int rc = ensure_gathered_steps(A, shard_rows, st)) return rc;
             // the LDS-staged kernels (33..64-row tiles; any tile under a row-major or gathered B) read the reference-layout image; the no-barrier kernel the fragment image
@@ -1919,7 +1947,7 @@ int spmm_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int
             if (A->n_steps[0] + A->n_steps[1] > 0) {
                 if (prof) HIP_TRY(hipEventRecord(A->cev[0][0], st));
                 if (A->has_tail && shard_rows == 0) {
-                    if (int rc = A->d_btail.ensure((size_t)A->w * n_cols * sizeof(float))) return rc;
+                    if (int rc = A->d_btail.ensure((size_t)A->w * n_cols * sizeof(float), A->retired)) return rc;
                     const int64_t row0 = ((A->cols - 1) / A->w) * A->w;
                     launch_tail_copy(st, dB, ldb, (int)(b_layout == SPARTA_ROW_MAJOR), row0, A->cols, (int)A->w, (int)n_cols, (float*)A->d_btail);
                     sp.B_tail = (const float*)A->d_btail;
@@ -1929,7 +1957,7 @@ int spmm_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int
                 const int probe_ty = A->n_steps[1] >= A->n_steps[0] ? 1 : 0;
                 for (int ty = 1; ty >= 0; ty--) {
                     if (A->n_steps[ty] == 0) continue;
-                    sp.steps = shard_rows > 0 ? A->d_steps_g[ty] : A->d_steps[ty]; sp.worker_range = A->d_wrange[ty]; sp.c_nt = c_store_nt(A, ty, sp.C, sp.ldc, sp.c_row_major != 0);
+                    sp.steps = shard_rows > 0 ? A->gathered[(size_t)A->g_cur].steps[ty] : A->d_steps[ty]; sp.worker_range = A->d_wrange[ty]; sp.c_nt = c_store_nt(A, ty, sp.C, sp.ldc, sp.c_row_major != 0);
                     sp.clk = (prof && ty == probe_ty) ? A->d_clk : nullptr;
                     if (ty == 0 && (A->d_a_frag || A->d_a_pack) && b_layout == SPARTA_COL_MAJOR && shard_rows == 0) {
                         StreamParams sd = sp;                 // the <= 32-row tiles without the workgroup stage
@@ -1996,7 +2024,7 @@ int spmm_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int
             if (path == 0 && g_capturing) return capture_refusal("time its two product paths");
             if (path == 0) {
                 // plan-time autotune: both paths write a scratch C (the caller's C must not be accumulated into twice)
-                if (int rc = A->d_tune.ensure(c_elems * sizeof(float))) return rc;
+                if (int rc = A->d_tune.ensure(c_elems * sizeof(float), A->retired)) return rc;
                 float best[3] = {0.0f, 1e30f, 1e30f};
                 for (int cand = 1; cand <= 2; cand++) {
                     for (int rep = 0; rep < 4; rep++) {
@@ -2243,7 +2271,7 @@ int sddmm_impl(sparta_vbs_t* A, const void* X, int64_t ldx, const void* Y, int64
     if (A->ext_sparse)
         return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_sddmm: the handle does not hold the dense blocks of every block-row (made by sparta_vbs_create_from_csr)");
 
-    const DeviceCall call{"sparta_vbs_sddmm", A->device, (hipStream_t)stream, ptr_space == SPARTA_PTR_DEVICE, dt_ms, "the product", A->ev0, A->ev1};
+    const DeviceCall call{"sparta_vbs_sddmm", A, (hipStream_t)stream, ptr_space == SPARTA_PTR_DEVICE, dt_ms, "the product", A->ev0, A->ev1};
     return open_call(call, [&](hipStream_t st) -> int {
         if (int rc = ensure_sddmm_items(A)) return rc;
 
@@ -2255,7 +2283,7 @@ int sddmm_impl(sparta_vbs_t* A, const void* X, int64_t ldx, const void* Y, int64
         const size_t g_elems = (size_t)A->nztot;
         if (ptr_space == SPARTA_PTR_HOST) {
             // host in, host out: X, Y, G staged in one device buffer; 16-bit handles round X, Y on the device
-            if (int rc = A->d_sd_ws.ensure((x_elems + y_elems + g_elems) * sizeof(float))) return rc;
+            if (int rc = A->d_sd_ws.ensure((x_elems + y_elems + g_elems) * sizeof(float), A->retired)) return rc;
             float* ws = (float*)A->d_sd_ws;
             HIP_TRY(hipMemcpyAsync(ws, X, x_elems * sizeof(float), hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(ws + x_elems, Y, y_elems * sizeof(float), hipMemcpyHostToDevice, st));
@@ -2264,7 +2292,7 @@ int sddmm_impl(sparta_vbs_t* A, const void* X, int64_t ldx, const void* Y, int64
             if (h16) {
                 kx = (A->rows + 7) / 8 * 8; ky = (A->cols + 7) / 8 * 8;       // (multiples of 8: the 16-byte loads of k_sddmm.hip)
                 const size_t hx = (size_t)kx * (size_t)k, hy = (size_t)ky * (size_t)k;
-                if (int rc = A->d_sd_h16.ensure((hx + hy) * sizeof(uint16_t))) return rc;
+                if (int rc = A->d_sd_h16.ensure((hx + hy) * sizeof(uint16_t), A->retired)) return rc;
                 uint16_t* hw = (uint16_t*)A->d_sd_h16;
                 launch_convert_h16(A->dtype == SPARTA_BF16, st, ws, ldx, A->rows, k, hw, kx);
                 launch_convert_h16(A->dtype == SPARTA_BF16, st, ws + x_elems, ldy, A->cols, k, hw + hx, ky);
@@ -2358,11 +2386,11 @@ int set_values_impl(sparta_vbs_t* A, const float* mab, int32_t ptr_space, void* 
     if (!mab && A->nztot > 0) return fail(SPARTA_ERR_INVALID, "sparta_vbs_set_values: mab is NULL");
     if (ptr_space != SPARTA_PTR_HOST && ptr_space != SPARTA_PTR_DEVICE) return fail(SPARTA_ERR_INVALID, "sparta_vbs_set_values: bad ptr_space");
     if (!(A->create_flags & SPARTA_CREATE_UPDATABLE)) return not_updatable("sparta_vbs_set_values");
-    const DeviceCall call{"sparta_vbs_set_values", A->device, (hipStream_t)stream, ptr_space == SPARTA_PTR_DEVICE, dt_ms, "the update", A->ev0, A->ev1, A->nztot <= 0};
+    const DeviceCall call{"sparta_vbs_set_values", A, (hipStream_t)stream, ptr_space == SPARTA_PTR_DEVICE, dt_ms, "the update", A->ev0, A->ev1, A->nztot <= 0};
     return open_call(call, [&](hipStream_t st) -> int {
         const float* src = mab;
         if (ptr_space == SPARTA_PTR_HOST && A->nztot > 0) {
-            if (int rc = A->d_upd_ws.ensure((size_t)A->nztot * sizeof(float))) return rc;
+            if (int rc = A->d_upd_ws.ensure((size_t)A->nztot * sizeof(float), A->retired)) return rc;
             HIP_TRY(hipMemcpyAsync(A->d_upd_ws, mab, (size_t)A->nztot * sizeof(float), hipMemcpyHostToDevice, st));
             src = (const float*)A->d_upd_ws;
         }
@@ -2416,7 +2444,7 @@ int sgd_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G, 
     int launches = 0;
     int fused = -1;
     bool live = false;
-    const DeviceCall call{entry, A->device, (hipStream_t)stream, true, dt_ms, "the step", A->ev0, A->ev1, A->nztot <= 0};
+    const DeviceCall call{entry, A, (hipStream_t)stream, true, dt_ms, "the step", A->ev0, A->ev1, A->nztot <= 0};
     const int rc = device_call(call, [&](hipStream_t st) {
         const SgdCfg c{cfg->lr, cfg->momentum, cfg->weight_decay, cfg->grad_scale};
         const uint32_t* ctl = (const uint32_t*)R;
@@ -2484,7 +2512,7 @@ int adam_step_impl(const char* entry, sparta_vbs_t* A, float* W, const float* G,
     int launches = 0;
     int fused = -1;
     bool live = false;
-    const DeviceCall call{entry, A->device, (hipStream_t)stream, true, dt_ms, "the step", A->ev0, A->ev1, A->nztot <= 0};
+    const DeviceCall call{entry, A, (hipStream_t)stream, true, dt_ms, "the step", A->ev0, A->ev1, A->nztot <= 0};
     const int rc = device_call(call, [&](hipStream_t st) {
         // the three derived constants, each operation rounded once to fp32 (volatile: no contraction, no wider intermediate)
         volatile float omb1 = 1.0f - cfg->beta1, omb2 = 1.0f - cfg->beta2, lr_wd = cfg->lr * cfg->weight_decay;
@@ -2549,7 +2577,7 @@ extern "C" int sparta_grad_stats(const float* G, int64_t n, void* R, int32_t acc
     if (n > 0 && !G) return fail(SPARTA_ERR_INVALID, "sparta_grad_stats: G is NULL with n > 0");
     if ((uintptr_t)G % 4 != 0) return fail(SPARTA_ERR_INVALID, "sparta_grad_stats: G must be 4-byte aligned");
     // handle-free: no guard, and the events of a timed call live for that call
-    return device_call(DeviceCall{"sparta_grad_stats", -1, (hipStream_t)stream, true, dt_ms, "the reduction"},
+    return device_call(DeviceCall{"sparta_grad_stats", nullptr, (hipStream_t)stream, true, dt_ms, "the reduction"},
                        [&](hipStream_t st) { launch_grad_stats(st, G, n, R, accumulate != 0); });
     SPARTA_GUARD_END("sparta_grad_stats")
 }
@@ -2565,7 +2593,7 @@ extern "C" int sparta_grad_ctl_finish(void* R, const sparta_grad_ctl_cfg* cfg, v
         return fail(SPARTA_ERR_INVALID, "sparta_grad_ctl_finish: growth_factor must be >= 1 and backoff_factor in (0, 1]");
     for (int i = 0; i < 4; i++)
         if (cfg->reserved[i] != 0) return fail(SPARTA_ERR_INVALID, "sparta_grad_ctl_finish: cfg->reserved must be 0");
-    return device_call(DeviceCall{"sparta_grad_ctl_finish", -1, (hipStream_t)stream, true},
+    return device_call(DeviceCall{"sparta_grad_ctl_finish", nullptr, (hipStream_t)stream, true},
                        [&](hipStream_t st) { launch_grad_ctl_finish(st, R, cfg->max_norm, cfg->growth_factor, cfg->backoff_factor, cfg->growth_interval); });
     SPARTA_GUARD_END("sparta_grad_ctl_finish")
 }
@@ -2631,7 +2659,7 @@ int64_t ep_scratch_bytes(int64_t rows, int64_t n_cols) {
 // the launches of one entry between two events of this call (handle-free, as sparta_grad_stats)
 template <class Launch>
 int ep_call(const char* entry, bool nothing_to_do, void* stream, float* dt_ms, Launch launch) {
-    return device_call(DeviceCall{entry, -1, (hipStream_t)stream, true, dt_ms, "the kernels", nullptr, nullptr, nothing_to_do}, launch);
+    return device_call(DeviceCall{entry, nullptr, (hipStream_t)stream, true, dt_ms, "the kernels", nullptr, nullptr, nothing_to_do}, launch);
 }
 
 }  // namespace
@@ -2741,7 +2769,7 @@ int ensure_prune_table(sparta_vbs_t* A, const char* entry) {
 // the launches of one entry between the handle's events, behind the block table (built at the first call that has something to do)
 template <class Launch>
 int prune_call(sparta_vbs_t* A, const char* entry, bool nothing_to_do, void* stream, float* dt_ms, Launch launch) {
-    const DeviceCall call{entry, A->device, (hipStream_t)stream, true, dt_ms, "the kernel", A->ev0, A->ev1, nothing_to_do};
+    const DeviceCall call{entry, A, (hipStream_t)stream, true, dt_ms, "the kernel", A->ev0, A->ev1, nothing_to_do};
     return open_call(call, [&](hipStream_t) -> int {
         if (!nothing_to_do)
             if (int rc = ensure_prune_table(A, entry)) return rc;
@@ -2937,7 +2965,7 @@ extern "C" int sparta_vbs_move_blocks(sparta_vbs_t* dst, const sparta_vbs_t* src
         }
     }
     const bool nothing_to_do = nb == 0 || dst->nztot == 0 || !any;
-    const DeviceCall call{me, dst->device, (hipStream_t)stream, true, dt_ms, nullptr, dst->ev0, dst->ev1, nothing_to_do};
+    const DeviceCall call{me, dst, (hipStream_t)stream, true, dt_ms, nullptr, dst->ev0, dst->ev1, nothing_to_do};
     return open_call(call, [&](hipStream_t st) -> int {
         if (g_capturing) return capture_refusal("build and upload the records of the move (it synchronises)", me);
         std::vector<int64_t> td, ts;
@@ -2953,7 +2981,7 @@ extern "C" int sparta_vbs_move_blocks(sparta_vbs_t* dst, const sparta_vbs_t* src
         }
         if (!nothing_to_do) {
             HIP_TRY(hipStreamSynchronize(st));                                // (the kernel of an earlier call may still read the records)
-            if (int rc = dst->d_repat.ensure(rec.size() * sizeof(MoveBlock))) return rc;
+            if (int rc = dst->d_repat.ensure(rec.size() * sizeof(MoveBlock), dst->retired)) return rc;
             HIP_TRY(hipMemcpy(dst->d_repat, rec.data(), rec.size() * sizeof(MoveBlock), hipMemcpyHostToDevice));
         }
         return timed_launches(call, [&](hipStream_t) { launch_move_blocks(st, (const MoveBlock*)dst->d_repat, nb, S, D); });
@@ -3111,7 +3139,7 @@ extern "C" int sparta_vbs_set_live_steps(sparta_vbs_t* A, int32_t enable, void* 
         A->live_steps = false;
         return SPARTA_OK;
     }
-    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+    return open_call(DeviceCall{entry, A, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
         if (int rc = ensure_live_step_arrays(A, entry)) return rc;
         if (A->live_on && A->live_n_words > 0) {     // a set is installed already: the words follow from its snapshot
             launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
@@ -3132,7 +3160,7 @@ extern "C" int sparta_vbs_set_live_blocks(sparta_vbs_t* A, const uint8_t* keep, 
         A->live_on = false;
         return SPARTA_OK;
     }
-    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+    return open_call(DeviceCall{entry, A, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
         if (int rc = ensure_live_arrays(A, entry)) return rc;
         launch_live_sddmm(st, A->d_brows, A->n_brows, (int)A->w, keep, A->nblocks, A->d_live_keep, A->d_live_goff, A->d_live_groups, A->d_live_gcount);
         if (A->create_flags & SPARTA_CREATE_TRANSPOSE)
@@ -3208,7 +3236,7 @@ extern "C" int sparta_vbs_sddmm_block_ssq(sparta_vbs_t* A, const void* X, int64_
     if (A->dtype != SPARTA_F32 && ((ldx | ldy) & 1)) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": 16-bit handles need even ldx, ldy");
     if (A->nblocks == 0) return SPARTA_OK;
 
-    const DeviceCall call{entry, A->device, (hipStream_t)stream, true, dt_ms, "the product", A->ev0, A->ev1};
+    const DeviceCall call{entry, A, (hipStream_t)stream, true, dt_ms, "the product", A->ev0, A->ev1};
     return open_call(call, [&](hipStream_t st) -> int {
         if (int rc = ensure_score_arrays(A, entry)) return rc;
 
@@ -3242,7 +3270,7 @@ extern "C" int sparta_vbs_set_live_forward(sparta_vbs_t* A, int32_t enable, void
     }
     if (A->a8_on)
         return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the fp8 weight image is on (sparta_vbs_set_forward_a8) and the two do not combine -- switch it off first");
-    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+    return open_call(DeviceCall{entry, A, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
         if (int rc = ensure_live_forward_arrays(A, entry)) return rc;
         if (A->live_on && A->live_fwd_ty >= 0) {     // a set is installed already: words and lists follow from its snapshot
             launch_live_step_words(st, A->d_live_wmap, A->live_n_words, A->d_live_keep, A->d_live_words);
@@ -3271,7 +3299,7 @@ extern "C" int sparta_vbs_live_forward_info(sparta_vbs_t* A, int64_t* info_out, 
     info_out[6] = A->n_split;
     info_out[7] = A->live_fwd_built && ty >= 0 ? A->fwd_n_ranges : 0;
     if (!A->live_on || !A->live_fwd_built || ty < 0) return SPARTA_OK;
-    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+    return open_call(DeviceCall{entry, A, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
         if (g_capturing) return capture_refusal("read the live ranges back (synchronises)", entry);
         HIP_TRY(hipStreamSynchronize(st));
         std::vector<int32_t> ranges((size_t)A->fwd_n_ranges * 2);
@@ -3290,7 +3318,7 @@ extern "C" int sparta_vbs_live_forward_lists_get(sparta_vbs_t* A, void* steps_pl
     if (int rc = prune_handle_check(A, entry)) return rc;
     if (!A->live_on) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": no live set is installed");
     if (!A->live_fwd_built || A->live_fwd_ty < 0) return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the handle has no live forward lists");
-    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+    return open_call(DeviceCall{entry, A, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
         if (g_capturing) return capture_refusal("read the live forward lists back (synchronises)", entry);
         HIP_TRY(hipStreamSynchronize(st));
         const int ty = A->live_fwd_ty;
@@ -3355,7 +3383,7 @@ extern "C" int sparta_vbs_set_forward_a8(sparta_vbs_t* A, int32_t enable, void* 
         return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": needs a 16-bit handle made with SPARTA_CREATE_UPDATABLE (sparta_vbs_create_range_ex)");
     if (A->live_fwd)
         return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": live forward is on (sparta_vbs_set_live_forward) and the two do not combine -- switch it off first");
-    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+    return open_call(DeviceCall{entry, A, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
         if (int rc = ensure_a8_arrays(A, entry)) return rc;
         if (!A->a8_on) A->a8_valid = false;          // invalid until the next write of values
         A->a8_on = true;
@@ -3396,7 +3424,7 @@ extern "C" int sparta_vbs_set_a8_live(sparta_vbs_t* A, int32_t enable, void* str
     if (!A->a8_on || !A->a8_built || A->a8_ty < 0)
         return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the fp8 weight image is off -- switch it on first (sparta_vbs_set_forward_a8)");
     if (int rc = prune_handle_check(A, entry)) return rc;
-    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+    return open_call(DeviceCall{entry, A, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
         if (int rc = ensure_live_forward_arrays(A, entry)) return rc;      // the word map, seg_last and the compacted arrays of live forward: the same ones
         if (A->live_fwd_ty != A->a8_ty)
             return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the stream image that has the fp8 image has no live forward lists");
@@ -3426,7 +3454,7 @@ extern "C" int sparta_vbs_a8_live_info(sparta_vbs_t* A, int64_t* info_out, void*
     info_out[3] = ty >= 0 ? A->n_steps[ty] : 0;
     info_out[5] = A->a8_live_launches;
     if (!A->live_on || !lists) return SPARTA_OK;
-    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+    return open_call(DeviceCall{entry, A, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
         if (g_capturing) return capture_refusal("read the live ranges back (synchronises)", entry);
         HIP_TRY(hipStreamSynchronize(st));
         std::vector<int32_t> ranges((size_t)A->fwd_n_ranges * 2);
@@ -3443,7 +3471,7 @@ extern "C" int sparta_vbs_a8_get(sparta_vbs_t* A, uint8_t* codes, int32_t* exps,
     const char* entry = "sparta_vbs_a8_get";
     if (!A) return fail(SPARTA_ERR_INVALID, std::string(entry) + ": NULL handle");
     if (!A->a8_built || A->a8_ty < 0) return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": the handle has no fp8 image (sparta_vbs_set_forward_a8 was never on)");
-    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+    return open_call(DeviceCall{entry, A, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
         if (g_capturing) return capture_refusal("read the fp8 image back (synchronises)", entry);
         HIP_TRY(hipStreamSynchronize(st));
         const int ty = A->a8_ty, tms = ty ? 64 : 32, kp = A->kp16;
@@ -3526,7 +3554,7 @@ namespace {
 // the device state of an installed live set on the host (synchronises `st`)
 struct LiveDownload { std::vector<uint8_t> keep; std::vector<int32_t> groups, gcount, tids, tcount; };
 int live_download(sparta_vbs_t* A, const char* entry, void* stream, LiveDownload& D) {
-    return open_call(DeviceCall{entry, A->device, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
+    return open_call(DeviceCall{entry, A, (hipStream_t)stream, true}, [&](hipStream_t st) -> int {
         if (g_capturing) return capture_refusal("read the live set back (synchronises)", entry);
         HIP_TRY(hipStreamSynchronize(st));
         auto get = [](auto& vec, const void* src, int64_t n) {
@@ -3629,7 +3657,7 @@ int spmm_t_impl(sparta_vbs_t* A, const void* X, int64_t ldx, int32_t n_cols, flo
     const bool h16 = A->dtype != SPARTA_F32;
     if (h16 && ptr_space == SPARTA_PTR_DEVICE && (ldx & 1)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_spmm_t: 16-bit handles need an even ldx");
 
-    const DeviceCall call{"sparta_vbs_spmm_t", A->device, (hipStream_t)stream, ptr_space == SPARTA_PTR_DEVICE, dt_ms, "the product", A->ev0, A->ev1};
+    const DeviceCall call{"sparta_vbs_spmm_t", A, (hipStream_t)stream, ptr_space == SPARTA_PTR_DEVICE, dt_ms, "the product", A->ev0, A->ev1};
     return open_call(call, [&](hipStream_t st) -> int {
         const void* dX = X;
         float* dC = Ct;
@@ -3637,14 +3665,14 @@ int spmm_t_impl(sparta_vbs_t* A, const void* X, int64_t ldx, int32_t n_cols, flo
         const size_t x_elems = (size_t)ldx * (size_t)(n_cols - 1) + (size_t)A->rows, c_elems = (size_t)ldo * (size_t)(n_cols - 1) + (size_t)A->cols;
         if (ptr_space == SPARTA_PTR_HOST) {
             // host in, host out: X and Ct staged in one device buffer (Ct whole, so that its padding rows come back as they went); 16-bit handles round X on the device
-            if (int rc = A->d_t_ws.ensure((x_elems + c_elems) * sizeof(float))) return rc;
+            if (int rc = A->d_t_ws.ensure((x_elems + c_elems) * sizeof(float), A->retired)) return rc;
             float* ws = (float*)A->d_t_ws;
             HIP_TRY(hipMemcpyAsync(ws, X, x_elems * sizeof(float), hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(ws + x_elems, Ct, c_elems * sizeof(float), hipMemcpyHostToDevice, st));
             dX = ws; dC = ws + x_elems;
             if (h16) {
                 kx = (A->rows + 7) / 8 * 8;
-                if (int rc = A->d_t_h16.ensure((size_t)kx * (size_t)n_cols * sizeof(uint16_t))) return rc;
+                if (int rc = A->d_t_h16.ensure((size_t)kx * (size_t)n_cols * sizeof(uint16_t), A->retired)) return rc;
                 launch_convert_h16(A->dtype == SPARTA_BF16, st, ws, ldx, A->rows, n_cols, (uint16_t*)A->d_t_h16, kx);
                 HIP_TRY(hipGetLastError());
                 dX = A->d_t_h16;

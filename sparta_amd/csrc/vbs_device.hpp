@@ -429,16 +429,29 @@ inline int capture_refusal(const char* what, const char* entry = "sparta_vbs_spm
                                                  " -- run it once outside the capture first");
 }
 
-// grow-only scratch of a handle: ensure(need) keeps what is large enough, otherwise frees and allocates `need` bytes (never under capture).  Converts to
-// any pointer type, as the void* it replaces was cast at every use.
+// what a handle keeps for the graphs captured from its calls (sparta_vbs::retired): `captured` is set when a call under capture returns SPARTA_OK
+// (CaptureScope, vbs_capi.cpp); from then on a launch baked into a graph may hold the address of any scratch, so scratch that has to grow is moved here
+// instead of being freed.  Freed with the handle; every buffer is smaller than its successor.
+struct Retired {
+    bool captured = false;
+    std::vector<DevBuf<uint8_t>> bufs;
+};
+
+// grow-only scratch of a handle: ensure(need, keep) keeps what is large enough, otherwise frees and allocates `need` bytes (never under capture).  Converts
+// to any pointer type, as the void* it replaces was cast at every use.
+// Once the handle has been captured (keep.captured) the outgrown allocation is retired to keep.bufs, not freed: a captured graph may replay on it.
 struct DevScratch {
     size_t bytes() const { return buf_.bytes(); }
     void* get() const { return buf_.get(); }
     template <class U> operator U*() const { return (U*)buf_.get(); }
     explicit operator bool() const { return buf_.get() != nullptr; }
-    int ensure(size_t need) {
+    int ensure(size_t need, Retired& keep) {
         if (buf_.bytes() >= need) return SPARTA_OK;
         if (g_capturing) return capture_refusal("allocate scratch memory");
+        if (keep.captured && buf_.get()) {
+            keep.bufs.emplace_back();                            // (first: if the list cannot grow, nothing has moved)
+            keep.bufs.back() = std::move(buf_);
+        }
         HIP_TRY(buf_.alloc(need));
         return SPARTA_OK;
     }
@@ -479,8 +492,16 @@ struct sparta_vbs {
     // stream plan (w % 32 == 0): see vbs_spmm_f32_stream_kernel
     sparta_dev::DevBuf<sparta_dev::StepRec> d_steps[2];      // per tile type: [0] <= 32 rows, [1] 33..64 rows
     std::vector<sparta_dev::StepRec> h_steps[2];               // host copies (padded), source of the gathered-B variants
-    sparta_dev::DevBuf<sparta_dev::StepRec> d_steps_g[2];    // step lists for sparta_vbs_spmm_gathered with shard_rows == g_shard_rows
-    int64_t g_shard_rows = 0;
+    // step lists for sparta_vbs_spmm_gathered: one set per slab height the handle has been called with, kept until destroy and never rewritten (a graph
+    // captured at one height replays on that height's lists whatever heights are called later); g_cur = the set of the last call's height, -1: none yet
+    struct GatheredSteps {
+        int64_t shard_rows = 0;
+        sparta_dev::DevBuf<sparta_dev::StepRec> steps[2];     // per tile type, as d_steps
+        sparta_dev::DevBuf<sparta_dev::HubStep> hub;          // as d_hub_steps
+    };
+    std::vector<GatheredSteps> gathered;
+    int g_cur = -1;
+    sparta_dev::Retired retired;                              // outgrown scratch a captured graph may still replay on (DevScratch::ensure)
     sparta_dev::DevBuf<int32_t> d_wrange[2];
     sparta_dev::DevBuf<sparta_dev::FixRec> d_fix;
     std::vector<std::pair<int64_t, int64_t>> zero_ranges;   // long runs of rows without blocks (local C rows), see vbs_zero_rows_kernel
@@ -503,7 +524,6 @@ struct sparta_vbs {
     bool legacy_dropped = false;                  // fp32: the reference-layout image d_A was freed once the fragment image had won (rebuilt on demand, then kept)
     // hub plan (16-bit handles of 64-wide blocks; vbs_plan.cpp, k_hub16.hip)
     sparta_dev::DevBuf<sparta_dev::HubStep> d_hub_steps;
-    sparta_dev::DevBuf<sparta_dev::HubStep> d_hub_steps_g; // step list for sparta_vbs_spmm_gathered with shard_rows == g_shard_rows
     std::vector<sparta_dev::HubStep> h_hub_steps; // host copy (padded), source of the gathered variant
     sparta_dev::DevBuf<sparta_dev::HubTile> d_hub_tiles;
     sparta_dev::DevBuf<int32_t> d_hub_wrange;
