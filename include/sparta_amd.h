@@ -874,6 +874,55 @@ int sparta_vbs_move_blocks(sparta_vbs_t* dst, const sparta_vbs_t* src, const int
                            const float* S0, float* D0, const float* S1, float* D1, const float* S2, float* D2, const float* S3, float* D3,
                            void* stream, float* dt_ms);
 
+/* ---- DENSE <-> BLOCKS: a dense matrix on the device scored, sampled into the mab layout of a handle and written back (k_dense.hip) ---------------------
+ * The way into the block-sparse stack from a dense weight matrix, and the way back out.  Device pointers only, all three entries.
+ *
+ * D: a dense rows x cols matrix in SPARTA_ROW_MAJOR (element (r, c) at D[r * ldd + c], ldd >= cols) or SPARTA_COL_MAJOR (D[c * ldd + r], ldd >= rows) of
+ * d_dtype SPARTA_F32, SPARTA_F16 or SPARTA_BF16 -- independent of a handle's storage type.  It may start on any element boundary (2 bytes for the 16-bit
+ * types, 4 for fp32).  For a handle, rows and cols are the handle's: a range handle has the rows of its block-rows, and row 0 of D is the first row of the
+ * range (as its slice of mab counts "from 0").  T: nztot floats in the layout of sparta_vbs_host.mab on any 4-byte boundary: element i of stored column q of
+ * a block is T[off + q * h + i] (off, h, jb: sparta_vbs_block_table_host).  No kernel dereferences a misaligned vector pointer: accesses are 16 bytes wide
+ * where base, leading dimension, block height and width allow it for a whole tile, one element wide elsewhere.
+ *
+ * sparta_vbs_gather_dense: for every stored block T[off + q * h + i] = D[r0 + i, jb * w + q] for the columns inside the matrix; the stored positions past
+ * `cols` of a ragged last block column get +0.0f.  Every element of T is written (T may be uninitialised); nothing of D outside the stored blocks is read.
+ * fp32 D travels as 32-bit words: NaN payloads, -0.0 and denormals arrive bit for bit.  bf16 is widened by a 16-bit shift, bit for bit.  fp16 is widened
+ * exactly; a NaN stays a NaN, its payload is not specified.
+ *
+ * sparta_vbs_scatter_dense: the inverse, D[r0 + i, jb * w + q] = T[off + q * h + i] for the columns inside the matrix; positions of T past `cols` are not
+ * read.  A 16-bit D receives the value rounded to nearest even exactly as sparta_vbs_create rounds a 16-bit handle's values and as every image is rounded
+ * (bf16 keeps a NaN a NaN, Inf stays Inf; a finite fp32 above the fp16 range becomes Inf).  fill == 0: every element of D outside the stored blocks keeps
+ * its bits.  fill != 0: every element of the rows x cols region outside the stored blocks becomes +0 of D's type (one launch that stores the region as +0,
+ * in front of the scatter; with an empty pattern it runs alone).  The ldd padding is never written.  A handle that stores the same block column twice in
+ * one block-row is refused with SPARTA_ERR_UNSUPPORTED (two blocks would write the same elements of D; gather takes it): found when the table is built.
+ *
+ * Handles: every handle made from VBS arrays (sparta_vbs_create, _create_range, _create_range_ex with any flags, all three dtypes -- the handles of
+ * sparta_vbs_block_ssq); those of sparta_vbs_create_from_csr / _create_transposed: SPARTA_ERR_UNSUPPORTED.  Neither entry reads or writes an image of the
+ * handle: to make a handle multiply with gathered values, follow with sparta_vbs_set_values.  The FIRST call of either entry on a handle builds and uploads
+ * one 32-byte record per chunk of at most 64 rows of a stored block (offset, first row, first column, height, the chunk's rows, columns inside the matrix --
+ * from the block table of sparta_vbs_block_table_host over the handle's own arrays; a block 257 rows tall is five work items, a block of height 0 none) into
+ * storage the handle owns, and returns SPARTA_ERR_UNSUPPORTED while the stream is being captured.  Every later call is launches only (one, or two with
+ * fill), no allocation, no synchronisation, and can be captured; a replay reads D / T again.  *dt_ms != NULL under capture: SPARTA_ERR_UNSUPPORTED.
+ *
+ * sparta_dense_block_ssq (no handle): ssq_out[ib * block_cols + jb], block_cols = (cols - 1) / block_col_size + 1, is the fp64 sum of the exact fp64 squares of
+ * the elements of grid block (ib, jb) -- rows row_part[ib] .. row_part[ib + 1] - 1, columns jb * w .. -- that lie inside the matrix: the definition of
+ * sparta_vbs_block_ssq, so a handle that stores the block and holds the gathered values scores it alike up to the order of the additions.  row_part:
+ * DEVICE, block_rows + 1 int64, non-decreasing from 0 to at most rows (it is read by the kernel only, which clamps it into [0, rows]: nothing outside D is
+ * read whatever it holds).  One wave per grid block, its runs (rows of the block in row-major, columns in column-major) in a fixed order with fma(d, d, acc)
+ * into four accumulators per lane, lanes by xor-shuffle, no atomics, one launch: the score depends on the block's elements and shape alone, is bit-identical
+ * from run to run and between an eager call and a replay, and lies within n_in * 2^-53 * ssq of the exact sum (the bound of sparta_vbs_block_ssq).  A block
+ * of a block-row of height 0 scores 0.0 (also when rows == 0: the scores are stored, D is not read); an Inf or NaN makes exactly its own block's score
+ * non-finite.  Launches only: capturable from the first call.
+ *
+ * SPARTA_ERR_INVALID, with nothing launched and no output touched: a NULL handle; NULL D, T, ssq_out with work to do; a layout or dtype code that is none of
+ * the above; ldd too small; D not aligned to its element, T to 4 bytes, row_part / ssq_out to 8; negative dimensions or block_col_size <= 0; row_part NULL
+ * with block_rows > 0.  2^31 or more rows or columns, a block of 2^31 or more elements, more than 2^31 - 1 grid blocks: SPARTA_ERR_UNSUPPORTED.  Empty work
+ * (nztot == 0; no grid block) succeeds and launches nothing -- except that fill on an empty pattern still fills. */
+int sparta_dense_block_ssq(const void* D, int64_t ldd, int32_t d_layout, int32_t d_dtype, int64_t rows, int64_t cols, int64_t block_rows, int64_t block_col_size,
+                           const int64_t* row_part /* device, block_rows + 1 */, double* ssq_out /* device, [block_rows][block_cols] */, void* stream, float* dt_ms);
+int sparta_vbs_gather_dense(sparta_vbs_t* A, const void* D, int64_t ldd, int32_t d_layout, int32_t d_dtype, float* T, void* stream, float* dt_ms);
+int sparta_vbs_scatter_dense(sparta_vbs_t* A, const float* T, void* D, int64_t ldd, int32_t d_layout, int32_t d_dtype, int32_t fill, void* stream, float* dt_ms);
+
 /* Ct (+)= A^T * X on the stored blocks of A: the gradient of the dense operand of C = A * B (X = dC, Ct = dB), on the handle itself, so that
  * it follows sparta_vbs_set_values in stream order.  Only handles made with SPARTA_CREATE_TRANSPOSE take the call; every other handle
  * (flags without the bit, sparta_vbs_create, _create_range, _create_from_csr, _create_transposed): SPARTA_ERR_UNSUPPORTED.

@@ -59,6 +59,7 @@ SYMBOLS = [
     "sparta_vbs_set_forward_a8", "sparta_vbs_a8_info", "sparta_vbs_a8_get", "sparta_a8_quantize_group",
     "sparta_vbs_set_a8_live", "sparta_vbs_a8_live_info",
     "sparta_vbs_repattern_host", "sparta_vbs_move_blocks",
+    "sparta_dense_block_ssq", "sparta_vbs_gather_dense", "sparta_vbs_scatter_dense",
     "sparta_debug_device_allocs",
 ]
 
@@ -195,6 +196,9 @@ def _load():
     L.sparta_vbs_repattern_host.argtypes = [C.c_int64, C.c_int64, C.c_int64, i64p, i64p, i64p, C.c_int64, C.c_int64, C.POINTER(C.c_uint8), i64p, C.c_int64,
                                             i64p, i64p, i32p, i64p]
     L.sparta_vbs_move_blocks.argtypes = [vp, vp, i32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, vp, f32p]
+    L.sparta_dense_block_ssq.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, f32p]
+    L.sparta_vbs_gather_dense.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, f32p]
+    L.sparta_vbs_scatter_dense.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, f32p]
     L.sparta_vbs_create_from_csr.argtypes =[C.POINTER(vp), C.c_int64, C.c_int64, i64p, i32p, f32p, i64p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]
     L.sparta_vbs_plan_stats.argtypes = [C.c_int64, C.c_int64, i64p, i32p, f32p, i64p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, i64p]
     L.sparta_vbs_prepare_b.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, vp, C.POINTER(vp)]

@@ -2989,6 +2989,125 @@ extern "C" int sparta_vbs_move_blocks(sparta_vbs_t* dst, const sparta_vbs_t* src
     SPARTA_GUARD_END("sparta_vbs_move_blocks")
 }
 
+// ---- dense <-> blocks: sparta_dense_block_ssq, sparta_vbs_gather_dense, sparta_vbs_scatter_dense (k_dense.hip) ---------------------------------------
+namespace {
+
+// what the three entries ask of D; D == NULL is judged by the caller (it depends on whether there is work)
+int dense_operand_check(const char* entry, const void* D, int64_t ldd, int32_t layout, int32_t dtype, int64_t rows, int64_t cols) {
+    using sparta::fail;
+    const std::string e(entry);
+    if (layout != SPARTA_ROW_MAJOR && layout != SPARTA_COL_MAJOR) return fail(SPARTA_ERR_INVALID, e + ": unknown layout " + std::to_string(layout) + " of D");
+    if (dtype != SPARTA_F32 && dtype != SPARTA_F16 && dtype != SPARTA_BF16) return fail(SPARTA_ERR_INVALID, e + ": unknown dtype " + std::to_string(dtype) + " of D");
+    if (ldd < (layout == SPARTA_ROW_MAJOR ? cols : rows))
+        return fail(SPARTA_ERR_INVALID, e + ": the leading dimension of D is too small (row-major: ldd >= cols, column-major: ldd >= rows)");
+    if ((uintptr_t)D % (dtype == SPARTA_F32 ? 4u : 2u) != 0) return fail(SPARTA_ERR_INVALID, e + ": D is not aligned to its element size");
+    if (rows > INT32_MAX || cols > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, e + ": 2^31 or more rows or columns");
+    return SPARTA_OK;
+}
+
+// the chunk records, made at the first call from the block table of the handle (build_block_table over the heights and counts kept at creation and the
+// handle's jab): per stored block of height > 0 one record per kDenseChunk rows
+int ensure_dense_table(sparta_vbs_t* A, const char* entry) {
+    using sparta::fail;
+    if (A->n_dense >= 0) return SPARTA_OK;
+    if (g_capturing) return capture_refusal("build and upload its table of block chunks", entry);
+    std::vector<int64_t> table;
+    if (int rc = host_block_table(A, entry, table)) return rc;
+    const int64_t nb = A->nblocks, w = A->w;
+    std::vector<DenseItem> items;
+    std::vector<int64_t> words((size_t)nb);                               // (block-row << 32 | block column: equal neighbours once sorted = a column stored twice)
+    for (int64_t q = 0; q < nb; q++) words[(size_t)q] = table[(size_t)(4 * q + 3)];
+    std::sort(words.begin(), words.end());
+    const bool dup = std::adjacent_find(words.begin(), words.end()) != words.end();
+    for (int64_t q = 0; q < nb; q++) {
+        const int64_t* t = table.data() + 4 * q;
+        const int64_t ib = t[3] >> 32, jb = t[3] & 0xffffffffll;
+        if (t[2] > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": a block of 2^31 or more elements");
+        const int64_t r0 = A->h_row_part[(size_t)ib], h = A->h_row_part[(size_t)ib + 1] - r0, c0 = jb * w;
+        for (int64_t i0 = 0; i0 < h; i0 += kDenseChunk)
+            items.push_back(DenseItem{t[0], (int32_t)r0, (int32_t)c0, (int32_t)h, (int32_t)i0, (int32_t)std::min<int64_t>(kDenseChunk, h - i0),
+                                      (int32_t)std::min(w, A->cols - c0)});
+    }
+    if ((int64_t)items.size() > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, std::string(entry) + ": more than 2^31 - 1 block chunks");
+    if (!items.empty()) HIP_TRY(A->d_dense.upload(items));
+    A->dense_dup = dup;
+    A->n_dense = (int64_t)items.size();
+    return SPARTA_OK;
+}
+
+}  // namespace
+
+extern "C" int sparta_dense_block_ssq(const void* D, int64_t ldd, int32_t d_layout, int32_t d_dtype, int64_t rows, int64_t cols, int64_t block_rows, int64_t block_col_size,
+                                      const int64_t* row_part, double* ssq_out, void* stream, float* dt_ms) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* me = "sparta_dense_block_ssq";
+    if (rows < 0 || cols < 0 || block_rows < 0 || block_col_size <= 0) return fail(SPARTA_ERR_INVALID, std::string(me) + ": bad dimensions");
+    if (int rc = dense_operand_check(me, D, ldd, d_layout, d_dtype, rows, cols)) return rc;
+    if (block_rows > 0 && !row_part) return fail(SPARTA_ERR_INVALID, std::string(me) + ": row_part is NULL with block_rows > 0");
+    if ((uintptr_t)row_part % 8 != 0 || (uintptr_t)ssq_out % 8 != 0) return fail(SPARTA_ERR_INVALID, std::string(me) + ": row_part and ssq_out must be 8-byte aligned");
+    const int64_t block_cols = cols > 0 ? (cols - 1) / block_col_size + 1 : 0;
+    if (block_cols > 0 && block_rows > INT32_MAX / block_cols) return fail(SPARTA_ERR_UNSUPPORTED, std::string(me) + ": more than 2^31 - 1 grid blocks");
+    const bool nothing = block_rows == 0 || block_cols == 0;
+    if (!nothing && !ssq_out) return fail(SPARTA_ERR_INVALID, std::string(me) + ": ssq_out is NULL");
+    if (!nothing && rows > 0 && !D) return fail(SPARTA_ERR_INVALID, std::string(me) + ": D is NULL");
+    return device_call(DeviceCall{me, nullptr, (hipStream_t)stream, true, dt_ms, "the kernel", nullptr, nullptr, nothing}, [&](hipStream_t st) {
+        launch_dense_block_ssq(st, D, ldd, d_layout == SPARTA_ROW_MAJOR, d_dtype, rows, cols, block_rows, block_col_size, row_part, ssq_out);
+    });
+    SPARTA_GUARD_END("sparta_dense_block_ssq")
+}
+
+extern "C" int sparta_vbs_gather_dense(sparta_vbs_t* A, const void* D, int64_t ldd, int32_t d_layout, int32_t d_dtype, float* T, void* stream, float* dt_ms) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* me = "sparta_vbs_gather_dense";
+    if (int rc = prune_handle_check(A, me)) return rc;
+    if (int rc = dense_operand_check(me, D, ldd, d_layout, d_dtype, A->rows, A->cols)) return rc;
+    if ((uintptr_t)T % 4 != 0) return fail(SPARTA_ERR_INVALID, std::string(me) + ": T must be 4-byte aligned");
+    const bool nothing = A->nztot == 0;
+    if (!nothing && (!D || !T)) return fail(SPARTA_ERR_INVALID, std::string(me) + ": D or T is NULL");
+    const DeviceCall call{me, A, (hipStream_t)stream, true, dt_ms, "the kernel", A->ev0, A->ev1, nothing};
+    return open_call(call, [&](hipStream_t) -> int {
+        if (!nothing)
+            if (int rc = ensure_dense_table(A, me)) return rc;
+        return timed_launches(call, [&](hipStream_t st) {
+            launch_dense_gather(st, A->d_dense, A->n_dense, D, ldd, d_layout == SPARTA_ROW_MAJOR, d_dtype, (int)A->w, T);
+        });
+    });
+    SPARTA_GUARD_END("sparta_vbs_gather_dense")
+}
+
+extern "C" int sparta_vbs_scatter_dense(sparta_vbs_t* A, const float* T, void* D, int64_t ldd, int32_t d_layout, int32_t d_dtype, int32_t fill, void* stream,
+                                        float* dt_ms) {
+    SPARTA_GUARD_BEGIN
+    using sparta::fail;
+    const char* me = "sparta_vbs_scatter_dense";
+    if (int rc = prune_handle_check(A, me)) return rc;
+    if (int rc = dense_operand_check(me, D, ldd, d_layout, d_dtype, A->rows, A->cols)) return rc;
+    if ((uintptr_t)T % 4 != 0) return fail(SPARTA_ERR_INVALID, std::string(me) + ": T must be 4-byte aligned");
+    const bool blocks = A->nztot > 0, region = fill != 0 && A->rows > 0 && A->cols > 0, nothing = !blocks && !region;
+    if (!nothing && !D) return fail(SPARTA_ERR_INVALID, std::string(me) + ": D is NULL");
+    if (blocks && !T) return fail(SPARTA_ERR_INVALID, std::string(me) + ": T is NULL");
+    const bool row_major = d_layout == SPARTA_ROW_MAJOR;
+    if (region) {
+        const int64_t esz = d_dtype == SPARTA_F32 ? 4 : 2, segs = dense_fill_segs((row_major ? A->cols : A->rows) * esz), n_runs = row_major ? A->rows : A->cols;
+        if (n_runs > INT32_MAX / segs) return fail(SPARTA_ERR_UNSUPPORTED, std::string(me) + ": the fill needs more than 2^31 - 1 workgroups");
+    }
+    const DeviceCall call{me, A, (hipStream_t)stream, true, dt_ms, "the kernels", A->ev0, A->ev1, nothing};
+    return open_call(call, [&](hipStream_t) -> int {
+        if (blocks) {
+            if (int rc = ensure_dense_table(A, me)) return rc;
+            if (A->dense_dup)
+                return fail(SPARTA_ERR_UNSUPPORTED, std::string(me) + ": a block-row of the handle stores a block column twice (two blocks would write the same elements of D)");
+        }
+        return timed_launches(call, [&](hipStream_t st) {
+            if (region) launch_dense_fill(st, D, ldd, row_major, d_dtype, A->rows, A->cols);
+            if (blocks) launch_dense_scatter(st, A->d_dense, A->n_dense, T, D, ldd, row_major, d_dtype);
+        });
+    });
+    SPARTA_GUARD_END("sparta_vbs_scatter_dense")
+}
+
 // ---- the live-block set: sparta_vbs_set_live_blocks, _live_info, _live_lists_get, _live_lists_host (k_live.hip) ----------------------------------
 namespace {
 

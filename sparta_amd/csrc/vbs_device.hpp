@@ -341,6 +341,12 @@ constexpr int kPruneWaves = kThreads / 64;    // blocks per workgroup: one wave 
 // how many (n_all), and whether the block is moved (1) or new (0: zeros, nothing read)
 struct MoveBlock { int64_t src_off, dst_off; int32_t n_all, moved; };
 static_assert(sizeof(MoveBlock) == 24, "MoveBlock must stay 24 bytes");
+// dense <-> blocks (k_dense.hip): one record per chunk of at most 64 rows of a stored block, mab order: the block's first element in the mab layout, its
+// first row (from the start of the handle's range) and first column in the dense matrix, its height, the chunk's first row inside the block and its rows,
+// and the block's stored columns inside the matrix.  Blocks of height 0 have no record.
+struct DenseItem { int64_t off; int32_t r0, c0, h, i0, hc, valid; };
+static_assert(sizeof(DenseItem) == 32, "DenseItem must stay 32 bytes");
+constexpr int kDenseChunk = 64;
 
 // the epilogue of a linear layer (k_epilogue.hip): column-major rows x n_cols operands.  A work item = a tile of kThreads rows x a run of kEpRun columns.
 // Rows [head, head + 4 n4) are the body (vec_tiles tiles, a lane owns four rows: every operand is aligned there in every column), the others the edge
@@ -628,6 +634,11 @@ struct sparta_vbs {
     int64_t n_prune = -1;                                      // -1: not built yet
     // repattern (sparta_vbs_move_blocks with this handle as the destination): the records of the last call, grown when needed
     sparta_dev::DevScratch d_repat;
+    // dense <-> blocks (sparta_vbs_gather_dense / sparta_vbs_scatter_dense): the chunk records, built from the same rows as the block table and uploaded at
+    // the first call; whether a block-row stores a block column twice (scatter is refused then: two blocks would write the same elements of D)
+    sparta_dev::DevBuf<sparta_dev::DenseItem> d_dense;
+    int64_t n_dense = -1;                                      // -1: not built yet
+    bool dense_dup = false;
     // the live-block set (sparta_vbs_set_live_blocks): whether one is installed is host state; the helper arrays (pattern only) are built at the first call,
     // the snapshot and the compacted lists are written by the launches of every call (k_live.hip)
     bool live_on = false, live_built = false;
@@ -784,6 +795,14 @@ void launch_block_ssq(hipStream_t st, const PruneBlock* blocks, int64_t n_blocks
 void launch_mask_blocks(hipStream_t st, const PruneBlock* blocks, int64_t n_blocks, const uint8_t* keep, float* T0, float* T1, float* T2, float* T3);
 // k_repattern.hip: one wave per record; per non-NULL pair (S[q], D[q]) the block copied bit for bit from the source layout or stored as +0.0f
 void launch_move_blocks(hipStream_t st, const MoveBlock* blocks, int64_t n_blocks, const float* const* S, float* const* D);
+// k_dense.hip: one wave per record (gather: T written from D, the stored positions past cols as +0.0f; scatter: D written from T); the rows x cols region
+// of D stored as +0 (dense_fill_segs: its workgroups per run); one wave per block of the (row_part, w) grid for the fp64 sums of squares
+void launch_dense_gather(hipStream_t st, const DenseItem* items, int64_t n_items, const void* D, int64_t ldd, int row_major, int dtype, int w, float* T);
+void launch_dense_scatter(hipStream_t st, const DenseItem* items, int64_t n_items, const float* T, void* D, int64_t ldd, int row_major, int dtype);
+int64_t dense_fill_segs(int64_t run_bytes);
+void launch_dense_fill(hipStream_t st, void* D, int64_t ldd, int row_major, int dtype, int64_t rows, int64_t cols);
+void launch_dense_block_ssq(hipStream_t st, const void* D, int64_t ldd, int row_major, int dtype, int64_t rows, int64_t cols, int64_t block_rows, int64_t w,
+                            const int64_t* row_part, double* ssq_out);
 // k_epilogue.hip: Y = act(Z + bias); dZ = dY * act'(Z + bias), and with p.dbias the fixed-order fp64 row sums (a second launch folds the runs when n_runs != 1)
 void launch_epilogue_fwd(hipStream_t st, int y_dtype, const EpilogueParams& p);
 void launch_epilogue_bwd(hipStream_t st, int dy_dtype, int dz_dtype, const EpilogueParams& p);

@@ -710,6 +710,69 @@ class DeviceVBS(ValuesRecord):
             total += dt.value
         return total if timed else None
 
+    def _dense_operand(self, D):
+        layout, ldd, dt = _dense_layout(D)
+        if D.device.index != self.device:
+            raise ValueError("D must live on device %d" % self.device)
+        if tuple(D.shape) != (self.rows, self.cols):
+            raise ValueError("D must be %d x %d (the rows of the handle's block-rows x cols)" % (self.rows, self.cols))
+        return layout, ldd, dt
+
+    def gather_dense(self, D, out=None, timed=False, stream=None):
+        """sparta_vbs_gather_dense, device tensors: the dense matrix D sampled into the mab layout of the handle -- values[off + q * h + i] = D[r0 + i, jb * w
+        + q] for every stored block; the stored positions past cols get +0.0; nothing of D outside the stored blocks is read.  D: a 2-D float32, float16 or
+        bfloat16 tensor on this device of the handle's rows x cols (a range handle: the rows of its block-rows), independent of the handle's own dtype; the
+        layout and the leading dimension are taken from its strides, one of which must be 1 (row-major: nn.Linear.weight as it is; column-major: its .t())
+        -- anything else raises ValueError, nothing is copied silently.  fp32 and bf16 values arrive bit for bit, fp16 exactly.  out: a contiguous float32
+        tensor of nztot elements on this device, or None (allocated); every element is written.  The handle's images are NOT changed: follow with
+        set_values.  Stream-ordered on torch's current stream; launches only after the first gather_dense / scatter_dense on the handle (capturable from
+        then on).  Returns out, or (out, kernel ms) if timed."""
+        import torch
+        layout, ldd, dt_code = self._dense_operand(D)
+        n = self._nztot()
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=D.device)
+        T = self._prune_operand("out", out)
+        st = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+        dt = C.c_float(0)
+        check(lib.sparta_vbs_gather_dense(self.h, C.c_void_p(D.data_ptr() if D.numel() else None), ldd, layout, dt_code, C.cast(T, C.c_void_p), C.c_void_p(st),
+                                          C.byref(dt) if timed else None))
+        return (out, dt.value) if timed else out
+
+    def scatter_dense(self, values, D, fill=True, timed=False, stream=None):
+        """sparta_vbs_scatter_dense, device tensors: the inverse of gather_dense, D[r0 + i, jb * w + q] = values[off + q * h + i] for every stored block (the
+        stored positions past cols are not read), written in place into D (as for gather_dense: float32, float16 or bfloat16, one stride 1; a 16-bit D gets
+        the handle-creation rounding, nearest even).  fill=True: the rest of the rows x cols region becomes +0, so that D is the dense form of the sparse
+        matrix; fill=False: the rest keeps its bits.  Padding between rows (columns) of a strided D is never written.  A handle that stores a block column
+        twice in one block-row is refused.  The version counter of D is bumped.  Stream-ordered on torch's current stream; capturable after the first
+        gather_dense / scatter_dense on the handle.  Returns kernel ms if timed else None."""
+        import torch
+        layout, ldd, dt_code = self._dense_operand(D)
+        T = self._prune_operand("values", values.detach())
+        st = torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+        dt = C.c_float(0)
+        check(lib.sparta_vbs_scatter_dense(self.h, C.cast(T, C.c_void_p), C.c_void_p(D.data_ptr() if D.numel() else None), ldd, layout, dt_code, int(bool(fill)),
+                                           C.c_void_p(st), C.byref(dt) if timed else None))
+        bump = getattr(torch.autograd.graph, "increment_version", None)
+        if bump is not None:
+            bump(D)
+        else:
+            with torch.no_grad():
+                D.add_(0)
+        return dt.value if timed else None
+
+    def to_dense(self, values, dtype=None, row_major=True):
+        """a fresh rows x cols tensor (dtype: torch.float32 by default, float16 or bfloat16) holding `values` in the stored blocks and +0 elsewhere:
+        scatter_dense with fill into an allocation of its own.  row_major=False returns the same matrix with column-major strides."""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        if row_major:
+            D = torch.empty((self.rows, self.cols), dtype=dtype, device=values.device)
+        else:
+            D = torch.empty((self.cols, self.rows), dtype=dtype, device=values.device).t()
+        self.scatter_dense(values, D, fill=True)
+        return D
+
     def set_values_host(self, mab):
         """set_values with a host array (numpy, fp32, nztot elements), staged through scratch of the handle.  Returns kernel ms."""
         mab = np.ascontiguousarray(mab, np.float32).reshape(-1)
@@ -852,6 +915,119 @@ class PreparedB:
             self.close()
         except Exception:
             pass
+
+
+def _dense_layout(D):
+    """(layout, ldd, dtype code) of a 2-D device tensor as the dense entries take it: one stride must be 1, the other at least the extent it steps over"""
+    import torch
+    codes = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
+    if not (hasattr(D, "is_cuda") and D.is_cuda and D.dim() == 2 and D.dtype in codes):
+        raise ValueError("D must be a 2-D float32, float16 or bfloat16 tensor on the GPU")
+    (rows, cols), (s0, s1) = D.shape, D.stride()
+    if (s1 == 1 or cols <= 1) and (s0 >= cols or rows <= 1):
+        return _lib.ROW_MAJOR, max(int(s0) if rows > 1 else 0, cols, 1), codes[D.dtype]
+    if (s0 == 1 or rows <= 1) and (s1 >= rows or cols <= 1):
+        return _lib.COL_MAJOR, max(int(s1) if cols > 1 else 0, rows, 1), codes[D.dtype]
+    raise ValueError("D must have a stride of 1 along its rows or its columns and must not overlap itself (strides %r for shape %r): make it contiguous "
+                     "yourself, nothing is copied silently" % (tuple(D.stride()), tuple(D.shape)))
+
+
+def dense_block_ssq(D, row_part, block_col_size, out=None, timed=False, stream=None):
+    """sparta_dense_block_ssq: the block scores of a dense matrix on the device, without a handle.  D: a 2-D float32, float16 or bfloat16 device tensor with
+    one stride 1 (as DeviceVBS.gather_dense takes it); row_part: the first rows of the block-rows and, last, rows (block_rows + 1 non-decreasing entries
+    from 0) as a sequence, a numpy array or a torch tensor (an int64 tensor on D's device is used as it is); block_col_size: w.  Returns a float64 tensor
+    (block_rows, block_cols): per grid block the sum of the squares of its elements inside the matrix, what DeviceVBS.block_ssq gives for a stored block
+    holding the same values.  One launch on torch's current stream, capturable.  Returns the scores, or (scores, kernel ms) if timed."""
+    import torch
+    layout, ldd, dt_code = _dense_layout(D)
+    rows, cols = D.shape
+    w = int(block_col_size)
+    if w <= 0:
+        raise ValueError("block_col_size must be > 0")
+    if isinstance(row_part, torch.Tensor):
+        rp = row_part.to(device=D.device, dtype=torch.int64).contiguous()
+    else:
+        rp = torch.as_tensor(np.ascontiguousarray(row_part, np.int64), device=D.device)
+    if rp.dim() != 1 or rp.numel() < 1:
+        raise ValueError("row_part must hold block_rows + 1 entries")
+    block_rows, block_cols = rp.numel() - 1, ((cols - 1) // w + 1 if cols > 0 else 0)
+    if out is None:
+        out = torch.empty((block_rows, block_cols), dtype=torch.float64, device=D.device)
+    elif not (out.is_cuda and out.dtype == torch.float64 and out.device == D.device and out.is_contiguous() and out.numel() == block_rows * block_cols):
+        raise ValueError("out must be a contiguous float64 tensor of block_rows * block_cols = %d elements on D's device" % (block_rows * block_cols))
+    with torch.cuda.device(D.device):
+        st = torch.cuda.current_stream(D.device).cuda_stream if stream is None else stream
+        dt = C.c_float(0)
+        check(lib.sparta_dense_block_ssq(C.c_void_p(D.data_ptr() if D.numel() else None), ldd, layout, dt_code, int(rows), int(cols), block_rows, w,
+                                         C.c_void_p(rp.data_ptr()), C.c_void_p(out.data_ptr() if out.numel() else None), C.c_void_p(st),
+                                         C.byref(dt) if timed else None))
+    out = out.view(block_rows, block_cols)
+    return (out, dt.value) if timed else out
+
+
+def sparsify(D, block_col_size, row_part=None, row_block_size=None, sparsity=None, mask=None, normalize=True, dtype=_lib.F32, device=None, updatable=True,
+             transposable=True):
+    """A dense layer made block-sparse on the device: -> (vbmat, handle, values).
+
+    D: the dense weight matrix, a 2-D float32 / float16 / bfloat16 device tensor with one stride 1 (nn.Linear.weight as it is).  The grid: block columns of
+    block_col_size, block-rows from row_part (block_rows + 1 entries from 0 to rows) or of row_block_size rows each (the last one shorter); one of the two.
+    Which blocks are stored: those of `mask` ((block_rows, block_cols), non-zero = stored; a tensor or an array -- a pattern from elsewhere, a random SET
+    pattern), or, with `sparsity`, the blocks prune.select keeps at that sparsity on the scores dense_block_ssq(D) -- divided by the block's elements inside
+    the matrix when normalize, a block without an element scoring +Inf, as BlockPruner.scores does; the lowest scores go first, ties to the lower index.
+    The mask is downloaded (one byte per grid block: the only host read), VBR.from_block_mask builds the pattern, to_device the handle (dtype, device --
+    default D's --, updatable, transposable), gather_dense the values, set_values gives them to the handle.
+    Returns the pattern-only VBR (its mab is zeros: the values live in `values`), the handle, and `values`: a float32 leaf tensor of nztot elements,
+    requires_grad set, ready for vbs_linear, VbsSGD and VbsAdamW."""
+    import torch
+    from . import prune
+    from .host import VBR
+    _dense_layout(D)
+    rows, cols = (int(x) for x in D.shape)
+    w = int(block_col_size)
+    if (row_part is None) == (row_block_size is None):
+        raise ValueError("give exactly one of row_part and row_block_size")
+    if (mask is None) == (sparsity is None):
+        raise ValueError("give exactly one of sparsity and mask")
+    if row_part is None:
+        hb = int(row_block_size)
+        if hb <= 0:
+            raise ValueError("row_block_size must be > 0")
+        row_part = np.minimum(np.arange(0, rows + hb, hb, dtype=np.int64), rows)[:(rows + hb - 1) // hb + 1]
+    elif isinstance(row_part, torch.Tensor):
+        row_part = row_part.detach().cpu().numpy()
+    row_part = np.ascontiguousarray(row_part, np.int64).reshape(-1)
+    block_rows, block_cols = len(row_part) - 1, (cols - 1) // w + 1
+    if mask is None:
+        rp_dev = torch.as_tensor(row_part, device=D.device)
+        s = dense_block_ssq(D.detach(), rp_dev, w)
+        if normalize:
+            hts = (rp_dev[1:] - rp_dev[:-1]).to(torch.float64)
+            wid = torch.clamp(cols - torch.arange(block_cols, device=D.device, dtype=torch.int64) * w, max=w).to(torch.float64)
+            n_in = hts[:, None] * wid[None, :]
+            s = torch.where(n_in > 0, s / n_in, torch.full_like(s, float("inf")))
+        keep = prune.select([s.reshape(-1)], [torch.ones(s.numel(), dtype=torch.uint8, device=D.device)], float(sparsity), "layer")[0]
+        mask = keep.reshape(block_rows, block_cols).cpu().numpy()                  # (synchronises: the one host read)
+    elif isinstance(mask, torch.Tensor):
+        mask = (mask.detach() != 0).to(torch.uint8).cpu().numpy()
+    vbmat = VBR.from_block_mask(rows, cols, row_part, w, mask)
+    dev = D.device.index if device is None else int(device)
+    if dev != D.device.index:
+        raise ValueError("device must be D's device (%d)" % D.device.index)
+    handle = vbmat.to_device(dev, dtype=dtype, updatable=updatable, transposable=transposable)
+    try:
+        values = handle.gather_dense(D.detach())
+        if updatable:
+            handle.set_values(values)
+        elif values.numel():
+            # a handle that takes no new values is created from them: the gathered values go through the host once and vbmat.mab holds them
+            vbmat.set_values(values.cpu().numpy())
+            handle.close()
+            handle = vbmat.to_device(dev, dtype=dtype, updatable=False, transposable=transposable)
+    except Exception:
+        handle.close()
+        raise
+    values.requires_grad_(True)
+    return vbmat, handle, values
 
 
 def repattern(vbmat, handle, tensors, keep=None, add=None, block_row_range=None):

@@ -337,6 +337,28 @@ class VBR:
         v._drop_device_images()
         return v
 
+    @classmethod
+    def from_block_mask(cls, rows, cols, row_part, block_col_size, mask):
+        """The pattern-only VBR of a block mask (host): block-rows from row_part (block_rows + 1 non-decreasing entries from 0 to rows), block columns of
+        block_col_size; block-row ib stores, in ascending order, the block columns jb with mask[ib, jb] != 0.  mask: (block_rows, block_cols), any dtype
+        (block_cols = (cols - 1) // block_col_size + 1); any other shape raises ValueError.  mab is zeros: the values of a layer made this way live in a
+        tensor of their own (DeviceVBS.gather_dense, sparta_amd.sparsify)."""
+        rows, cols, w = int(rows), int(cols), int(block_col_size)
+        if rows < 0 or cols <= 0 or w <= 0:
+            raise ValueError("rows >= 0, cols > 0 and block_col_size > 0 are required")
+        rp = np.ascontiguousarray(row_part, np.int64).reshape(-1)
+        if len(rp) < 1 or rp[0] != 0 or rp[-1] != rows or np.any(np.diff(rp) < 0):
+            raise ValueError("row_part must be non-decreasing from 0 to rows")
+        block_rows, block_cols = len(rp) - 1, (cols - 1) // w + 1
+        mask = np.asarray(mask)
+        if mask.shape != (block_rows, block_cols):
+            raise ValueError("mask must have the shape (block_rows, block_cols) = (%d, %d), not %r" % (block_rows, block_cols, tuple(mask.shape)))
+        stored = mask != 0
+        nzcount = stored.sum(axis=1).astype(np.int64)
+        jab = np.nonzero(stored)[1].astype(np.int64)                   # (row by row, ascending inside a row)
+        nztot = int((np.diff(rp) * nzcount).sum()) * w
+        return cls.from_arrays(rows, cols, w, rp, nzcount, jab, np.zeros(nztot, np.float32))
+
     def _host_struct(self):
         h = _lib.VbsHost()
         h.rows, h.cols, h.block_rows, h.block_cols = self.rows, self.cols, self.block_rows, self.block_cols
