@@ -1031,6 +1031,15 @@ int sparta_vbs_colres_info(const sparta_vbs_t* A, int64_t* info_out);
  * to check the builder with.  Not a product path (and not a fallback: sparta_vbs_spmm never calls it). */
 int sparta_colres_host_check(int64_t rows, int64_t cols, const int64_t* rowptr, const int32_t* colidx, const float* vals, const int64_t* crow, const float* x,
                              float* y, int64_t* info_out);
+/* HOST-side walk of the sparse-row device form (what the sparse-row kernels read: the list of short rows, the long rows' records and segments, the column windows and the
+ * eight per-XCD streams) of a CSR matrix for one column x of B; rows, crow and y as for sparta_colres_host_check.  The short rows come from the list, a long row from its record:
+ * its segments in row order, one partial per segment, the partials added in that order.  SPARTA_ERR_INVALID with a message if the form is broken: a nonzero covered not exactly
+ * once, a row's segments not contiguous and in order, the partials' places not a permutation, the segments not in window order (one list), or the streams not monotone, a window
+ * split across streams, a stream's windows not in column order (XCD order).  The SPARTA_SPARSE_SEG / SPARTA_SP_* switches apply as at creation.
+ * info_out (12 words): [0] sparse rows [1] short rows [2] long rows [3] segments [4] window width in columns (0: no windows) [5] streams that hold segments (0: one list)
+ * [6] base segment length [7] longest short row [8] nonzeros a segment holds before a window boundary ends it.  For the CPU suite; not a product path. */
+int sparta_sparse_rows_host_check(int64_t rows, int64_t cols, const int64_t* rowptr, const int32_t* colidx, const float* vals, const int64_t* crow, const float* x,
+                                  float* y, int64_t* info_out);
 
 /* the column-compacted ("union-pattern") tiles of a handle made by sparta_vbs_create_from_csr (fp32, and since the round's second half fp16 / bf16 storage: the same tiles through the 16-bit matrix instruction).  They replace what the reference's builder stores for a cluster at
  * SMALL block widths -- VBR::fill_from_CSR_inplace flags, per block-row, exactly the column blocks its rows touch and stores them back to back

@@ -18,7 +18,7 @@ from ._lib import (SpartaError, LIB_PATH, F32, F16, BF16, COL_MAJOR, ROW_MAJOR, 
                    FMT_EL, FMT_MTX, IO_COMPAT, IO_STRICT)
 from .host import (CSR, BlockingEngine, VBR, get_permutation, get_partition, get_fixed_size_grouping,  # noqa: F401
                    row_distance, merge_rows, BLOCKING_ALGOS, save_grouping, read_grouping_file, blocking_csv_row,
-                   save_blocking_data, CSV_COLUMNS, STEP_DTYPE, live_forward_compact, a8_quantize_group)
+                   save_blocking_data, CSV_COLUMNS, STEP_DTYPE, live_forward_compact, a8_quantize_group, sparse_rows_host_check)
 from .device import (DeviceVBS, vbs_multiply, device_count, repattern, repattern_prepare, repattern_commit,  # noqa: F401
                      dense_block_ssq, sparsify)
 from . import gen, dist, autograd, optim, gradctl, prune, epilogue  # noqa: F401

@@ -118,22 +118,280 @@ void destroy_impl(sparta_vbs* v) {
     delete v;
 }
 
+// ---- the sparse-row leg of a handle on the host: no builder below makes a HIP call ----------------------------------------------------------------------
+// 16-bit handles: the values the kernels multiply are the ROUNDED ones (a value that rounds to zero is a zero)
+float stored_as(float x, int32_t dtype) {
+    if (dtype == SPARTA_F32) return x;
+    const bool bf16h = dtype == SPARTA_BF16;
+    const uint16_t u = to_h16(x, bf16h);
+    if (bf16h) { const uint32_t v32 = (uint32_t)u << 16; float f; std::memcpy(&f, &v32, 4); return f; }
+    _Float16 hh; std::memcpy(&hh, &u, 2); return (float)hh;
+}
+
+// ---- sparse-row path: which block-rows are better served as rows of (column, value) --------------------------------
+// An MFMA step (one <=32-row tile x 32 k x 128 columns) takes the time of ~12 nonzeros on the sparse-row path (2.1 ns per
+// step across the 512 workers vs 512 B of B per nonzero and 128-column slab at ~3 TB/s): a block-row whose blocks hold
+// fewer than SPARTA_SPARSE_K (default 24) nonzeros per step goes there (measured break-even, scripts/sparse_k_sweep.py:
+// ~60 nonzeros per step while B fits the L2s, ~15 when its rows come from HBM).  SPARTA_SPARSE_K=0 switches the path off.
+void collect_sparse_rows_from_ext(const sparta::HybridSparse& ext_, int64_t cols, int32_t dtype, SparseRowsHost& S) {
+    const sparta::HybridSparse* ext = &ext_;
+    std::vector<uint8_t>& sparse_flag = S.flag;
+    std::vector<int64_t>& sp_rowptr = S.rowptr;
+    std::vector<int32_t>&sp_col = S.col, &sp_crow = S.crow;
+    std::vector<float>& sp_val = S.val;
+    auto stored = [&](float x) -> float { return stored_as(x, dtype); };
+    // flag 1: the block-row has no tile at all (skipped by the MFMA plans); flag 2 (mixed): its well-filled blocks are tiles like any other
+    // (nzcount / jab hold only those), the nonzeros of its other blocks are sparse rows that ADD to C (bit 31 of their crow entry)
+    sparse_flag.assign(ext->flag.size(), 0);
+    bool any = false;
+    // (flag 3: column-compacted tiles, UnionPlanHost -- no w-wide block either; their thinly used columns are sparse rows that add, as for flag 2)
+    for (size_t q = 0; q < ext->flag.size(); q++) { sparse_flag[q] = ext->flag[q] == 1 || ext->flag[q] == 3; any = any || sparse_flag[q]; }
+    if (!any) sparse_flag.clear();
+    // the entries that survive the storage type (a value that rounds to zero is a zero) and lie inside the matrix: counted, then
+    // copied, on all host threads (10^8..10^9 entries on the power-law configs)
+    const int64_t n_ext = (int64_t)ext->crow.size();
+    std::vector<int64_t> keep((size_t)n_ext + 1, 0);
+    sparta::parallel_for_dynamic(n_ext, 2048, [&](int64_t lo, int64_t hi, int) {
+        for (int64_t t = lo; t < hi; t++) {
+            int64_t c = 0;
+            for (int64_t k = ext->rowptr[(size_t)t]; k < ext->rowptr[(size_t)t + 1]; k++)
+                c += stored(ext->val[(size_t)k]) != 0.0f && ext->col[(size_t)k] < cols;
+            keep[(size_t)t + 1] = c;
+        }
+    });
+    for (int64_t t = 0; t < n_ext; t++) keep[(size_t)t + 1] += keep[(size_t)t];
+    sp_rowptr.swap(keep);
+    sp_col.resize((size_t)sp_rowptr.back()); sp_val.resize((size_t)sp_rowptr.back()); sp_crow.resize((size_t)n_ext);
+    sparta::parallel_for_dynamic(n_ext, 2048, [&](int64_t lo, int64_t hi, int) {
+        for (int64_t t = lo; t < hi; t++) {
+            int64_t o = sp_rowptr[(size_t)t];
+            for (int64_t k = ext->rowptr[(size_t)t]; k < ext->rowptr[(size_t)t + 1]; k++) {
+                const float a = stored(ext->val[(size_t)k]);
+                if (a != 0.0f && ext->col[(size_t)k] < cols) { sp_col[(size_t)o] = ext->col[(size_t)k]; sp_val[(size_t)o] = a; o++; }
+            }
+            sp_crow[(size_t)t] = ext->crow[(size_t)t] | ((size_t)t < ext->row_add.size() && ext->row_add[(size_t)t] ? (int32_t)0x80000000 : 0);
+        }
+    });
+}
+
+void collect_sparse_rows_from_blocks(const StreamPlanIn& in, bool updatable, SparseRowsHost& S) {
+    const int64_t cols = in.cols, w = in.w, br0 = in.br0, br1 = in.br1, jab_lo = in.jab_lo, mab_lo = in.mab_lo;
+    const int64_t* row_part = in.row_part; const int64_t* nzcount = in.nzcount; const int64_t* jab = in.jab; const float* mab = in.mab;
+    const bool h16 = in.dtype != SPARTA_F32;
+    std::vector<uint8_t>& sparse_flag = S.flag;
+    std::vector<int64_t>& sp_rowptr = S.rowptr;
+    std::vector<int32_t>&sp_col = S.col, &sp_crow = S.crow;
+    std::vector<float>& sp_val = S.val;
+    auto stored = [&](float x) -> float { return stored_as(x, in.dtype); };
+    double K = 24.0;
+    if (const char* e = std::getenv("SPARTA_SPARSE_K")) K = atof(e);
+    if (updatable) K = 0.0;          // (the sparse-row image holds only what was non-zero at creation: sparta_vbs_set_values could not fill it)
+    if (K > 0.0) {
+        sparse_flag.assign((size_t)(br1 - br0), 0);
+        int64_t jo2 = 0, mo2 = 0, n_flagged = 0;
+        const int64_t row0 = row_part[br0];
+        std::vector<int64_t> cnt;
+        sp_rowptr.push_back(0);
+        // pass 1: which block-rows qualify and what they would cost as tiles (a handful stays with the tiles: see vbs_build_hybrid)
+        std::vector<uint8_t> qualifies((size_t)(br1 - br0), 0);
+        {
+            double steps_saved = 0.0;
+            int64_t mo1 = 0;
+            for (int64_t ib = br0; ib < br1; ib++) {
+                const int64_t h = row_part[ib + 1] - row_part[ib], nb = nzcount[ib];
+                const float* blk = mab + mab_lo + mo1;
+                const int64_t n_el = nb * h * w;
+                int64_t nnz = 0;
+                for (int64_t q = 0; q < n_el; q++) nnz += stored(blk[q]) != 0.0f;
+                const int64_t kdep = h16 && w % 64 == 0 ? 64 : 32;                 // k depth of a step of the kernels this handle would use
+                const double steps_br = (double)nb * (double)((w + kdep - 1) / kdep) * (double)((h + 31) / 32);
+                if (h > 0 && nb > 0 && (double)nnz < K * steps_br) { qualifies[(size_t)(ib - br0)] = 1; steps_saved += steps_br; }
+                mo1 += n_el;
+            }
+            if (steps_saved < (double)sparta::sparse_min_steps()) std::fill(qualifies.begin(), qualifies.end(), 0);
+        }
+        for (int64_t ib = br0; ib < br1; ib++) {
+            const int64_t h = row_part[ib + 1] - row_part[ib], nb = nzcount[ib];
+            const float* blk = mab + mab_lo + mo2;
+            const int64_t n_el = nb * h * w;
+            if (qualifies[(size_t)(ib - br0)] && (int64_t)sp_col.size() + n_el < ((int64_t)1 << 40)) {
+                sparse_flag[(size_t)(ib - br0)] = 1;
+                n_flagged++;
+                // rows of this block-row: (column, value) in the reference's order (blocks ascending, k ascending: vbr.cpp:358-363)
+                cnt.assign((size_t)h, 0);
+                for (int64_t b = 0; b < nb; b++)
+                    for (int64_t k = 0; k < w; k++)
+                        for (int64_t i = 0; i < h; i++) cnt[(size_t)i] += (stored(blk[(b * w + k) * h + i]) != 0.0f) && jab[jab_lo + jo2 + b] * w + k < cols;
+                const size_t base_row = sp_crow.size();
+                for (int64_t i = 0; i < h; i++) {
+                    sp_crow.push_back((int32_t)(row_part[ib] - row0 + i));
+                    sp_rowptr.push_back(sp_rowptr.back() + cnt[(size_t)i]);
+                }
+                sp_col.resize((size_t)sp_rowptr.back());
+                sp_val.resize((size_t)sp_rowptr.back());
+                for (int64_t i = 0; i < h; i++) cnt[(size_t)i] = sp_rowptr[base_row + (size_t)i];
+                for (int64_t b = 0; b < nb; b++) {
+                    const int64_t c0 = jab[jab_lo + jo2 + b] * w;
+                    for (int64_t k = 0; k < w && c0 + k < cols; k++)
+                        for (int64_t i = 0; i < h; i++) {
+                            const float a = stored(blk[(b * w + k) * h + i]);
+                            if (a != 0.0f) { sp_col[(size_t)cnt[(size_t)i]] = (int32_t)(c0 + k); sp_val[(size_t)cnt[(size_t)i]++] = a; }
+                        }
+                }
+            }
+            jo2 += nb;
+            mo2 += n_el;
+        }
+        if (n_flagged == 0) sparse_flag.clear();
+    }
+}
+
+int order_sparse_rows(SparseRowsHost& S, int64_t cols) {
+    std::vector<int64_t>& sp_rowptr = S.rowptr;
+    std::vector<int32_t>&sp_col = S.col, &sp_crow = S.crow, &sp_list = S.list, &sp_stream_begin = S.stream_begin;
+    std::vector<SpSegRec>& sp_segs = S.segs;
+    std::vector<SpLongRec>& sp_long = S.longs;
+    // a wave keeps SP_BATCH (16) rows of B in flight: a row of n nonzeros takes ~n / 16 memory latencies whatever else the GPU is doing, so rows
+    // longer than kSpLong are cut into kSpSeg-nonzero segments that run on different waves (SPARTA_SPARSE_SEG overrides kSpSeg)
+    // The segment length follows the size of the sparse part (decided below, once it is known): short segments keep a small
+    // problem parallel (R-MAT 2^16: 128 -> 148 us, 512 -> 187 us), long ones save partial rows on a large one (2^20: 3.99 vs 3.75 ms).
+    int64_t kSpSeg = 0;
+    if (const char* e = std::getenv("SPARTA_SPARSE_SEG")) kSpSeg = std::max(8, atoi(e));
+    // short rows: one wave each; rows with more than kSpLong nonzeros (hubs): segments of kSpSeg, one wave each + a reduction
+    if (kSpSeg == 0) {
+        const int64_t total = sp_rowptr.empty() ? 0 : sp_rowptr.back();
+        // (below 1 M nonzeros the GPU has more idle waves than rows: 32-nonzero segments -- ca-HepPh: rows of up to 256 nonzeros on one wave each took
+        // 57 us for 115 k nonzeros, 16 batches of gathers one after the other)
+        kSpSeg = total < ((int64_t)1 << 20) ? 32 : (total < ((int64_t)4 << 20) ? 128 : (total < ((int64_t)16 << 20) ? 256 : 512));
+    }
+    int64_t kSpLong = 2 * kSpSeg;
+    // Column windows.  The rows of B a launch gathers at any one time should lie close together: on a power-law matrix with millions of columns the nonzeros of the
+    // rows in flight are spread over all of B (GBs), every gather is an HBM access (measured with FETCH_SIZE: 327 of 336 GB gathered came from HBM on a part of
+    // the 8 M-row R-MAT) and the kernels run at the random-row rate of HBM.  So the columns are cut into windows of win_w columns (16-32 MB of B at N = 256..512
+    // in 16 bits), a row of more than 128 nonzeros is cut into segments that also end where its columns cross into another window (once a segment holds sp_minseg
+    // nonzeros), and the segments are PROCESSED window by window -- all rows' segments of window 0, then of window 1, ... (workgroups start in the order of the
+    // list).  What is in flight then gathers from one window, which the Infinity Cache and the L2s hold: the same part 62.4 -> 35.1 ms, R-MAT 2^20 at 0.1 %
+    // (B = 512, bf16) 11.6 -> 8.1 ms per part.  A row's partial rows are still added in segment order (the sum does not depend on the processing order).
+    // Width / segment minimum 65536 / 64 -> 32768 / 128 (the defaults): another 3 % on both configs (34.8 -> 33.9 ms, 8.05 -> 7.80).
+    // SPARTA_SP_WINDOW_COLS: unset = automatic (on from 262144 columns and 4 M nonzeros on this path), 0 = off, > 0 = the window width in columns;
+    // SPARTA_SP_LONG / SPARTA_SP_MINSEG: the row length above which a row is cut / the nonzeros a segment holds before a window boundary ends it.
+    const int64_t sp_total = sp_rowptr.empty() ? 0 : sp_rowptr.back();
+    // Round 4: the windows are dealt to eight streams, one per XCD (below: every L2 then holds its OWN window instead of a copy of everybody's), and are 8192 columns wide
+    // (2 MB of B per L2 at the 256-byte row chunks the large parts run with).  Parts of configs[4] / configs[3] at 1 %, sparse-row kernels, ms: one list of 32768-column
+    // windows 25.8 / 31.5 / 10.7 -> eight streams of 8192-column windows 24.5 / 28.9 / 10.3 (4096 .. 32768 columns: within 1 %).  SPARTA_SP_XCD=0: one list, 32768 columns.
+    bool sp_xcd = true;
+    if (const char* e = std::getenv("SPARTA_SP_XCD")) sp_xcd = atoi(e) != 0;
+    int64_t win_w = (cols >= 4 * 65536 && sp_total >= ((int64_t)4 << 20)) ? (sp_xcd ? 8192 : 32768) : 0, sp_minseg = 128;
+    if (const char* e = std::getenv("SPARTA_SP_WINDOW_COLS")) win_w = std::max(0, atoi(e));
+    if (win_w > 0) kSpLong = 128;
+    if (const char* e = std::getenv("SPARTA_SP_LONG")) kSpLong = std::max(8, atoi(e));
+    if (const char* e = std::getenv("SPARTA_SP_MINSEG")) sp_minseg = std::max(1, atoi(e));
+    // the segments of row t (appended to out, or only counted when out is null)
+    auto cut_row = [&](size_t t, std::vector<SpSegRec>* out) -> int32_t {
+        const int64_t p0 = sp_rowptr[t], n = sp_rowptr[t + 1] - p0;
+        int32_t n_seg = 0;
+        if (win_w > 0) {
+            const int64_t L = std::max<int64_t>(kSpSeg, 512);
+            int64_t o = 0;
+            while (o < n) {
+                // the segment [o, e): up to L nonzeros, ending early at the first window boundary behind its first sp_minseg nonzeros
+                int64_t e = std::min(n, o + L);
+                if (e - o > sp_minseg) {
+                    const int64_t wend = ((int64_t)sp_col[(size_t)(p0 + o + sp_minseg - 1)] / win_w + 1) * win_w;      // end of the window of the sp_minseg-th nonzero
+                    const int32_t* b = sp_col.data() + p0 + o + sp_minseg;
+                    const int32_t* bend = sp_col.data() + p0 + e;
+                    const int32_t* f = std::lower_bound(b, bend, (int32_t)std::min<int64_t>(wend, INT32_MAX));
+                    e = o + sp_minseg + (f - b);
+                }
+                if (out) out->push_back(SpSegRec{p0 + o, (int32_t)(e - o), 0});
+                n_seg++;
+                o = e;
+            }
+            return n_seg;
+        }
+        // a hub row's segments run in parallel, its partial rows are added one after the other: with segments of L nonzeros the chain is L / 16 gather
+        // batches + n / L additions -- shortest near L = sqrt(1.6 n) (a batch ~ 10 additions), never below the size-dependent base, never above 512
+        // (ia-wikiquote, 239 k nonzeros with rows of 10^4: 32-nonzero segments everywhere took 271 us, mostly the reduction of its hub rows)
+        int64_t L = ((int64_t)std::sqrt(1.6 * (double)n) + 15) / 16 * 16;
+        L = std::max(kSpSeg, std::min<int64_t>(512, L));
+        for (int64_t o = 0; o < n; o += L) { if (out) out->push_back(SpSegRec{p0 + o, (int32_t)std::min<int64_t>(L, n - o), 0}); n_seg++; }
+        return n_seg;
+    };
+    {
+        // rows in order; the segments of the long ones are cut on all threads (chunks of rows, concatenated in row order)
+        const int64_t n_rows_sp = (int64_t)sp_crow.size();
+        const int nt = sparta::host_threads();
+        const int64_t chunk = std::max<int64_t>(1024, (n_rows_sp + 4 * nt - 1) / (4 * std::max(nt, 1)));
+        const int64_t n_chunks = (n_rows_sp + chunk - 1) / std::max<int64_t>(chunk, 1);
+        std::vector<std::vector<SpSegRec>> segs_of((size_t)n_chunks);
+        std::vector<std::vector<SpLongRec>> long_of((size_t)n_chunks);
+        std::vector<std::vector<int32_t>> short_of((size_t)n_chunks);
+        sparta::parallel_for_dynamic(n_chunks, 1, [&](int64_t lo, int64_t hi, int) {
+            for (int64_t c = lo; c < hi; c++)
+                for (int64_t t = c * chunk; t < std::min(n_rows_sp, (c + 1) * chunk); t++) {
+                    if (sp_rowptr[(size_t)t + 1] - sp_rowptr[(size_t)t] <= kSpLong) { short_of[(size_t)c].push_back((int32_t)t); continue; }
+                    SpLongRec lr{(int32_t)t, (int32_t)segs_of[(size_t)c].size(), 0, 0};      // seg_begin: within the chunk for now
+                    lr.n_seg = cut_row((size_t)t, &segs_of[(size_t)c]);
+                    long_of[(size_t)c].push_back(lr);
+                }
+        });
+        for (int64_t c = 0; c < n_chunks; c++) {
+            const int32_t base = (int32_t)sp_segs.size();
+            if ((int64_t)sp_segs.size() + (int64_t)segs_of[(size_t)c].size() > INT32_MAX)
+                return sparta::fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_create: too many sparse-row segments for 32-bit indexing");
+            sp_list.insert(sp_list.end(), short_of[(size_t)c].begin(), short_of[(size_t)c].end());
+            sp_segs.insert(sp_segs.end(), segs_of[(size_t)c].begin(), segs_of[(size_t)c].end());
+            for (SpLongRec lr : long_of[(size_t)c]) { lr.seg_begin += base; sp_long.push_back(lr); }
+        }
+    }
+    // a segment's partial row lives at its index in row order (pad); the order of the list is the order the waves take them in: window by window
+    // (a stable counting sort on the window of the segment's first column)
+    for (size_t i = 0; i < sp_segs.size(); i++) sp_segs[i].pad = (int32_t)i;
+    if (win_w > 0 && !sp_segs.empty()) {
+        const int64_t n_win = (cols + win_w - 1) / win_w;
+        std::vector<int64_t> start((size_t)n_win + 1, 0);
+        for (const SpSegRec& g : sp_segs) start[(size_t)(sp_col[(size_t)g.p0] / win_w) + 1]++;
+        for (int64_t k = 0; k < n_win; k++) start[(size_t)k + 1] += start[(size_t)k];
+        std::vector<SpSegRec> sorted(sp_segs.size());
+        for (const SpSegRec& g : sp_segs) sorted[(size_t)start[(size_t)(sp_col[(size_t)g.p0] / win_w)]++] = g;
+        sp_segs.swap(sorted);
+        // XCD-affine order (k_sparse.hip: sparse_segments_xcd_kernel): the windows are dealt to eight streams -- heaviest first, each to the stream with the fewest
+        // nonzeros so far -- and the list becomes stream 0's windows in column order, then stream 1's, ...; workgroup b takes from stream b % 8 = its XCD.
+        if (sp_xcd && sp_segs.size() >= 64) {
+            std::vector<int64_t> w_nnz((size_t)n_win, 0), w_begin((size_t)n_win + 1, 0);
+            for (const SpSegRec& g : sp_segs) { const size_t k = (size_t)(sp_col[(size_t)g.p0] / win_w); w_nnz[k] += g.cnt; w_begin[k + 1]++; }
+            for (int64_t k = 0; k < n_win; k++) w_begin[(size_t)k + 1] += w_begin[(size_t)k];
+            std::vector<int64_t> order((size_t)n_win);
+            for (int64_t k = 0; k < n_win; k++) order[(size_t)k] = k;
+            std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return w_nnz[(size_t)a] > w_nnz[(size_t)b]; });
+            int64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            std::vector<int8_t> stream_of((size_t)n_win, 0);
+            for (int64_t k : order) {
+                int best = 0;
+                for (int x = 1; x < 8; x++) if (load[x] < load[best]) best = x;
+                stream_of[(size_t)k] = (int8_t)best;
+                load[best] += w_nnz[(size_t)k] + 16 * (w_begin[(size_t)k + 1] - w_begin[(size_t)k]);       // (a segment costs about a batch whatever it holds)
+            }
+            std::vector<SpSegRec> streamed;
+            streamed.reserve(sp_segs.size());
+            sp_stream_begin.assign(9, 0);
+            for (int x = 0; x < 8; x++) {
+                sp_stream_begin[(size_t)x] = (int32_t)streamed.size();
+                for (int64_t k = 0; k < n_win; k++)
+                    if (stream_of[(size_t)k] == x) streamed.insert(streamed.end(), sp_segs.begin() + w_begin[(size_t)k], sp_segs.begin() + w_begin[(size_t)k + 1]);
+            }
+            sp_stream_begin[8] = (int32_t)streamed.size();
+            sp_segs.swap(streamed);
+        }
+    }
+    S.seg = kSpSeg; S.long_cut = kSpLong; S.minseg = sp_minseg; S.win_w = win_w;
+    return SPARTA_OK;
+}
+
 // ---- resident-column product (k_colres.hip): A as length-sorted slots, 64 to a slice -----------------------------------------------------------
 // Only for handles whose rows of C are ALL sparse rows (nothing for a tile launch to store first) and small enough that a column of B (and of C, with the
 // extra cells of the long rows) fits LDS.  SPARTA_COLRES=0: never built.  SPARTA_COLRES_LMAX: longest slot (default max(32, nnz / 2048): at 1024 lanes per
 // workgroup a slot of twice the average load per lane is not the critical path).
-constexpr int64_t kColresCells = 160 * 1024 / 4;                  // floats of LDS a workgroup may hold
-struct ColresHost {
-    std::vector<uint16_t> col;                                    // per batch of 4 steps and lane: four columns (relative to their K range) ...
-    std::vector<float> val;                                       // ... and four values (empty: every stored value is 1.0f -- a unit image, the reference's -P 1)
-    std::vector<ColresPartDev> parts;
-    std::vector<int32_t> meta, dest;                              // per part: see ColresPartDev
-    std::vector<uint8_t> mode;                                    // per row of C (padded to 4): 0 not this kernel's, 1 store, 2 add
-    std::vector<ColresLong> longs;
-    std::vector<int32_t> krange;                                  // [n_ranges + 1]
-    int32_t max_slices = 0, max_cells = 0, lmax = 0;              // slices of the part with most; cells a column set needs in LDS (largest range of B + its zero cell / largest staging image)
-    int64_t entries = 0;
-};
 // force_parts > 1: that many parts of the rows of C (about equal staging images), one K range -- the image for products of few column sets
 bool build_colres(int64_t rows, int64_t cols, const std::vector<int64_t>& rowptr, const std::vector<int32_t>& col, const std::vector<float>& val,
                   const std::vector<int32_t>& crow, ColresHost& H, int force_parts = 0) {
@@ -302,6 +560,16 @@ bool build_colres(int64_t rows, int64_t cols, const std::vector<int64_t>& rowptr
     H.lmax = (int32_t)lmax;
     return true;
 }
+
+void build_colres_images(int64_t rows, int64_t cols, const SparseRowsHost& S, ColresImages& I) {
+    I.has_main = build_colres(rows, cols, S.rowptr, S.col, S.val, S.crow, I.main);
+    if (!I.has_main) return;
+    // the four-part image for products of few column sets (SPARTA_COLRES_SMALL=0: not built)
+    const char* es = std::getenv("SPARTA_COLRES_SMALL");
+    if (I.main.parts.size() == 1 && I.main.krange.size() == 2 && rows >= 2048 && !(es && atoi(es) == 0))
+        I.has_small = build_colres(rows, cols, S.rowptr, S.col, S.val, S.crow, I.small, 4) && I.small.val.empty() == I.main.val.empty();
+}
+
 // columns of B per workgroup: as many as LDS holds next to each other (columns of B first, the staging image of C after them, in the same cells)
 // ... as many as fit: with one workgroup per CU the phases (columns of B in, stream of A, columns of C out) take the sum of their times, and the stream of A costs the same
 // per workgroup whatever NC (measured): fewer passes win.  SPARTA_COLRES_NC caps it (read per call: developer A/B, tests).
@@ -330,325 +598,47 @@ int colres_columns(const sparta_vbs_t* A, int n_cols) {
     return nc >= 1 && A->cr_slices <= colres_max_slices(nc) ? nc : 0;
 }
 
-}  // namespace
+// ---- creation: per family a host builder (no HIP call; the stream and union plans are in vbs_plan.cpp / vbs_union.cpp) and an upload that copies its arrays to the device and fills in the handle's counters --------------------------------------
+// a HIP call of an upload: out of device memory is SPARTA_ERR_ALLOC, anything else SPARTA_ERR_HIP (`fail` is sparta::fail in the function that uses it)
+#define CREATE_TRY(expr)                                                                                     \
+    do {                                                                                                     \
+        hipError_t e_ = (expr);                                                                              \
+        if (e_ != hipSuccess) {                                                                              \
+            std::string m_ = std::string(#expr) + ": " + hipGetErrorString(e_);                              \
+            return fail(e_ == hipErrorOutOfMemory ? SPARTA_ERR_ALLOC : SPARTA_ERR_HIP, m_);                  \
+        }                                                                                                    \
+    } while (0)
 
-extern "C" {
+int no_device() { return sparta::fail(SPARTA_ERR_NO_DEVICE, "sparta_vbs_create: no HIP device visible (this path has no CPU fallback)"); }
 
-int sparta_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
+// compute units of the device the plans are cut for.  Asked once per creation, by device index (no device has to be current): build_stream_plans wants the
+// count whenever w is a multiple of 32 and build_union_plan for every union plan, which leaves few handles that would not need it
+int device_cu_count(int32_t device) {
+    hipDeviceProp_t pr;
+    return hipGetDeviceProperties(&pr, device) == hipSuccess && pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
 }
 
-// `ext` (sparta_vbs_create_from_csr): the sparse-row part of the matrix decided and collected by the hybrid host builder.  Fully sparse
-// block-rows (ext->flag 1) have nzcount = 0 in the arrays given here and get neither tiles nor zero-fill records; MIXED block-rows (flag 2)
-// keep their well-filled blocks in nzcount / jab / mab as tiles like any other, and the nonzeros of their other blocks are sparse rows that
-// add to C behind the tile launches (see the ordering note at the sparse-row launch in spmm_impl).
-static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t block_rows, int64_t w, const int64_t* row_part,
-                       const int64_t* nzcount, const int64_t* jab, const float* mab, int64_t br0, int64_t br1, int32_t dtype,
-                       int32_t device, const sparta::HybridSparse* ext, int32_t flags = 0) {
+// the handle's block columns in 32 bits, every one checked against the matrix
+int narrow_jab(const int64_t* jab, int64_t jab_lo, int64_t nblocks, int64_t block_cols, std::vector<int32_t>& jab32) {
     using sparta::fail;
-    if (!out) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: out is NULL");
-    if (flags & ~(SPARTA_CREATE_UPDATABLE | SPARTA_CREATE_TRANSPOSE)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create_range_ex: unknown bits in flags");
-    const bool updatable = (flags & SPARTA_CREATE_UPDATABLE) != 0;        // every block-row stays in the dense-block images; the slices' sources are kept
-    const bool transposable = (flags & SPARTA_CREATE_TRANSPOSE) != 0;     // sparta_vbs_spmm_t: block-column index + an image it can read (changes nothing of the forward product)
-    if (transposable && ext) return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_create: SPARTA_CREATE_TRANSPOSE needs the dense blocks of every block-row");
-    *out = nullptr;
-    sparta::BuildTrace trace("vbs_create");
-    if (rows <= 0 || cols <= 0 || block_rows <= 0 || w <= 0 || !row_part || !nzcount)
-        return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: bad dimensions or NULL index array");
-    if (br0 < 0 || br1 > block_rows || br0 >= br1) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: bad block-row range");
-    if (dtype != SPARTA_F32 && dtype != SPARTA_F16 && dtype != SPARTA_BF16) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: bad dtype");
-    const bool h16 = dtype != SPARTA_F32;
-    if (h16 && w % 32 != 0)
-        return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_create: SPARTA_F16 / SPARTA_BF16 need block_col_size % 32 == 0 (only the stream kernels have a 16-bit form)");
-    if (rows > INT32_MAX || w > (1 << 20)) return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_create: rows >= 2^31 or w > 2^20");
-    const int64_t block_cols = (cols - 1) / w + 1;
-
-    // validate the partition and locate the range inside jab / mab
-    if (row_part[0] != 0 || row_part[block_rows] != rows) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: row_part must span [0, rows]");
-    int64_t jab_lo = 0, mab_lo = 0, jab_hi = 0, mab_hi = 0, jo = 0, mo = 0;
-    for (int64_t ib = 0; ib < block_rows; ib++) {
-        const int64_t h = row_part[ib + 1] - row_part[ib];
-        if (h < 0 || nzcount[ib] < 0 || nzcount[ib] > block_cols) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: invalid row_part / nzcount");
-        if (h > INT32_MAX / 2 || nzcount[ib] > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_create: block-row too large");
-        if (ib == br0) { jab_lo = jo; mab_lo = mo; }
-        jo += nzcount[ib];
-        mo += nzcount[ib] * h * w;
-        if (ib == br1 - 1) { jab_hi = jo; mab_hi = mo; }
-    }
-    const int64_t nblocks = jab_hi - jab_lo, nztot = mab_hi - mab_lo;
-    if (nblocks > 0 && (!jab || !mab)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: jab / mab is NULL");
-
-    int ndev = sparta_device_count();
-    const bool plan_debug = std::getenv("SPARTA_PLAN_DEBUG") != nullptr && ndev <= 0;   // developer aid: print the plan statistics on a host without a GPU, then fail as usual
-    if (ndev <= 0 && !plan_debug) return fail(SPARTA_ERR_NO_DEVICE, "sparta_vbs_create: no HIP device visible (this path has no CPU fallback)");
-    if (!plan_debug && (device < 0 || device >= ndev)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: device index out of range");
-
-    // ---- sparse-row path: which block-rows are better served as rows of (column, value) --------------------------------
-    // An MFMA step (one <=32-row tile x 32 k x 128 columns) takes the time of ~12 nonzeros on the sparse-row path (2.1 ns per
-    // step across the 512 workers vs 512 B of B per nonzero and 128-column slab at ~3 TB/s): a block-row whose blocks hold
-    // fewer than SPARTA_SPARSE_K (default 24) nonzeros per step goes there (measured break-even, scripts/sparse_k_sweep.py:
-    // ~60 nonzeros per step while B fits the L2s, ~15 when its rows come from HBM).  SPARTA_SPARSE_K=0 switches the path off.
-    std::vector<uint8_t> sparse_flag;
-    std::vector<int64_t> sp_rowptr;
-    std::vector<int32_t> sp_col, sp_crow, sp_list;
-    std::vector<float> sp_val;
-    std::vector<SpSegRec> sp_segs;
-    std::vector<SpLongRec> sp_long;
-    // a wave keeps SP_BATCH (16) rows of B in flight: a row of n nonzeros takes ~n / 16 memory latencies whatever else the GPU is doing, so rows
-    // longer than kSpLong are cut into kSpSeg-nonzero segments that run on different waves (SPARTA_SPARSE_SEG overrides kSpSeg)
-    // The segment length follows the size of the sparse part (decided below, once it is known): short segments keep a small
-    // problem parallel (R-MAT 2^16: 128 -> 148 us, 512 -> 187 us), long ones save partial rows on a large one (2^20: 3.99 vs 3.75 ms).
-    int64_t kSpSeg = 0;
-    if (const char* e = std::getenv("SPARTA_SPARSE_SEG")) kSpSeg = std::max(8, atoi(e));
-    int64_t n_sp_short = 0, n_sp_long = 0;
-    // 16-bit handles: the values the kernels multiply are the ROUNDED ones (a value that rounds to zero is a zero)
-    const bool bf16h = dtype == SPARTA_BF16;
-    auto stored = [&](float x) -> float {
-        if (!h16) return x;
-        const uint16_t u = to_h16(x, bf16h);
-        if (bf16h) { const uint32_t v32 = (uint32_t)u << 16; float f; std::memcpy(&f, &v32, 4); return f; }
-        _Float16 hh; std::memcpy(&hh, &u, 2); return (float)hh;
-    };
-    if (ext) {
-        // flag 1: the block-row has no tile at all (skipped by the MFMA plans); flag 2 (mixed): its well-filled blocks are tiles like any other
-        // (nzcount / jab hold only those), the nonzeros of its other blocks are sparse rows that ADD to C (bit 31 of their crow entry)
-        sparse_flag.assign(ext->flag.size(), 0);
-        bool any = false;
-        // (flag 3: column-compacted tiles, UnionPlanHost -- no w-wide block either; their thinly used columns are sparse rows that add, as for flag 2)
-        for (size_t q = 0; q < ext->flag.size(); q++) { sparse_flag[q] = ext->flag[q] == 1 || ext->flag[q] == 3; any = any || sparse_flag[q]; }
-        if (!any) sparse_flag.clear();
-        // the entries that survive the storage type (a value that rounds to zero is a zero) and lie inside the matrix: counted, then
-        // copied, on all host threads (10^8..10^9 entries on the power-law configs)
-        const int64_t n_ext = (int64_t)ext->crow.size();
-        std::vector<int64_t> keep((size_t)n_ext + 1, 0);
-        sparta::parallel_for_dynamic(n_ext, 2048, [&](int64_t lo, int64_t hi, int) {
-            for (int64_t t = lo; t < hi; t++) {
-                int64_t c = 0;
-                for (int64_t k = ext->rowptr[(size_t)t]; k < ext->rowptr[(size_t)t + 1]; k++)
-                    c += stored(ext->val[(size_t)k]) != 0.0f && ext->col[(size_t)k] < cols;
-                keep[(size_t)t + 1] = c;
-            }
-        });
-        for (int64_t t = 0; t < n_ext; t++) keep[(size_t)t + 1] += keep[(size_t)t];
-        sp_rowptr.swap(keep);
-        sp_col.resize((size_t)sp_rowptr.back()); sp_val.resize((size_t)sp_rowptr.back()); sp_crow.resize((size_t)n_ext);
-        sparta::parallel_for_dynamic(n_ext, 2048, [&](int64_t lo, int64_t hi, int) {
-            for (int64_t t = lo; t < hi; t++) {
-                int64_t o = sp_rowptr[(size_t)t];
-                for (int64_t k = ext->rowptr[(size_t)t]; k < ext->rowptr[(size_t)t + 1]; k++) {
-                    const float a = stored(ext->val[(size_t)k]);
-                    if (a != 0.0f && ext->col[(size_t)k] < cols) { sp_col[(size_t)o] = ext->col[(size_t)k]; sp_val[(size_t)o] = a; o++; }
-                }
-                sp_crow[(size_t)t] = ext->crow[(size_t)t] | ((size_t)t < ext->row_add.size() && ext->row_add[(size_t)t] ? (int32_t)0x80000000 : 0);
-            }
-        });
-    } else {
-        double K = 24.0;
-        if (const char* e = std::getenv("SPARTA_SPARSE_K")) K = atof(e);
-        if (updatable) K = 0.0;          // (the sparse-row image holds only what was non-zero at creation: sparta_vbs_set_values could not fill it)
-        if (K > 0.0) {
-            sparse_flag.assign((size_t)(br1 - br0), 0);
-            int64_t jo2 = 0, mo2 = 0, n_flagged = 0;
-            const int64_t row0 = row_part[br0];
-            std::vector<int64_t> cnt;
-            sp_rowptr.push_back(0);
-            // pass 1: which block-rows qualify and what they would cost as tiles (a handful stays with the tiles: see vbs_build_hybrid)
-            std::vector<uint8_t> qualifies((size_t)(br1 - br0), 0);
-            {
-                double steps_saved = 0.0;
-                int64_t mo1 = 0;
-                for (int64_t ib = br0; ib < br1; ib++) {
-                    const int64_t h = row_part[ib + 1] - row_part[ib], nb = nzcount[ib];
-                    const float* blk = mab + mab_lo + mo1;
-                    const int64_t n_el = nb * h * w;
-                    int64_t nnz = 0;
-                    for (int64_t q = 0; q < n_el; q++) nnz += stored(blk[q]) != 0.0f;
-                    const int64_t kdep = h16 && w % 64 == 0 ? 64 : 32;                 // k depth of a step of the kernels this handle would use
-                    const double steps_br = (double)nb * (double)((w + kdep - 1) / kdep) * (double)((h + 31) / 32);
-                    if (h > 0 && nb > 0 && (double)nnz < K * steps_br) { qualifies[(size_t)(ib - br0)] = 1; steps_saved += steps_br; }
-                    mo1 += n_el;
-                }
-                if (steps_saved < (double)sparta::sparse_min_steps()) std::fill(qualifies.begin(), qualifies.end(), 0);
-            }
-            for (int64_t ib = br0; ib < br1; ib++) {
-                const int64_t h = row_part[ib + 1] - row_part[ib], nb = nzcount[ib];
-                const float* blk = mab + mab_lo + mo2;
-                const int64_t n_el = nb * h * w;
-                if (qualifies[(size_t)(ib - br0)] && (int64_t)sp_col.size() + n_el < ((int64_t)1 << 40)) {
-                    sparse_flag[(size_t)(ib - br0)] = 1;
-                    n_flagged++;
-                    // rows of this block-row: (column, value) in the reference's order (blocks ascending, k ascending: vbr.cpp:358-363)
-                    cnt.assign((size_t)h, 0);
-                    for (int64_t b = 0; b < nb; b++)
-                        for (int64_t k = 0; k < w; k++)
-                            for (int64_t i = 0; i < h; i++) cnt[(size_t)i] += (stored(blk[(b * w + k) * h + i]) != 0.0f) && jab[jab_lo + jo2 + b] * w + k < cols;
-                    const size_t base_row = sp_crow.size();
-                    for (int64_t i = 0; i < h; i++) {
-                        sp_crow.push_back((int32_t)(row_part[ib] - row0 + i));
-                        sp_rowptr.push_back(sp_rowptr.back() + cnt[(size_t)i]);
-                    }
-                    sp_col.resize((size_t)sp_rowptr.back());
-                    sp_val.resize((size_t)sp_rowptr.back());
-                    for (int64_t i = 0; i < h; i++) cnt[(size_t)i] = sp_rowptr[base_row + (size_t)i];
-                    for (int64_t b = 0; b < nb; b++) {
-                        const int64_t c0 = jab[jab_lo + jo2 + b] * w;
-                        for (int64_t k = 0; k < w && c0 + k < cols; k++)
-                            for (int64_t i = 0; i < h; i++) {
-                                const float a = stored(blk[(b * w + k) * h + i]);
-                                if (a != 0.0f) { sp_col[(size_t)cnt[(size_t)i]] = (int32_t)(c0 + k); sp_val[(size_t)cnt[(size_t)i]++] = a; }
-                            }
-                    }
-                }
-                jo2 += nb;
-                mo2 += n_el;
-            }
-            if (n_flagged == 0) sparse_flag.clear();
-        }
-    }
-    // short rows: one wave each; rows with more than kSpLong nonzeros (hubs): segments of kSpSeg, one wave each + a reduction
-    if (kSpSeg == 0) {
-        const int64_t total = sp_rowptr.empty() ? 0 : sp_rowptr.back();
-        // (below 1 M nonzeros the GPU has more idle waves than rows: 32-nonzero segments -- ca-HepPh: rows of up to 256 nonzeros on one wave each took
-        // 57 us for 115 k nonzeros, 16 batches of gathers one after the other)
-        kSpSeg = total < ((int64_t)1 << 20) ? 32 : (total < ((int64_t)4 << 20) ? 128 : (total < ((int64_t)16 << 20) ? 256 : 512));
-    }
-    int64_t kSpLong = 2 * kSpSeg;
-    // Column windows.  The rows of B a launch gathers at any one time should lie close together: on a power-law matrix with millions of columns the nonzeros of the
-    // rows in flight are spread over all of B (GBs), every gather is an HBM access (measured with FETCH_SIZE: 327 of 336 GB gathered came from HBM on a part of
-    // the 8 M-row R-MAT) and the kernels run at the random-row rate of HBM.  So the columns are cut into windows of win_w columns (16-32 MB of B at N = 256..512
-    // in 16 bits), a row of more than 128 nonzeros is cut into segments that also end where its columns cross into another window (once a segment holds sp_minseg
-    // nonzeros), and the segments are PROCESSED window by window -- all rows' segments of window 0, then of window 1, ... (workgroups start in the order of the
-    // list).  What is in flight then gathers from one window, which the Infinity Cache and the L2s hold: the same part 62.4 -> 35.1 ms, R-MAT 2^20 at 0.1 %
-    // (B = 512, bf16) 11.6 -> 8.1 ms per part.  A row's partial rows are still added in segment order (the sum does not depend on the processing order).
-    // Width / segment minimum 65536 / 64 -> 32768 / 128 (the defaults): another 3 % on both configs (34.8 -> 33.9 ms, 8.05 -> 7.80).
-    // SPARTA_SP_WINDOW_COLS: unset = automatic (on from 262144 columns and 4 M nonzeros on this path), 0 = off, > 0 = the window width in columns;
-    // SPARTA_SP_LONG / SPARTA_SP_MINSEG: the row length above which a row is cut / the nonzeros a segment holds before a window boundary ends it.
-    const int64_t sp_total = sp_rowptr.empty() ? 0 : sp_rowptr.back();
-    // Round 4: the windows are dealt to eight streams, one per XCD (below: every L2 then holds its OWN window instead of a copy of everybody's), and are 8192 columns wide
-    // (2 MB of B per L2 at the 256-byte row chunks the large parts run with).  Parts of configs[4] / configs[3] at 1 %, sparse-row kernels, ms: one list of 32768-column
-    // windows 25.8 / 31.5 / 10.7 -> eight streams of 8192-column windows 24.5 / 28.9 / 10.3 (4096 .. 32768 columns: within 1 %).  SPARTA_SP_XCD=0: one list, 32768 columns.
-    bool sp_xcd = true;
-    if (const char* e = std::getenv("SPARTA_SP_XCD")) sp_xcd = atoi(e) != 0;
-    int64_t win_w = (cols >= 4 * 65536 && sp_total >= ((int64_t)4 << 20)) ? (sp_xcd ? 8192 : 32768) : 0, sp_minseg = 128;
-    std::vector<int32_t> sp_stream_begin;
-    if (const char* e = std::getenv("SPARTA_SP_WINDOW_COLS")) win_w = std::max(0, atoi(e));
-    if (win_w > 0) kSpLong = 128;
-    if (const char* e = std::getenv("SPARTA_SP_LONG")) kSpLong = std::max(8, atoi(e));
-    if (const char* e = std::getenv("SPARTA_SP_MINSEG")) sp_minseg = std::max(1, atoi(e));
-    // the segments of row t (appended to out, or only counted when out is null)
-    auto cut_row = [&](size_t t, std::vector<SpSegRec>* out) -> int32_t {
-        const int64_t p0 = sp_rowptr[t], n = sp_rowptr[t + 1] - p0;
-        int32_t n_seg = 0;
-        if (win_w > 0) {
-            const int64_t L = std::max<int64_t>(kSpSeg, 512);
-            int64_t o = 0;
-            while (o < n) {
-                // the segment [o, e): up to L nonzeros, ending early at the first window boundary behind its first sp_minseg nonzeros
-                int64_t e = std::min(n, o + L);
-                if (e - o > sp_minseg) {
-                    const int64_t wend = ((int64_t)sp_col[(size_t)(p0 + o + sp_minseg - 1)] / win_w + 1) * win_w;      // end of the window of the sp_minseg-th nonzero
-                    const int32_t* b = sp_col.data() + p0 + o + sp_minseg;
-                    const int32_t* bend = sp_col.data() + p0 + e;
-                    const int32_t* f = std::lower_bound(b, bend, (int32_t)std::min<int64_t>(wend, INT32_MAX));
-                    e = o + sp_minseg + (f - b);
-                }
-                if (out) out->push_back(SpSegRec{p0 + o, (int32_t)(e - o), 0});
-                n_seg++;
-                o = e;
-            }
-            return n_seg;
-        }
-        // a hub row's segments run in parallel, its partial rows are added one after the other: with segments of L nonzeros the chain is L / 16 gather
-        // batches + n / L additions -- shortest near L = sqrt(1.6 n) (a batch ~ 10 additions), never below the size-dependent base, never above 512
-        // (ia-wikiquote, 239 k nonzeros with rows of 10^4: 32-nonzero segments everywhere took 271 us, mostly the reduction of its hub rows)
-        int64_t L = ((int64_t)std::sqrt(1.6 * (double)n) + 15) / 16 * 16;
-        L = std::max(kSpSeg, std::min<int64_t>(512, L));
-        for (int64_t o = 0; o < n; o += L) { if (out) out->push_back(SpSegRec{p0 + o, (int32_t)std::min<int64_t>(L, n - o), 0}); n_seg++; }
-        return n_seg;
-    };
-    {
-        // rows in order; the segments of the long ones are cut on all threads (chunks of rows, concatenated in row order)
-        const int64_t n_rows_sp = (int64_t)sp_crow.size();
-        const int nt = sparta::host_threads();
-        const int64_t chunk = std::max<int64_t>(1024, (n_rows_sp + 4 * nt - 1) / (4 * std::max(nt, 1)));
-        const int64_t n_chunks = (n_rows_sp + chunk - 1) / std::max<int64_t>(chunk, 1);
-        std::vector<std::vector<SpSegRec>> segs_of((size_t)n_chunks);
-        std::vector<std::vector<SpLongRec>> long_of((size_t)n_chunks);
-        std::vector<std::vector<int32_t>> short_of((size_t)n_chunks);
-        sparta::parallel_for_dynamic(n_chunks, 1, [&](int64_t lo, int64_t hi, int) {
-            for (int64_t c = lo; c < hi; c++)
-                for (int64_t t = c * chunk; t < std::min(n_rows_sp, (c + 1) * chunk); t++) {
-                    if (sp_rowptr[(size_t)t + 1] - sp_rowptr[(size_t)t] <= kSpLong) { short_of[(size_t)c].push_back((int32_t)t); continue; }
-                    SpLongRec lr{(int32_t)t, (int32_t)segs_of[(size_t)c].size(), 0, 0};      // seg_begin: within the chunk for now
-                    lr.n_seg = cut_row((size_t)t, &segs_of[(size_t)c]);
-                    long_of[(size_t)c].push_back(lr);
-                }
-        });
-        for (int64_t c = 0; c < n_chunks; c++) {
-            const int32_t base = (int32_t)sp_segs.size();
-            if ((int64_t)sp_segs.size() + (int64_t)segs_of[(size_t)c].size() > INT32_MAX)
-                return sparta::fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_create: too many sparse-row segments for 32-bit indexing");
-            sp_list.insert(sp_list.end(), short_of[(size_t)c].begin(), short_of[(size_t)c].end());
-            sp_segs.insert(sp_segs.end(), segs_of[(size_t)c].begin(), segs_of[(size_t)c].end());
-            for (SpLongRec lr : long_of[(size_t)c]) { lr.seg_begin += base; sp_long.push_back(lr); }
-        }
-    }
-    // a segment's partial row lives at its index in row order (pad); the order of the list is the order the waves take them in: window by window
-    // (a stable counting sort on the window of the segment's first column)
-    for (size_t i = 0; i < sp_segs.size(); i++) sp_segs[i].pad = (int32_t)i;
-    if (win_w > 0 && !sp_segs.empty()) {
-        const int64_t n_win = (cols + win_w - 1) / win_w;
-        std::vector<int64_t> start((size_t)n_win + 1, 0);
-        for (const SpSegRec& g : sp_segs) start[(size_t)(sp_col[(size_t)g.p0] / win_w) + 1]++;
-        for (int64_t k = 0; k < n_win; k++) start[(size_t)k + 1] += start[(size_t)k];
-        std::vector<SpSegRec> sorted(sp_segs.size());
-        for (const SpSegRec& g : sp_segs) sorted[(size_t)start[(size_t)(sp_col[(size_t)g.p0] / win_w)]++] = g;
-        sp_segs.swap(sorted);
-        // XCD-affine order (k_sparse.hip: sparse_segments_xcd_kernel): the windows are dealt to eight streams -- heaviest first, each to the stream with the fewest
-        // nonzeros so far -- and the list becomes stream 0's windows in column order, then stream 1's, ...; workgroup b takes from stream b % 8 = its XCD.
-        if (sp_xcd && sp_segs.size() >= 64) {
-            std::vector<int64_t> w_nnz((size_t)n_win, 0), w_begin((size_t)n_win + 1, 0);
-            for (const SpSegRec& g : sp_segs) { const size_t k = (size_t)(sp_col[(size_t)g.p0] / win_w); w_nnz[k] += g.cnt; w_begin[k + 1]++; }
-            for (int64_t k = 0; k < n_win; k++) w_begin[(size_t)k + 1] += w_begin[(size_t)k];
-            std::vector<int64_t> order((size_t)n_win);
-            for (int64_t k = 0; k < n_win; k++) order[(size_t)k] = k;
-            std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return w_nnz[(size_t)a] > w_nnz[(size_t)b]; });
-            int64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            std::vector<int8_t> stream_of((size_t)n_win, 0);
-            for (int64_t k : order) {
-                int best = 0;
-                for (int x = 1; x < 8; x++) if (load[x] < load[best]) best = x;
-                stream_of[(size_t)k] = (int8_t)best;
-                load[best] += w_nnz[(size_t)k] + 16 * (w_begin[(size_t)k + 1] - w_begin[(size_t)k]);       // (a segment costs about a batch whatever it holds)
-            }
-            std::vector<SpSegRec> streamed;
-            streamed.reserve(sp_segs.size());
-            sp_stream_begin.assign(9, 0);
-            for (int x = 0; x < 8; x++) {
-                sp_stream_begin[(size_t)x] = (int32_t)streamed.size();
-                for (int64_t k = 0; k < n_win; k++)
-                    if (stream_of[(size_t)k] == x) streamed.insert(streamed.end(), sp_segs.begin() + w_begin[(size_t)k], sp_segs.begin() + w_begin[(size_t)k + 1]);
-            }
-            sp_stream_begin[8] = (int32_t)streamed.size();
-            sp_segs.swap(streamed);
-        }
-    }
-    n_sp_short = (int64_t)sp_list.size(); n_sp_long = (int64_t)sp_long.size();
-    trace.lap("sparse rows (device form)");
-    const uint8_t* skip = sparse_flag.empty() ? nullptr : sparse_flag.data();
-
-    // ---- plan: row tiles per class -----------------------------------------------------------------
-    std::vector<TileDesc> tiles[4];
-    std::vector<BlockRowDesc> brows;
-    std::vector<int32_t> jab32((size_t)std::max<int64_t>(nblocks, 1));
+    jab32.assign((size_t)std::max<int64_t>(nblocks, 1), 0);
     for (int64_t q = 0; q < nblocks; q++) {
         const int64_t jb = jab[jab_lo + q];
         if (jb < 0 || jb >= block_cols) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: jab entry out of range");
         jab32[(size_t)q] = (int32_t)jb;
     }
-    int64_t exec_area = 0;
+    return SPARTA_OK;
+}
+
+void build_class_tiles(const StreamPlanIn& in, ClassTilesHost& T) {
+    const int64_t cols = in.cols, w = in.w, br0 = in.br0, br1 = in.br1, jab_lo = in.jab_lo, block_cols = (in.cols - 1) / in.w + 1;
+    const int64_t* row_part = in.row_part; const int64_t* nzcount = in.nzcount; const int64_t* jab = in.jab;
+    const uint8_t* skip = in.skip;
+    std::vector<TileDesc>(&tiles)[4] = T.tiles;
+    std::vector<BlockRowDesc>& brows = T.brows;
+    int64_t(&n_real)[4] = T.n_real;
+    int64_t& exec_area = T.exec_area;
+    // ---- plan: row tiles per class -----------------------------------------------------------------
     {
         int64_t jo2 = 0, mo2 = 0;
         const int64_t row0 = row_part[br0];
@@ -684,7 +674,6 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
     // same B panels, so they should share an L2), each chunk sorted by descending cost (the hardware hands workgroups
     // to free slots in blockIdx order => longest-processing-time-first per XCD), interleaved so that entry t is XCD
     // t % 8's (t / 8)-th item; short chunks are padded with empty tiles (nb = 0, mt = 0: nothing loaded or stored).
-    int64_t n_real[4];
     for (int c = 0; c < 4; c++) n_real[c] = (int64_t)tiles[c].size();
     {
         const char* ord = std::getenv("SPARTA_TILE_ORDER");
@@ -714,56 +703,39 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
             L.swap(arranged);
         }
     }
+}
 
-    // ---- stream plans (persistent kernels): see build_stream_plans ----
-    StreamPlanHost plan;
-    {
-        StreamPlanIn pin{cols, w, br0, br1, jab_lo, mab_lo, row_part, nzcount, jab, mab, dtype, device, skip, updatable && h16, !h16 && flags == 0};
-        trace.lap("tile lists");
-        if (int rc = build_stream_plans(pin, plan)) return rc;
-        trace.lap("stream plans");
+// the device form of the column-compacted tiles of the hybrid builder
+int build_union_host(const sparta::UnionPlanHost& uni, int32_t dtype, int n_cus, UnionDevPlan& uplan) {
+    if (uni.empty()) return SPARTA_OK;
+    // (workgroups per CU the kernel is built for: k_union.hip's launch bound and LDS; SPARTA_UNION_WPC: developer A/B)
+    const int wpc = [] { const char* e = std::getenv("SPARTA_UNION_WPC"); return e ? std::max(1, atoi(e)) : 3; }();
+    return build_union_plan(uni, wpc * n_cus, uplan, dtype, n_cus);
+}
+
+// the block-column index of sparta_vbs_spmm_t (pattern only) and, for 16-bit handles, the [ceil(h / 8)][w][8] image of k_spmm_t.hip; fp32 handles read d_A (kept: drop_legacy_image)
+int build_spmm_t_host(const StreamPlanIn& in, SpmmTHost& H) {
+    const bool h16 = in.dtype != SPARTA_F32, bf16h = in.dtype == SPARTA_BF16;
+    const int64_t w = in.w, mab_lo = in.mab_lo;
+    const float* mab = in.mab;
+    SpmmTIndexHost& T = H.index;
+    if (int rc = build_spmm_t_index(in.cols, w, in.br0, in.br1, in.row_part, in.nzcount, in.jab, in.jab_lo, h16, T)) return rc;
+    if (h16 && T.image_elems > 0) {
+        std::unique_ptr<uint16_t[]>& img = H.image;
+        img.reset(new uint16_t[(size_t)T.image_elems]);
+        sparta::parallel_for_dynamic((int64_t)T.src.size(), 64, [&](int64_t lo, int64_t hi, int) {
+            for (int64_t q = lo; q < hi; q++) pack_spmm_t_block(mab + mab_lo + T.src[(size_t)q].src, T.src[(size_t)q].h, w, bf16h, img.get() + T.src[(size_t)q].dst);
+        });
     }
-    UnionDevPlan uplan;
-    if (ext && !ext->uni.empty()) {
-        int n_cus = 256;
-        if (!plan_debug) { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, device) == hipSuccess && pr.multiProcessorCount > 0) n_cus = pr.multiProcessorCount; }
-        // (workgroups per CU the kernel is built for: k_union.hip's launch bound and LDS; SPARTA_UNION_WPC: developer A/B)
-        const int wpc = [] { const char* e = std::getenv("SPARTA_UNION_WPC"); return e ? std::max(1, atoi(e)) : 3; }();
-        if (int rc = build_union_plan(ext->uni, wpc * n_cus, uplan, dtype, n_cus)) return rc;
-        trace.lap("column-compacted tiles (plan)");
-    }
-    std::vector<StepRec>(&steps)[2] = plan.steps;
-    std::vector<int32_t>(&wrange)[2] = plan.wrange;
-    std::vector<FixRec>& fix = plan.fix;
-    std::vector<int32_t>& fix_slots = plan.fix_slots;
-    const int n_workers = plan.n_workers, n_split = plan.n_split;
-    const int64_t kp = plan.kp;
+    return SPARTA_OK;
+}
 
-    // the handle is owned by `hold` until it is handed to the caller: any early return or exception below frees it and every
-    // device allocation made so far
-    struct VbsDeleter { void operator()(sparta_vbs* q) const { destroy_impl(q); } };
-    std::unique_ptr<sparta_vbs, VbsDeleter> hold(new (std::nothrow) sparta_vbs);
-    if (plan_debug) return fail(SPARTA_ERR_NO_DEVICE, "sparta_vbs_create: no HIP device visible (this path has no CPU fallback)");
-    sparta_vbs* v = hold.get();
-    if (!v) return fail(SPARTA_ERR_ALLOC, "sparta_vbs_create: out of host memory");
-    v->device = device; v->dtype = dtype; v->create_flags = flags;
-    v->zero_ranges = plan.zero_ranges;
-    v->rows = row_part[br1] - row_part[br0]; v->cols = cols; v->block_rows = br1 - br0; v->w = w;
-    v->nblocks = nblocks; v->nztot = nztot; v->exec_area = exec_area;
-    v->h_row_part.resize((size_t)(br1 - br0) + 1);          // what the block table of sparta_vbs_block_ssq / _mask_blocks is built from (with the handle's jab)
-    for (int64_t ib = br0; ib <= br1; ib++) v->h_row_part[(size_t)(ib - br0)] = row_part[ib] - row_part[br0];
-    v->h_nzcount.assign(nzcount + br0, nzcount + br1);
-
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, "sparta_vbs_create: hipSetDevice failed");
-#define CREATE_TRY(expr)                                                                                     \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess) {                                                                              \
-            std::string m_ = std::string(#expr) + ": " + hipGetErrorString(e_);                              \
-            return fail(e_ == hipErrorOutOfMemory ? SPARTA_ERR_ALLOC : SPARTA_ERR_HIP, m_);                  \
-        }                                                                                                    \
-    } while (0)
+// A itself: the caller's blocks (fp32), or the 16-bit slices of the stream plans with the sources of an updatable handle's slices
+int upload_a_image(sparta_vbs* v, const StreamPlanIn& in, bool updatable, const StreamPlanHost& plan) {
+    using sparta::fail;
+    const bool h16 = in.dtype != SPARTA_F32;
+    const int64_t nztot = v->nztot, mab_lo = in.mab_lo, kp = plan.kp;
+    const float* mab = in.mab;
     // A is padded by 128 floats so that no (masked-off) lane ever forms an address past the allocation
     if (!h16) {
         v->a_bytes = (nztot + 128) * (int64_t)sizeof(float);
@@ -789,6 +761,15 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
             CREATE_TRY(v->d_upd_hub.upload(plan.upd_hub));
         }
     }
+    return SPARTA_OK;
+}
+
+int upload_class_tiles(sparta_vbs* v, const std::vector<int32_t>& jab32, const ClassTilesHost& T) {
+    using sparta::fail;
+    const std::vector<TileDesc>(&tiles)[4] = T.tiles;
+    const std::vector<BlockRowDesc>& brows = T.brows;
+    const int64_t(&n_real)[4] = T.n_real;
+    v->exec_area = T.exec_area;
     CREATE_TRY(v->d_jab.upload(jab32));
     for (int c = 0; c < 4; c++) {
         v->n_tiles[c] = (int64_t)tiles[c].size();
@@ -798,6 +779,20 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
     }
     v->n_brows = (int64_t)brows.size();
     if (!brows.empty()) CREATE_TRY(v->d_brows.upload(brows));
+    return SPARTA_OK;
+}
+
+// the stream plans: step lists (padded here), worker ranges, fix-up records, the fragment / packed image of fp32 one-tile plans, the hub plan
+int upload_stream_plans(sparta_vbs* v, const StreamPlanIn& in, bool updatable, StreamPlanHost& plan) {
+    using sparta::fail;
+    const bool h16 = in.dtype != SPARTA_F32;
+    const int64_t cols = in.cols, w = in.w;
+    v->zero_ranges = plan.zero_ranges;
+    std::vector<StepRec>(&steps)[2] = plan.steps;
+    std::vector<int32_t>(&wrange)[2] = plan.wrange;
+    std::vector<FixRec>& fix = plan.fix;
+    std::vector<int32_t>& fix_slots = plan.fix_slots;
+    const int n_workers = plan.n_workers, n_split = plan.n_split;
     if (!steps[0].empty() || !steps[1].empty() || !fix.empty() || !plan.zero_ranges.empty() || plan.n_hub_steps > 0) {
         v->has_tail = (cols % w) != 0;
         v->n_workers = n_workers; v->n_fix = (int32_t)fix.size(); v->n_split = n_split; v->n_slots = (int32_t)fix_slots.size();
@@ -866,6 +861,12 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
         CREATE_TRY(v->d_fix_slots.alloc(std::max<size_t>(fix_slots.size(), 1)));
         if (!fix_slots.empty()) CREATE_TRY(hipMemcpy(v->d_fix_slots, fix_slots.data(), fix_slots.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
+    return SPARTA_OK;
+}
+
+int upload_union(sparta_vbs* v, const UnionDevPlan& uplan, const sparta::HybridSparse* ext) {
+    using sparta::fail;
+    const bool h16 = v->dtype != SPARTA_F32;
     for (int ty = 0; ty < kUnionTypes; ty++) {
         if (uplan.n_steps[ty] == 0) continue;
         v->u_workers[ty] = uplan.n_workers[ty]; v->u_steps[ty] = uplan.n_steps[ty]; v->u_tiles[ty] = uplan.n_tiles[ty]; v->u_steps_total += uplan.n_steps[ty];
@@ -879,88 +880,217 @@ static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t b
         v->exec_area += uplan.n_steps[ty] * 32 * uplan.type_rows[ty];
         v->u_exec_area += uplan.n_steps[ty] * 32 * uplan.type_rows[ty];
     }
-    if (ext) {
-        v->u_area = uplan.area; v->u_cols = uplan.cols; v->u_nnz = ext->uni.nnz; v->u_tail_nnz = ext->uni.tail_nnz; v->u_rows = uplan.rows;
-        for (int hh = 0; hh < 2; hh++) { v->u_tiles_h[hh] = uplan.tiles_by_height[hh]; v->u_steps_h[hh] = uplan.steps_by_height[hh]; }
+    v->u_area = uplan.area; v->u_cols = uplan.cols; v->u_nnz = ext->uni.nnz; v->u_tail_nnz = ext->uni.tail_nnz; v->u_rows = uplan.rows;
+    for (int hh = 0; hh < 2; hh++) { v->u_tiles_h[hh] = uplan.tiles_by_height[hh]; v->u_steps_h[hh] = uplan.steps_by_height[hh]; }
+    return SPARTA_OK;
+}
+
+int upload_sparse_rows(sparta_vbs* v, const SparseRowsHost& S) {
+    using sparta::fail;
+    const std::vector<int64_t>& sp_rowptr = S.rowptr;
+    const std::vector<int32_t>&sp_col = S.col, &sp_crow = S.crow, &sp_list = S.list, &sp_stream_begin = S.stream_begin;
+    const std::vector<float>& sp_val = S.val;
+    const std::vector<SpSegRec>& sp_segs = S.segs;
+    const std::vector<SpLongRec>& sp_long = S.longs;
+    const int64_t n_sp_short = (int64_t)sp_list.size(), n_sp_long = (int64_t)sp_long.size();
+    if (sp_crow.empty()) return SPARTA_OK;
+    v->n_sp_rows = (int64_t)sp_crow.size(); v->n_sp_short = n_sp_short; v->n_sp_long = n_sp_long; v->sp_nnz = sp_rowptr.back();
+    CREATE_TRY(v->d_sp_rowptr.upload(sp_rowptr));
+    CREATE_TRY(v->d_sp_col.upload(sp_col, 64));      // +64: a batch reads up to SP_BATCH entries at once
+    CREATE_TRY(v->d_sp_val.upload(sp_val, 64));
+    CREATE_TRY(v->d_sp_crow.upload(sp_crow));
+    if (!sp_list.empty()) CREATE_TRY(v->d_sp_list.upload(sp_list));
+    if (!sp_long.empty()) {
+        v->n_sp_segs = (int64_t)sp_segs.size();
+        CREATE_TRY(v->d_sp_segs.upload(sp_segs));
+        if (!sp_stream_begin.empty()) {
+            CREATE_TRY(v->d_sp_stream_begin.upload(sp_stream_begin.data(), 9));
+            for (int x = 0; x < 8; x++) v->sp_max_stream = std::max<int64_t>(v->sp_max_stream, sp_stream_begin[(size_t)x + 1] - sp_stream_begin[(size_t)x]);
+        }
+        CREATE_TRY(v->d_sp_long.upload(sp_long));
     }
-    if (!sp_crow.empty()) {
-        v->n_sp_rows = (int64_t)sp_crow.size(); v->n_sp_short = n_sp_short; v->n_sp_long = n_sp_long; v->sp_nnz = sp_rowptr.back();
-        CREATE_TRY(v->d_sp_rowptr.upload(sp_rowptr));
-        CREATE_TRY(v->d_sp_col.upload(sp_col, 64));      // +64: a batch reads up to SP_BATCH entries at once
-        CREATE_TRY(v->d_sp_val.upload(sp_val, 64));
-        CREATE_TRY(v->d_sp_crow.upload(sp_crow));
-        if (!sp_list.empty()) CREATE_TRY(v->d_sp_list.upload(sp_list));
-        if (!sp_long.empty()) {
-            v->n_sp_segs = (int64_t)sp_segs.size();
-            CREATE_TRY(v->d_sp_segs.upload(sp_segs));
-            if (!sp_stream_begin.empty()) {
-                CREATE_TRY(v->d_sp_stream_begin.upload(sp_stream_begin.data(), 9));
-                for (int x = 0; x < 8; x++) v->sp_max_stream = std::max<int64_t>(v->sp_max_stream, sp_stream_begin[(size_t)x + 1] - sp_stream_begin[(size_t)x]);
-            }
-            CREATE_TRY(v->d_sp_long.upload(sp_long));
+    return SPARTA_OK;
+}
+
+int upload_colres(sparta_vbs* v, const ColresImages& I) {
+    using sparta::fail;
+    if (!I.has_main) return SPARTA_OK;
+    const ColresHost& H = I.main;
+    CREATE_TRY(v->d_cr_col.upload(H.col));
+    if (!H.val.empty()) CREATE_TRY(v->d_cr_val.upload(H.val));
+    CREATE_TRY(v->d_cr_meta.upload(H.meta));
+    CREATE_TRY(v->d_cr_mode.upload(H.mode));
+    CREATE_TRY(v->d_cr_parts.upload(H.parts));
+    CREATE_TRY(v->d_cr_dest.upload(H.dest));
+    if (!H.longs.empty()) CREATE_TRY(v->d_cr_longs.upload(H.longs));
+    v->cr_slices = H.max_slices; v->cr_long = (int32_t)H.longs.size(); v->cr_plane = H.max_cells; v->cr_lmax = H.lmax;
+    v->cr_parts = (int32_t)H.parts.size(); v->cr_ranges = (int32_t)H.krange.size() - 1;
+    for (size_t r = 0; r < H.krange.size(); r++) v->cr_krange[r] = H.krange[r];
+    v->cr_entries = H.entries;
+    v->a_bytes += (int64_t)(H.col.size() * sizeof(uint16_t) + H.val.size() * sizeof(float));
+    v->cr_unit = H.val.empty();
+    if (!I.has_small) return SPARTA_OK;
+    const ColresHost& S = I.small;
+    auto& cs = v->cr_small;
+    CREATE_TRY(cs.col.upload(S.col));
+    if (!S.val.empty()) CREATE_TRY(cs.val.upload(S.val));
+    CREATE_TRY(cs.meta.upload(S.meta));
+    CREATE_TRY(cs.dest.upload(S.dest));
+    if (!S.longs.empty()) CREATE_TRY(cs.longs.upload(S.longs));
+    CREATE_TRY(cs.parts.upload(S.parts));
+    cs.slices = S.max_slices; cs.plane = S.max_cells; cs.n_parts = (int32_t)S.parts.size();
+    v->a_bytes += (int64_t)(S.col.size() * sizeof(uint16_t) + S.val.size() * sizeof(float));
+    return SPARTA_OK;
+}
+
+int upload_spmm_t(sparta_vbs* v, const SpmmTHost& H, bool updatable) {
+    using sparta::fail;
+    const SpmmTIndexHost& T = H.index;
+    v->n_t_items = (int64_t)T.items.size();
+    v->n_t_blocks = (int64_t)T.blocks.size();
+    CREATE_TRY(v->d_t_items.upload(T.items));
+    if (!T.blocks.empty()) CREATE_TRY(v->d_t_blocks.upload(T.blocks));
+    if (H.image) {
+        const std::unique_ptr<uint16_t[]>& img = H.image;
+        CREATE_TRY(v->d_t_A.upload(img.get(), (size_t)T.image_elems));
+        v->a_bytes += T.image_elems * (int64_t)sizeof(uint16_t);
+        if (updatable) {
+            v->n_t_src = (int64_t)T.src.size();
+            CREATE_TRY(v->d_t_src.upload(T.src));
         }
     }
+    return SPARTA_OK;
+}
+
+// SPARTA_PLAN_DEBUG on a host without a GPU (developer aid, scripts/asan_host.sh): the host planning of the tiles runs to its end, then the call fails as usual
+int plan_without_device(const StreamPlanIn& in, const sparta::HybridSparse* ext, sparta::BuildTrace& trace) {
+    ClassTilesHost ct;
+    build_class_tiles(in, ct);
+    trace.lap("tile lists");
+    StreamPlanHost plan;
+    if (int rc = build_stream_plans(in, plan)) return rc;
+    trace.lap("stream plans");
+    UnionDevPlan uplan;
+    if (ext) if (int rc = build_union_host(ext->uni, in.dtype, in.n_cus, uplan)) return rc;
+    if (ext && !ext->uni.empty()) trace.lap("column-compacted tiles (plan)");
+    return no_device();
+}
+
+}  // namespace
+
+extern "C" {
+
+int sparta_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+// `ext` (sparta_vbs_create_from_csr): the sparse-row part of the matrix decided and collected by the hybrid host builder.  Fully sparse
+// block-rows (ext->flag 1) have nzcount = 0 in the arrays given here and get neither tiles nor zero-fill records; MIXED block-rows (flag 2)
+// keep their well-filled blocks in nzcount / jab / mab as tiles like any other, and the nonzeros of their other blocks are sparse rows that
+// add to C behind the tile launches (see the ordering note at the sparse-row launch in spmm_impl).
+static int create_core(sparta_vbs_t** out, int64_t rows, int64_t cols, int64_t block_rows, int64_t w, const int64_t* row_part,
+                       const int64_t* nzcount, const int64_t* jab, const float* mab, int64_t br0, int64_t br1, int32_t dtype,
+                       int32_t device, const sparta::HybridSparse* ext, int32_t flags = 0) {
+    using sparta::fail;
+    if (!out) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: out is NULL");
+    if (flags & ~(SPARTA_CREATE_UPDATABLE | SPARTA_CREATE_TRANSPOSE)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create_range_ex: unknown bits in flags");
+    const bool updatable = (flags & SPARTA_CREATE_UPDATABLE) != 0;        // every block-row stays in the dense-block images; the slices' sources are kept
+    const bool transposable = (flags & SPARTA_CREATE_TRANSPOSE) != 0;     // sparta_vbs_spmm_t: block-column index + an image it can read (changes nothing of the forward product)
+    if (transposable && ext) return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_create: SPARTA_CREATE_TRANSPOSE needs the dense blocks of every block-row");
+    *out = nullptr;
+    sparta::BuildTrace trace("vbs_create");
+    if (rows <= 0 || cols <= 0 || block_rows <= 0 || w <= 0 || !row_part || !nzcount)
+        return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: bad dimensions or NULL index array");
+    if (br0 < 0 || br1 > block_rows || br0 >= br1) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: bad block-row range");
+    if (dtype != SPARTA_F32 && dtype != SPARTA_F16 && dtype != SPARTA_BF16) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: bad dtype");
+    const bool h16 = dtype != SPARTA_F32;
+    if (h16 && w % 32 != 0)
+        return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_create: SPARTA_F16 / SPARTA_BF16 need block_col_size % 32 == 0 (only the stream kernels have a 16-bit form)");
+    if (rows > INT32_MAX || w > (1 << 20)) return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_create: rows >= 2^31 or w > 2^20");
+    const int64_t block_cols = (cols - 1) / w + 1;
+
+    // validate the partition and locate the range inside jab / mab
+    if (row_part[0] != 0 || row_part[block_rows] != rows) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: row_part must span [0, rows]");
+    int64_t jab_lo = 0, mab_lo = 0, jab_hi = 0, mab_hi = 0, jo = 0, mo = 0;
+    for (int64_t ib = 0; ib < block_rows; ib++) {
+        const int64_t h = row_part[ib + 1] - row_part[ib];
+        if (h < 0 || nzcount[ib] < 0 || nzcount[ib] > block_cols) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: invalid row_part / nzcount");
+        if (h > INT32_MAX / 2 || nzcount[ib] > INT32_MAX) return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_create: block-row too large");
+        if (ib == br0) { jab_lo = jo; mab_lo = mo; }
+        jo += nzcount[ib];
+        mo += nzcount[ib] * h * w;
+        if (ib == br1 - 1) { jab_hi = jo; mab_hi = mo; }
+    }
+    const int64_t nblocks = jab_hi - jab_lo, nztot = mab_hi - mab_lo;
+    if (nblocks > 0 && (!jab || !mab)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: jab / mab is NULL");
+
+    const int ndev = sparta_device_count();
+    const bool plan_debug = std::getenv("SPARTA_PLAN_DEBUG") != nullptr && ndev <= 0;   // developer aid: the host planning on a host without a GPU, then fail as usual
+    if (ndev <= 0 && !plan_debug) return no_device();
+    if (!plan_debug && (device < 0 || device >= ndev)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_create: device index out of range");
+    StreamPlanIn in{cols, w, br0, br1, jab_lo, mab_lo, row_part, nzcount, jab, mab, dtype, plan_debug ? 256 : device_cu_count(device), nullptr, updatable && h16, !h16 && flags == 0};
+    std::vector<int32_t> jab32;
+    if (int rc = narrow_jab(jab, jab_lo, nblocks, block_cols, jab32)) return rc;
+
+    // ---- sparse rows: which block-rows are better served as rows of (column, value), and their device form; they live until the resident-column image is made ----
+    SparseRowsHost sp;
+    if (ext) collect_sparse_rows_from_ext(*ext, cols, dtype, sp);
+    else collect_sparse_rows_from_blocks(in, updatable, sp);
+    if (int rc = order_sparse_rows(sp, cols)) return rc;
+    trace.lap("sparse rows (device form)");
+    in.skip = sp.flag.empty() ? nullptr : sp.flag.data();
+    if (plan_debug) return plan_without_device(in, ext, trace);
+
+    // the handle is owned by `hold` until it is handed to the caller: any early return or exception below frees it and every
+    // device allocation made so far
+    struct VbsDeleter { void operator()(sparta_vbs* q) const { destroy_impl(q); } };
+    std::unique_ptr<sparta_vbs, VbsDeleter> hold(new (std::nothrow) sparta_vbs);
+    sparta_vbs* v = hold.get();
+    if (!v) return fail(SPARTA_ERR_ALLOC, "sparta_vbs_create: out of host memory");
+    v->device = device; v->dtype = dtype; v->create_flags = flags;
+    v->rows = row_part[br1] - row_part[br0]; v->cols = cols; v->block_rows = br1 - br0; v->w = w;
+    v->nblocks = nblocks; v->nztot = nztot;
+    v->h_row_part.resize((size_t)(br1 - br0) + 1);          // what the block table of sparta_vbs_block_ssq / _mask_blocks is built from (with the handle's jab)
+    for (int64_t ib = br0; ib <= br1; ib++) v->h_row_part[(size_t)(ib - br0)] = row_part[ib] - row_part[br0];
+    v->h_nzcount.assign(nzcount + br0, nzcount + br1);
+
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(SPARTA_ERR_HIP, "sparta_vbs_create: hipSetDevice failed");
+    {   // ---- the w-wide tiles: class tile lists and stream plans, with A's own image ----
+        ClassTilesHost ct;
+        build_class_tiles(in, ct);
+        trace.lap("tile lists");
+        StreamPlanHost plan;
+        if (int rc = build_stream_plans(in, plan)) return rc;
+        trace.lap("stream plans");
+        if (int rc = upload_a_image(v, in, updatable, plan)) return rc;
+        if (int rc = upload_class_tiles(v, jab32, ct)) return rc;
+        if (int rc = upload_stream_plans(v, in, updatable, plan)) return rc;
+    }
+    if (ext) {   // ---- column-compacted tiles ----
+        UnionDevPlan uplan;
+        if (int rc = build_union_host(ext->uni, dtype, in.n_cus, uplan)) return rc;
+        if (!ext->uni.empty()) trace.lap("column-compacted tiles (plan)");
+        if (int rc = upload_union(v, uplan, ext)) return rc;
+    }
+    if (int rc = upload_sparse_rows(v, sp)) return rc;
     // resident-column image (k_colres.hip): at least half the rows of C are sparse rows (the tile launches, if any, come first on the stream), a column of B fits LDS
-    if (!h16 && !sp_crow.empty()) {
-        ColresHost H;
-        if (build_colres(v->rows, cols, sp_rowptr, sp_col, sp_val, sp_crow, H)) {
-            CREATE_TRY(v->d_cr_col.upload(H.col));
-            if (!H.val.empty()) CREATE_TRY(v->d_cr_val.upload(H.val));
-            CREATE_TRY(v->d_cr_meta.upload(H.meta));
-            CREATE_TRY(v->d_cr_mode.upload(H.mode));
-            CREATE_TRY(v->d_cr_parts.upload(H.parts));
-            CREATE_TRY(v->d_cr_dest.upload(H.dest));
-            if (!H.longs.empty()) CREATE_TRY(v->d_cr_longs.upload(H.longs));
-            v->cr_slices = H.max_slices; v->cr_long = (int32_t)H.longs.size(); v->cr_plane = H.max_cells; v->cr_lmax = H.lmax;
-            v->cr_parts = (int32_t)H.parts.size(); v->cr_ranges = (int32_t)H.krange.size() - 1;
-            for (size_t r = 0; r < H.krange.size(); r++) v->cr_krange[r] = H.krange[r];
-            v->cr_entries = H.entries;
-            v->a_bytes += (int64_t)(H.col.size() * sizeof(uint16_t) + H.val.size() * sizeof(float));
-            v->cr_unit = H.val.empty();
-            // the four-part image for products of few column sets (SPARTA_COLRES_SMALL=0: not built)
-            const char* es = std::getenv("SPARTA_COLRES_SMALL");
-            if (v->cr_parts == 1 && v->cr_ranges == 1 && v->rows >= 2048 && !(es && atoi(es) == 0)) {
-                ColresHost S;
-                if (build_colres(v->rows, cols, sp_rowptr, sp_col, sp_val, sp_crow, S, 4) && S.val.empty() == H.val.empty()) {
-                    auto& cs = v->cr_small;
-                    CREATE_TRY(cs.col.upload(S.col));
-                    if (!S.val.empty()) CREATE_TRY(cs.val.upload(S.val));
-                    CREATE_TRY(cs.meta.upload(S.meta));
-                    CREATE_TRY(cs.dest.upload(S.dest));
-                    if (!S.longs.empty()) CREATE_TRY(cs.longs.upload(S.longs));
-                    CREATE_TRY(cs.parts.upload(S.parts));
-                    cs.slices = S.max_slices; cs.plane = S.max_cells; cs.n_parts = (int32_t)S.parts.size();
-                    v->a_bytes += (int64_t)(S.col.size() * sizeof(uint16_t) + S.val.size() * sizeof(float));
-                }
-            }
-        }
+    if (!h16 && !sp.crow.empty()) {
+        ColresImages cr;
+        build_colres_images(v->rows, cols, sp, cr);
+        if (int rc = upload_colres(v, cr)) return rc;
     }
     if (transposable) {
-        // the block-column index (pattern only) and, for 16-bit handles, the [ceil(h / 8)][w][8] image of k_spmm_t.hip; fp32 handles read d_A (kept: drop_legacy_image)
-        SpmmTIndexHost T;
-        if (int rc = build_spmm_t_index(cols, w, br0, br1, row_part, nzcount, jab, jab_lo, h16, T)) return rc;
-        v->n_t_items = (int64_t)T.items.size();
-        v->n_t_blocks = (int64_t)T.blocks.size();
-        CREATE_TRY(v->d_t_items.upload(T.items));
-        if (!T.blocks.empty()) CREATE_TRY(v->d_t_blocks.upload(T.blocks));
-        if (h16 && T.image_elems > 0) {
-            std::unique_ptr<uint16_t[]> img(new uint16_t[(size_t)T.image_elems]);
-            sparta::parallel_for_dynamic((int64_t)T.src.size(), 64, [&](int64_t lo, int64_t hi, int) {
-                for (int64_t q = lo; q < hi; q++) pack_spmm_t_block(mab + mab_lo + T.src[(size_t)q].src, T.src[(size_t)q].h, w, bf16h, img.get() + T.src[(size_t)q].dst);
-            });
-            CREATE_TRY(v->d_t_A.upload(img.get(), (size_t)T.image_elems));
-            v->a_bytes += T.image_elems * (int64_t)sizeof(uint16_t);
-            if (updatable) {
-                v->n_t_src = (int64_t)T.src.size();
-                CREATE_TRY(v->d_t_src.upload(T.src));
-            }
-        }
+        SpmmTHost t;
+        if (int rc = build_spmm_t_host(in, t)) return rc;
+        if (int rc = upload_spmm_t(v, t, updatable)) return rc;
     }
     CREATE_TRY(v->ev0.create());
     CREATE_TRY(v->ev1.create());
     CREATE_TRY(v->tev0.create());
     CREATE_TRY(v->tev1.create());
-#undef CREATE_TRY
     trace.lap("upload");
     *out = hold.release();
     return SPARTA_OK;
@@ -1262,6 +1392,110 @@ int sparta_colres_host_check(int64_t rows, int64_t cols, const int64_t* rowptr, 
     info[8] = (int64_t)H.parts.size(); info[9] = n_ranges;
     return SPARTA_OK;
     SPARTA_GUARD_END("sparta_colres_host_check")
+}
+
+// the sparse-row device form of a CSR matrix (order_sparse_rows), built and walked on the HOST as the kernels of k_sparse.hip walk it for ONE column x of B: the short
+// rows from the list, a long row through its record -- its segments in row order, one partial per segment at the segment's `pad`, the partials added in that order.
+// What the CPU suite checks the builder with (no GPU involved; not a product path).  crow: as for sparta_colres_host_check.
+// info: [0] sparse rows, [1] short rows, [2] long rows, [3] segments, [4] window width (0: off), [5] streams with segments (0: one list), [6] base segment length,
+// [7] longest short row, [8] SPARTA_SP_MINSEG as resolved
+int sparta_sparse_rows_host_check(int64_t rows, int64_t cols, const int64_t* rowptr, const int32_t* colidx, const float* vals, const int64_t* crow, const float* x, float* y,
+                                  int64_t* info) {
+    using sparta::fail;
+    SPARTA_GUARD_BEGIN
+    if (rows <= 0 || cols <= 0 || !rowptr || !colidx || !vals || !x || !y || !info) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: bad argument");
+    // the walk below indexes x by column and y by crow: a CSR that is not one comes back as an error, not as a read out of bounds
+    if (rowptr[0] != 0) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: rowptr must start at 0");
+    for (int64_t i = 0; i < rows; i++) {
+        if (rowptr[i + 1] < rowptr[i]) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: rowptr is not monotone");
+        for (int64_t k = rowptr[i]; k < rowptr[i + 1]; k++)
+            if (colidx[k] < 0 || colidx[k] >= cols) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: column index out of range");
+        if (crow && crow[i] != -1 && (crow[i] < 0 || (crow[i] & 0x7fffffffll) >= rows || (crow[i] >> 32) != 0))
+            return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: crow entry out of range");
+    }
+    SparseRowsHost S;
+    S.rowptr.push_back(0);
+    for (int64_t i = 0; i < rows; i++) {
+        if (crow && crow[i] == -1) continue;
+        S.col.insert(S.col.end(), colidx + rowptr[i], colidx + rowptr[i + 1]);
+        S.val.insert(S.val.end(), vals + rowptr[i], vals + rowptr[i + 1]);
+        S.rowptr.push_back((int64_t)S.col.size());
+        S.crow.push_back(crow ? (int32_t)(uint32_t)(crow[i] & 0xffffffffll) : (int32_t)i);
+    }
+    for (int k = 0; k < 12; k++) info[k] = 0;
+    if (int rc = order_sparse_rows(S, cols)) return rc;
+    const int64_t n = (int64_t)S.crow.size(), n_segs = (int64_t)S.segs.size();
+    std::vector<uint8_t> covered((size_t)S.rowptr.back(), 0), seen((size_t)n, 0);
+    // entries [p0, p0 + cnt) of the CSR times x, each entry taken once
+    auto dot = [&](int64_t p0, int64_t cnt, float& sum) -> bool {
+        if (p0 < 0 || cnt < 0 || p0 + cnt > S.rowptr.back()) return false;
+        for (int64_t k = p0; k < p0 + cnt; k++) {
+            if (covered[(size_t)k]++) return false;
+            sum = std::fma(S.val[(size_t)k], x[S.col[(size_t)k]], sum);
+        }
+        return true;
+    };
+    auto finish = [&](int64_t t, float sum) { const int32_t c = S.crow[(size_t)t]; if (c < 0) y[c & 0x7fffffff] += sum; else y[c] = sum; };
+    for (const int32_t t : S.list) {
+        if (t < 0 || t >= n || seen[(size_t)t]++) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: a list entry is no row, or a row is taken twice");
+        if (S.rowptr[(size_t)t + 1] - S.rowptr[(size_t)t] > S.long_cut) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: a long row in the list of short rows");
+        float sum = 0.0f;
+        if (!dot(S.rowptr[(size_t)t], S.rowptr[(size_t)t + 1] - S.rowptr[(size_t)t], sum)) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: a nonzero is covered twice");
+        finish(t, sum);
+    }
+    std::vector<int64_t> at_pad((size_t)n_segs, -1);                                  // segment in row order -> its place in the list
+    for (int64_t i = 0; i < n_segs; i++) {
+        const int32_t p = S.segs[(size_t)i].pad;
+        if (p < 0 || p >= n_segs || at_pad[(size_t)p] >= 0) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: pad is not a permutation of the segments");
+        at_pad[(size_t)p] = i;
+    }
+    std::vector<float> partial((size_t)n_segs, 0.0f);
+    int64_t segs_of_rows = 0;
+    for (const SpLongRec& lr : S.longs) {
+        if (lr.ord < 0 || lr.ord >= n || seen[(size_t)lr.ord]++) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: a long record is no row, or a row is taken twice");
+        if (lr.n_seg <= 0 || lr.seg_begin != segs_of_rows || (int64_t)lr.seg_begin + lr.n_seg > n_segs)
+            return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: the segments of the long rows are not back to back in row order");
+        int64_t next = S.rowptr[(size_t)lr.ord];
+        float sum = 0.0f;
+        for (int32_t q = lr.seg_begin; q < lr.seg_begin + lr.n_seg; q++) {
+            const SpSegRec& g = S.segs[(size_t)at_pad[(size_t)q]];
+            if (g.p0 != next || g.cnt <= 0) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: a row's segments are not contiguous and in order");
+            if (!dot(g.p0, g.cnt, partial[(size_t)q])) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: a nonzero is covered twice");
+            next = g.p0 + g.cnt;
+            sum += partial[(size_t)q];
+        }
+        if (next != S.rowptr[(size_t)lr.ord + 1]) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: a row's segments do not end at the row's end");
+        segs_of_rows += lr.n_seg;
+        finish(lr.ord, sum);
+    }
+    if (segs_of_rows != n_segs) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: a segment belongs to no long row");
+    for (int64_t t = 0; t < n; t++) if (!seen[(size_t)t]) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: a row is neither short nor long");
+    for (const uint8_t c : covered) if (c != 1) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: a nonzero is not covered");
+    // the order the waves take the segments in: window by window (one list), or per stream (XCD order)
+    auto window_of = [&](int64_t i) { return (int64_t)S.col[(size_t)S.segs[(size_t)i].p0] / S.win_w; };
+    int64_t streams_used = 0;
+    if (!S.stream_begin.empty()) {
+        const std::vector<int32_t>& sb = S.stream_begin;
+        if (S.win_w <= 0 || sb.size() != 9 || sb[0] != 0 || sb[8] != n_segs) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: stream_begin does not span the segments");
+        std::vector<int8_t> stream_of((size_t)((cols + S.win_w - 1) / S.win_w), -1);
+        for (int s = 0; s < 8; s++) {
+            if (sb[(size_t)s + 1] < sb[(size_t)s]) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: stream_begin is not monotone");
+            streams_used += sb[(size_t)s + 1] > sb[(size_t)s];
+            for (int64_t i = sb[(size_t)s]; i < sb[(size_t)s + 1]; i++) {
+                const int64_t k = window_of(i);
+                if (stream_of[(size_t)k] >= 0 && stream_of[(size_t)k] != s) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: a window's segments are split across streams");
+                stream_of[(size_t)k] = (int8_t)s;
+                if (i > sb[(size_t)s] && window_of(i - 1) > k) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: a stream's windows are not in column order");
+            }
+        }
+    } else if (S.win_w > 0) {
+        for (int64_t i = 1; i < n_segs; i++)
+            if (window_of(i - 1) > window_of(i)) return fail(SPARTA_ERR_INVALID, "sparta_sparse_rows_host_check: the segments are not in window order");
+    }
+    info[0] = n; info[1] = (int64_t)S.list.size(); info[2] = (int64_t)S.longs.size(); info[3] = n_segs; info[4] = S.win_w; info[5] = streams_used;
+    info[6] = S.seg; info[7] = S.long_cut; info[8] = S.minseg;
+    return SPARTA_OK;
+    SPARTA_GUARD_END("sparta_sparse_rows_host_check")
 }
 
 // the hybrid image of a CSR matrix under `grouping`, built exactly as sparta_vbs_create_from_csr builds it for an fp32 handle -- w-wide tiles, column-compacted tiles,
@@ -1868,12 +2102,10 @@ int spmm_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int
     if (algo != SPARTA_SPMM_MFMA && algo != SPARTA_SPMM_EXACT) return fail(SPARTA_ERR_INVALID, "sparta_vbs_spmm: bad algo");
     if (ptr_space != SPARTA_PTR_HOST && ptr_space != SPARTA_PTR_DEVICE) return fail(SPARTA_ERR_INVALID, "sparta_vbs_spmm: bad ptr_space");
 
-    DeviceGuard guard(A->device);
-    if (!guard.ok) return fail(SPARTA_ERR_HIP, "sparta_vbs_spmm: hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    const CaptureScope capture(st, ptr_space == SPARTA_PTR_DEVICE, A);
-    if (g_capturing && dt_ms) return capture_refusal("time the product (dt_ms != NULL synchronises)");
-    return capture.done(spmm_run(A, B, ldb, b_layout, shard_rows, shard_stride, n_cols, C, ldc, c_layout, accumulate, ptr_space, st, algo, dt_ms));
+    const DeviceCall call{"sparta_vbs_spmm", A, (hipStream_t)stream, ptr_space == SPARTA_PTR_DEVICE, dt_ms, "the product"};
+    return open_call(call, [&](hipStream_t st) {
+        return spmm_run(A, B, ldb, b_layout, shard_rows, shard_stride, n_cols, C, ldc, c_layout, accumulate, ptr_space, st, algo, dt_ms);
+    });
 }
 
 // the product of a checked call, inside spmm_impl's guard and capture scope

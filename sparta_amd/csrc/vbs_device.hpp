@@ -835,7 +835,7 @@ void launch_a8_live_scales(hipStream_t st, const StepRec* a8_recs, int64_t n_ste
 struct StreamPlanIn {
     int64_t cols, w, br0, br1, jab_lo, mab_lo;
     const int64_t* row_part; const int64_t* nzcount; const int64_t* jab; const float* mab;
-    int32_t dtype, device;
+    int32_t dtype, n_cus;                     // n_cus: compute units of the handle's device (the host builders make no HIP call)
     const uint8_t* skip;                      // [br1 - br0] block-rows handled by the sparse-row path (no tiles), or nullptr
     bool updatable = false;                   // SPARTA_CREATE_UPDATABLE: record the source of every 16-bit slice (StreamPlanHost::upd_map / upd_hub)
     bool allow_pack = false;                  // fp32 handles made without creation flags: the one-tile plan may become a packed plan (k_f32_packed.hip)
@@ -907,6 +907,46 @@ struct SpmmTIndexHost {
 };
 int build_spmm_t_index(int64_t cols, int64_t w, int64_t br0, int64_t br1, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, int64_t jab_lo, bool h16,
                        SpmmTIndexHost& T);
+// the host forms of creation (vbs_capi.cpp: one builder and one upload per family)
+// The sparse rows in the form the kernels of k_sparse.hip take them: a CSR of the rows, the short rows as a list (one wave each), the long ones cut into segments
+struct SparseRowsHost {
+    std::vector<uint8_t> flag;                // [br1 - br0] 1: the block-row gets no tile (StreamPlanIn::skip); empty: none does
+    std::vector<int64_t> rowptr;
+    std::vector<int32_t> col, crow;           // crow: the row of C of every sparse row; bit 31: the row ADDS to C (a mixed block-row's sparse part)
+    std::vector<float> val;
+    std::vector<int32_t> list;                // the short rows
+    std::vector<SpSegRec> segs;               // the segments of the long rows in the order the waves take them; pad = the segment's index in row order
+    std::vector<SpLongRec> longs;
+    std::vector<int32_t> stream_begin;        // XCD order: [9] the eight streams of segs; empty: one list
+    int64_t seg = 0, long_cut = 0, minseg = 0, win_w = 0;   // as order_sparse_rows resolved them: base segment length, longest short row, SPARTA_SP_MINSEG, window width (0: off)
+};
+// the resident-column image (k_colres.hip) of sparse rows
+constexpr int64_t kColresCells = 160 * 1024 / 4;                  // floats of LDS a workgroup may hold
+struct ColresHost {
+    std::vector<uint16_t> col;                                    // per batch of 4 steps and lane: four columns (relative to their K range) ...
+    std::vector<float> val;                                       // ... and four values (empty: every stored value is 1.0f -- a unit image, the reference's -P 1)
+    std::vector<ColresPartDev> parts;
+    std::vector<int32_t> meta, dest;                              // per part: see ColresPartDev
+    std::vector<uint8_t> mode;                                    // per row of C (padded to 4): 0 not this kernel's, 1 store, 2 add
+    std::vector<ColresLong> longs;
+    std::vector<int32_t> krange;                                  // [n_ranges + 1]
+    int32_t max_slices = 0, max_cells = 0, lmax = 0;              // slices of the part with most; cells a column set needs in LDS (largest range of B + its zero cell / largest staging image)
+    int64_t entries = 0;
+};
+// what a handle keeps: the main image and, where eligible, the four-part image (SPARTA_COLRES_SMALL=0: not built)
+struct ColresImages { ColresHost main, small; bool has_main = false, has_small = false; };
+// the row tiles of every class in launch order (padded to 8 streams), the block-row descriptors, and the elements the tile kernels multiply
+struct ClassTilesHost {
+    std::vector<TileDesc> tiles[4];
+    int64_t n_real[4] = {0, 0, 0, 0};
+    std::vector<BlockRowDesc> brows;
+    int64_t exec_area = 0;
+};
+// the transposed index with, for 16-bit handles, the [ceil(h / 8)][w][8] image of k_spmm_t.hip
+struct SpmmTHost {
+    SpmmTIndexHost index;
+    std::unique_ptr<uint16_t[]> image;       // index.image_elems elements, or null
+};
 // the block table of block pruning: [n_blocks][4] = {offset, n_in, n_all, (block-row - br0) << 32 | block column}; table == nullptr only counts
 int build_block_table(int64_t cols, int64_t w, int64_t br0, int64_t br1, const int64_t* row_part, const int64_t* nzcount, const int64_t* jab, int64_t jab_lo,
                       int64_t* table, int64_t* n_blocks);

@@ -31,7 +31,7 @@ int build_stream_plans(const StreamPlanIn& in, StreamPlanHost& P) {
     using sparta::fail;
     const int64_t cols = in.cols, w = in.w, br0 = in.br0, br1 = in.br1, jab_lo = in.jab_lo, mab_lo = in.mab_lo;
     const int64_t* row_part = in.row_part; const int64_t* nzcount = in.nzcount; const int64_t* jab = in.jab; const float* mab = in.mab;
-    const int32_t dtype = in.dtype, device = in.device;
+    const int32_t dtype = in.dtype;
     const bool h16 = dtype != SPARTA_F32;
     std::vector<StepRec>(&steps)[2] = P.steps;
     std::vector<int32_t>(&wrange)[2] = P.wrange;
@@ -52,9 +52,7 @@ int build_stream_plans(const StreamPlanIn& in, StreamPlanHost& P) {
     const int64_t kp = !h16 ? SK_KP : (w % 64 == 0 ? 64 : 32);
     P.kp = kp;
     if (w % SK_KP == 0) {
-        hipDeviceProp_t prop;
-        int cus = 256;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+        const int cus = in.n_cus;
         // workers (persistent workgroups) per CU: fp32 two -- the MFMAs of one hide the loads of the other (one: 60.8 us against 54 on the flagship);
         // 16-bit ONE -- these kernels are bound by the L2 / HBM side, a second workgroup per CU only adds cache pressure (flagship 23.4 -> 23.1 us, 64 x 64
         // blocks 23.8 -> 23.1, N = 256 46.7 -> 42.9, banded 32.2 -> 30.6; three: slower still) and 256 workers balance better than 512

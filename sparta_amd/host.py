@@ -59,6 +59,21 @@ def a8_quantize_group(v, kcols=None):
     return codes, int(e[0])
 
 
+def sparse_rows_host_check(rowptr, colidx, vals, cols, x, crow=None, y=None):
+    """sparta_sparse_rows_host_check: the sparse-row device form of a CSR matrix (short rows, segments of the long rows, column windows, XCD streams) built and
+    walked on the host for one column x of B, no GPU.  crow: the row of y of every CSR row (None: its own; + 2^31: the row adds to y; -1: not a sparse row);
+    y: what the rows start from (default zeros).  Returns (y, info); raises SpartaError if the form is broken."""
+    rowptr, colidx = np.ascontiguousarray(rowptr, np.int64), np.ascontiguousarray(colidx, np.int32)
+    vals, x = np.ascontiguousarray(vals, np.float32), np.ascontiguousarray(x, np.float32)
+    rows = rowptr.size - 1
+    y = np.zeros(rows, np.float32) if y is None else np.array(y, np.float32)
+    cr = None if crow is None else np.ascontiguousarray(crow, np.int64)
+    info = np.zeros(12, np.int64)
+    check(lib.sparta_sparse_rows_host_check(rows, int(cols), _p64(rowptr), _p32(colidx), _pf(vals), None if cr is None else _p64(cr), _pf(x), _pf(y), _p64(info)))
+    keys = ["rows", "short_rows", "long_rows", "segments", "win_w", "streams", "seg", "long", "minseg"]
+    return y, {k: int(info[i]) for i, k in enumerate(keys)}
+
+
 def _p64(a):
     return a.ctypes.data_as(_i64p)
 
