@@ -6,14 +6,26 @@
 //   k_h16.hip         fp16 / bf16 storage: LDS-staged and direct stream kernels, conversions (the direct kernel's body: k_h16_direct.inc)
 //   k_h16_live.hip    the live form of the direct 16-bit kernel: the same body on the compacted records of sparta_vbs_set_live_forward
 //   k_h16_a8.hip      the a8 form of the direct 16-bit kernel (fp8 e4m3 image of A, sparta_vbs_set_forward_a8) and the kernel that quantises the image
+//   k_h16_a8_live.hip the a8 form on the compacted records of live forward (sparta_vbs_set_a8_live) and the kernel that places the exponent words there
+//   k_hub16.hip       the GEMM-shaped kernel for the hub plan of 16-bit handles (the dense part under the fixed 64 x 64 grid)
 //   k_sparse.hip      sparse-row kernels, layout transposes, row-block pack
+//   k_colres.hip      the resident-column product: small fp32 handles whose rows are all sparse rows, columns of B held in LDS
+//   k_union.hip       the MFMA kernels of the column-compacted ("union-pattern") tiles, fp32 and 16-bit
+//   k_sddmm.hip       sampled dense-dense product on a handle's stored blocks (sparta_vbs_sddmm) and its score form (sparta_vbs_sddmm_block_ssq)
 //   k_spmm_t.hip      the transposed product on a handle's own stored blocks (sparta_vbs_spmm_t)
-//   k_update.hip      new values for the images of an updatable handle (sparta_vbs_set_values)
+//   k_update.hip      new values for the images of an updatable handle (sparta_vbs_set_values) and the optimizer steps (sparta_vbs_sgd_step, sparta_vbs_adam_step)
+//   k_gradctl.hip     the control record of gradient clipping and loss scaling (sparta_grad_stats, sparta_grad_ctl_finish)
 //   k_prune.hip       block pruning: per-block sums of squares, zero fill of chosen blocks (sparta_vbs_block_ssq, sparta_vbs_mask_blocks)
 //   k_epilogue.hip    the epilogue of a linear layer: bias, activation, output type, bias gradient (sparta_epilogue_fwd, sparta_epilogue_bwd)
 //   k_live.hip        the live-block set of a handle: stable compaction of the lists sddmm and spmm_t walk (sparta_vbs_set_live_blocks)
-//   vbs_plan.cpp      host: stream plans (step lists, worker ranges, split tiles)
-//   vbs_capi.cpp      host: device image (sparta_vbs), sparta_vbs_create* / sparta_vbs_spmm* (include/sparta_amd.h)
+//   k_repattern.hip   values and optimizer state moved from one handle's layout to another's (sparta_vbs_move_blocks)
+//   k_dense.hip       a dense matrix and the stored blocks of a handle: block scores, gather, scatter (sparta_dense_block_ssq, sparta_vbs_gather_dense / _scatter_dense)
+//   vbs_plan.cpp      host: stream plans (step lists, worker ranges, split tiles), hub plan, packed plan, block table
+//   vbs_union.cpp     host: the device form of the column-compacted tiles
+//   vbs_capi.cpp      host: device image (sparta_vbs) and the sparta_vbs_* entries that make HIP calls: create, the products, the training steps, pruning, the live set
+//   vbs_host_check.cpp host: the entries that make no HIP call (sparta_*_host_check, sparta_vbs_*_host, the packing and quantising rules)
+//   vbs_epilogue.cpp  host: sparta_epilogue_fwd / _bwd / _scratch_bytes
+//   (vbs_host.hpp: what the files of the entry points share among themselves; the other host files -- capi.cpp, reorder.cpp, vbs_build.cpp, io.cpp -- see host_core.hpp only)
 // Every kernel TU exports plain launch functions (namespace sparta_dev); the host TUs never see a __global__ symbol.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -350,7 +362,7 @@ constexpr int kDenseChunk = 64;
 
 // the epilogue of a linear layer (k_epilogue.hip): column-major rows x n_cols operands.  A work item = a tile of kThreads rows x a run of kEpRun columns.
 // Rows [head, head + 4 n4) are the body (vec_tiles tiles, a lane owns four rows: every operand is aligned there in every column), the others the edge
-// (edge_tiles tiles, one element per access); ep_plan (vbs_capi.cpp) fills the four.  dY / Out: the types are the kernels' template arguments.
+// (edge_tiles tiles, one element per access); ep_plan (vbs_epilogue.cpp) fills the four.  dY / Out: the types are the kernels' template arguments.
 constexpr int kEpRun = 32, kEpNone = 0, kEpRelu = 1, kEpGelu = 2;
 struct EpilogueParams {
     const void* dY;                 // backward only
@@ -427,7 +439,7 @@ private:
     size_t bytes_ = 0;
 };
 
-// set for the duration of a call whose stream is being captured into a graph (CaptureScope, vbs_capi.cpp): what allocates, synchronises or times then
+// set for the duration of a call whose stream is being captured into a graph (CaptureScope, vbs_host.hpp): what allocates, synchronises or times then
 // fails with SPARTA_ERR_UNSUPPORTED instead of breaking the capture
 inline thread_local bool g_capturing = false;
 inline int capture_refusal(const char* what, const char* entry = "sparta_vbs_spmm") {
@@ -436,7 +448,7 @@ inline int capture_refusal(const char* what, const char* entry = "sparta_vbs_spm
 }
 
 // what a handle keeps for the graphs captured from its calls (sparta_vbs::retired): `captured` is set when a call under capture returns SPARTA_OK
-// (CaptureScope, vbs_capi.cpp); from then on a launch baked into a graph may hold the address of any scratch, so scratch that has to grow is moved here
+// (CaptureScope, vbs_host.hpp); from then on a launch baked into a graph may hold the address of any scratch, so scratch that has to grow is moved here
 // instead of being freed.  Freed with the handle; every buffer is smaller than its successor.
 struct Retired {
     bool captured = false;
