@@ -329,6 +329,20 @@ int sparta_vbs_plan_stats(int64_t rows, int64_t cols, const int64_t* rowptr, con
  * A once the no-barrier kernel carries its products keeps both images.  sparta_debug_device_allocs counts all of it; a handle that is never captured
  * frees and reallocates as before.
  *
+ * WHERE A DEVICE OPERAND MAY START (SPARTA_PTR_DEVICE; tests/test_footprint_gpu.py runs the products at offset bases inside guarded arenas).
+ *   fp32 operands -- B, C, X, Y, G, Ct and mab of sparta_vbs_spmm, _gathered, _gathered_ld, _prepared, sparta_vbs_prepare_b, sparta_vbs_sddmm,
+ *   sparta_vbs_spmm_t and sparta_vbs_set_values -- may start on ANY 4-byte boundary and have any leading dimension the entry accepts: a slice of a
+ *   larger buffer is a valid operand.  Wider alignment only selects faster code (non-temporal stores of C when ldc % 32 == 0 and C is 128-byte aligned,
+ *   16-byte vectors in the resident-column and sparse-row kernels, a row-major B read in place by the column-compacted tiles when its rows are 16-byte
+ *   aligned); the result has the same bits either way, and nothing outside the defined elements of an output is written.
+ *   16-bit operands -- B of sparta_vbs_spmm, _gathered, _gathered_ld and sparta_vbs_prepare_b, X and Y of sparta_vbs_sddmm, X of sparta_vbs_spmm_t --
+ *   must start on a 4-byte boundary (an EVEN element), as their leading dimensions must be even: the forward kernels read B a dword and more at a time,
+ *   some straight into LDS.  A base on an odd element is refused before anything is launched, with the code the entry uses for an odd leading dimension
+ *   (SPARTA_ERR_UNSUPPORTED from the forward products and sparta_vbs_prepare_b, SPARTA_ERR_INVALID from sparta_vbs_sddmm and sparta_vbs_spmm_t); the
+ *   outputs keep every bit.  The one exception is sparta_vbs_sddmm_block_ssq: its X and Y may start on ANY element (2-byte boundary) -- its kernel reads X
+ *   one element at a time and tests the address of Y itself before it takes 16-byte loads (tests/test_sddmm_score_gpu.py: test_operand_placement holds it
+ *   to the bits of the aligned call).
+ *
  * WHAT AN OUTPUT ELEMENT DEPENDS ON (non-finite operands included: Inf and NaN are ordinary data, and 0 * Inf is NaN, so "multiplied by a zero"
  * is not "not read"; tests/test_poison_gpu.py).
  *   Forward products (sparta_vbs_spmm, _gathered, _gathered_ld, _prepared, SPARTA_SPMM_EXACT, sparta_vbs_spmm_ba on B^T): C[i, j] depends only on

@@ -1788,6 +1788,9 @@ int spmm_impl(sparta_vbs_t* A, const void* B, int64_t ldb, int32_t b_layout, int
     if (ldc < (c_layout == SPARTA_COL_MAJOR ? A->rows : (int64_t)n_cols)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_spmm: ldc too small");
     if (algo != SPARTA_SPMM_MFMA && algo != SPARTA_SPMM_EXACT) return fail(SPARTA_ERR_INVALID, "sparta_vbs_spmm: bad algo");
     if (ptr_space != SPARTA_PTR_HOST && ptr_space != SPARTA_PTR_DEVICE) return fail(SPARTA_ERR_INVALID, "sparta_vbs_spmm: bad ptr_space");
+    // (the 16-bit kernels read B a dword and more at a time, some straight into LDS: an odd-element base is refused like an odd ldb, before anything is launched)
+    if (A->dtype != SPARTA_F32 && ptr_space == SPARTA_PTR_DEVICE && ((uintptr_t)B % 4) != 0)
+        return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_spmm: 16-bit B must start on a 4-byte boundary (16-byte loads start on 4-byte boundaries)");
 
     const DeviceCall call{"sparta_vbs_spmm", A, (hipStream_t)stream, ptr_space == SPARTA_PTR_DEVICE, dt_ms, "the product"};
     return open_call(call, [&](hipStream_t st) {
@@ -2056,6 +2059,8 @@ int sparta_vbs_prepare_b(sparta_vbs_t* A, const void* B, int64_t ldb, int64_t sh
     if (shard_rows != 0 && (shard_rows < 0 || shard_rows % A->w != 0 || A->cols % shard_rows != 0 || shard_ld < shard_rows ||
                             shard_stride < shard_ld * (int64_t)(n_cols - 1) + shard_rows))
         return fail(SPARTA_ERR_INVALID, "sparta_vbs_prepare_b: bad gathered layout");
+    if (A->dtype != SPARTA_F32 && ((uintptr_t)B % 4) != 0)          // (as sparta_vbs_spmm refuses it: the copy made below and every later product read B a dword and more at a time)
+        return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_prepare_b: 16-bit B must start on a 4-byte boundary");
     if (g_capturing) return capture_refusal("prepare a copy of B");
     DeviceGuard guard(A->device);
     // owned by `hold` until it is handed to the caller (the guard above outlives it: the copy is freed with the handle's device current)
@@ -2187,6 +2192,8 @@ int sddmm_impl(sparta_vbs_t* A, const void* X, int64_t ldx, const void* Y, int64
     if (ldx > (INT64_C(1) << 61) / k || ldy > (INT64_C(1) << 61) / k) return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_sddmm: ldx * k or ldy * k beyond 2^61");
     const bool h16 = A->dtype != SPARTA_F32;
     if (h16 && ptr_space == SPARTA_PTR_DEVICE && ((ldx | ldy) & 1)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_sddmm: 16-bit handles need even ldx, ldy");
+    if (h16 && ptr_space == SPARTA_PTR_DEVICE && (((uintptr_t)X | (uintptr_t)Y) % 4) != 0)
+        return fail(SPARTA_ERR_INVALID, "sparta_vbs_sddmm: 16-bit X and Y must start on 4-byte boundaries");
     if (A->ext_sparse)
         return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_sddmm: the handle does not hold the dense blocks of every block-row (made by sparta_vbs_create_from_csr)");
 
@@ -3396,6 +3403,7 @@ int spmm_t_impl(sparta_vbs_t* A, const void* X, int64_t ldx, int32_t n_cols, flo
     if (ldx > (INT64_C(1) << 61) / n_cols || ldo > (INT64_C(1) << 61) / n_cols) return fail(SPARTA_ERR_UNSUPPORTED, "sparta_vbs_spmm_t: ldx * n_cols or ldo * n_cols beyond 2^61");
     const bool h16 = A->dtype != SPARTA_F32;
     if (h16 && ptr_space == SPARTA_PTR_DEVICE && (ldx & 1)) return fail(SPARTA_ERR_INVALID, "sparta_vbs_spmm_t: 16-bit handles need an even ldx");
+    if (h16 && ptr_space == SPARTA_PTR_DEVICE && ((uintptr_t)X % 4) != 0) return fail(SPARTA_ERR_INVALID, "sparta_vbs_spmm_t: 16-bit X must start on a 4-byte boundary");
 
     const DeviceCall call{"sparta_vbs_spmm_t", A, (hipStream_t)stream, ptr_space == SPARTA_PTR_DEVICE, dt_ms, "the product", A->ev0, A->ev1};
     return open_call(call, [&](hipStream_t st) -> int {
